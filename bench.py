@@ -4,13 +4,13 @@
 A step = one pass of the hot path (fused warp + variance cost volume -> 3-D U-Net regularisation ->
 softmax / depth regression / confidence) over one batch of synthetic input that is already resident in
 HBM: BASELINE.json configs[1] = MVSNet, 1 ref + 4 src views, 512x640 images (128x160x32 feature maps),
-D = 192 planes, bf16 storage / fp32 accumulation (--dtype bf16, the default since round 6; fp16 is measured too and reported under "alt").
+D = 192 planes, bf16 storage / fp32 accumulation (--dtype bf16, the default since round 6; fp16 is measured too with --full and reported under "alt").
 3 932 160 cost-volume voxels per reference view; a batch is --batch reference views (default 3, each with its own source views).
 --batch-mode views (default): one single-branch hipGraph per view, each replayed on its own HIP stream, consecutive steps not joined
 (wild_deep_mvs_amd.graph.ViewPipeline); --batch-mode streams (rounds 3-5): ONE hipGraph whose views are parallel branches;
 --batch-mode batched: one launch per layer for the whole batch on one stream, replayed as a hipGraph; --batch 1 = one view at a time as in
-rounds 1-2, also reported in every line.  The timed region (exactly --steps steps between barrier + synchronize) runs --repeats times
-(default 5); the line reports the median region and min / median / max.
+rounds 1-2, also reported in every --full line.  The timed region (exactly --steps steps between barrier + synchronize) runs --repeats times
+(default 1; 5 with --full); the line reports the median region and min / median / max.
 
 Multi-GPU (--gpus N, one process per GPU): reference views are independent objects, so each rank sweeps its own
 view (global batch = N) with no data-path collective -> weak scaling.  Ranks come either from a launcher
@@ -18,9 +18,14 @@ view (global batch = N) with no data-path collective -> weak scaling.  Ranks com
 environment) or, when WORLD_SIZE is unset, from bench.py itself (`python bench.py --gpus N` spawns its N ranks the
 way the reference's train.py / depthmap_eval.py do with mp.spawn).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype and ms_per_step (milliseconds of one timed step).  A
+plain run does only what that line needs: set-up, warm-up, the timed steps, the line.  --dump-outputs DIR writes what the timed path
+returned in its last step (depth and confidence maps, float32 .npy) for output-by-output comparisons of two builds.  --full adds
+everything else the benchmark measures and checks, after the headline region:
   roofline     the dominant kernel's achieved algorithmic GB/s vs the HBM peak (HIP events on the launch stream)
   cpu_baseline the CPU oracle (a port of the reference's PyTorch path) timed on this box's host cores
+and the other 16-bit format ("alt"), per-kernel times, the replay-vs-eager check, the DTU-like rig, BASELINE configurations 1-5,
+the training step and, with --gpus N > 1, the sharded legs.
 """
 from __future__ import annotations
 
@@ -68,6 +73,7 @@ MFMA_PEAK_TFLOPS = 2500.0   # dense bf16 / fp16 MFMA peak of one MI355X (MI355X_
 
 
 DTYPES = {"f16": torch.float16, "bf16": torch.bfloat16}
+WARM_S = 0.25               # least seconds of warm-up replays on the timed path before the clock starts
 
 
 def pmc_traffic(name: str):
@@ -103,7 +109,7 @@ def live_traffic(dtype_name: str, timeout_s: int = 150):
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs",
            "--eager", "--no-live-traffic", "--batch", "1", "--dtype", dtype_name]
     try:
         for sub, counter in (("pmc_fetch", "FETCH_SIZE"), ("pmc_write", "WRITE_SIZE")):
@@ -482,10 +488,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-sharded", action="store_true", help="N > 1: skip the depth-plane / source-view sharded legs (configurations 3 and 5)")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default="bf16",
                     help="16-bit HBM storage format of the headline line (arithmetic is fp32): bf16 = the format BASELINE.json configuration 2 "
-                         "names; the other format is measured too and reported under \"alt\"")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region (exactly --steps steps between barrier + synchronize) is run this "
-                    "many times; the line's value / ms_per_step is the MEDIAN region, min / median / max are in \"repeats\"")
-    ap.add_argument("--dump-events", default=None, help="write every per-launch event duration to this file")
+                         "names; with --full the other format is measured too and reported under \"alt\"")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (exactly --steps steps between barrier + synchronize) is run this "
+                    "many times (default 1, with --full 5); the line's value / ms_per_step is the MEDIAN region, min / median / max are in \"repeats\"")
+    ap.add_argument("--full", action="store_true", help="after the headline region, also measure and check everything else: the other 16-bit "
+                                                         "format, per-kernel times and rooflines, the replay-vs-eager check, cpu_baseline, the DTU-like "
+                                                         "rig, BASELINE configurations 1-5, the training step, the sharded legs (N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path returned in its last "
+                                                                          "step (depth and confidence maps) to DIR/<name>.npy in float32")
+    ap.add_argument("--dump-events", default=None, help="--full: write every per-launch event duration to this file")
     ap.add_argument("--eager", action="store_true", help="time eager launches instead of hipGraph replays")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="pscv_set_tuning knob (measurement runs)")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 counter passes that measure roofline.traffic "
@@ -495,7 +506,14 @@ def parse_args(argv=None):
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="N > 1: start the ranks, join the process group, run one all-reduce, print a one-line report and exit "
                          "(tests/test_dist_cpu.py drives this with --backend gloo on CPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_events and not args.full:
+        ap.error("--dump-events needs --full (the per-launch events come from the eager pass that --full adds)")
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def _free_port() -> int:
@@ -570,6 +588,23 @@ def sharded_legs_bounded(dist, device, world, rank, budget_s, legs=None):
     return box.get("res"), True
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir: str, outputs: dict, rank: int) -> None:
+    """``--dump-outputs``: every array of ``outputs`` as ``out_dir/<name>.npy`` in float32 (rank r > 0 of an N-GPU run: ``<name>_rank<r>``).
+    Should they exceed DUMP_BYTES_MAX together, each is replaced by the same fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            keep = a.size * DUMP_BYTES_MAX // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def rendezvous(args):
     """(dist module or None, world, rank, local_rank) from RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -633,9 +668,10 @@ def run(args):
     # the views drift out of phase, 0.894-0.907 against 0.918-0.927 ms for the forked graph (profiles/r06_step_schedule.txt)
     views_mode = args.batch_mode == "views" and NB >= 2 and not args.eager
 
-    def timed_region(dtype_name, feats_cl_, steps):
-        """W warm-up steps, then exactly `steps` steps between barrier + synchronize on both sides; then the same steps once
-        more eagerly with a HIP event pair around every launch (per-kernel durations)."""
+    def timed_region(dtype_name, feats_cl_, steps, full):
+        """W warm-up steps, then exactly `steps` steps between barrier + synchronize on both sides; the maps the last timed step
+        returned are kept.  `full`: then the same steps once more eagerly with a HIP event pair around every launch (per-kernel
+        durations), one view at a time, and the replayed step against eager launches on fresh inputs."""
         net.storage_dtype = DTYPES[dtype_name]
 
         def step():
@@ -679,8 +715,15 @@ def run(args):
             # then the remaining warm-up on the path that is timed, then barrier + synchronize, then the clock starts
             gc.collect()
             gc.disable()
-            for _ in range(max(args.warmup, 1) * 8):
-                run()
+            # ... and at least WARM_S of it: with five regions the first two still ran at the ramp (0.910 / 0.909 ms against a median
+            # of 0.893, profiles/r06_bench_line.json); a plain run times one region
+            t_warm = time.perf_counter()
+            while True:
+                for _ in range(max(args.warmup, 1) * 8):
+                    run()
+                torch.cuda.synchronize()
+                if time.perf_counter() - t_warm >= WARM_S:
+                    break
             # the timed region -- exactly `steps` steps between barrier + synchronize on both sides -- `args.repeats` times back to back
             # (box-to-box and run-to-run spread is +-4 %: one region of 20 steps = 19 ms cannot show a 3 % change); every rank times
             # every region, the MAX over ranks is taken per region, the line reports the median region
@@ -691,46 +734,49 @@ def run(args):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(steps):
-                    run()
+                    out = run()
                 if pipe is not None:
                     depth, conf = pipe.results()        # join of the view streams + the last step's maps: inside the timed region
+                elif graph is None:
+                    depth, conf = out                   # eager launches (a replayed graph writes its captured output tensors)
                 torch.cuda.synchronize()
                 if dist is not None:
                     dist.barrier()
                 torch.cuda.synchronize()
                 regions.append(time.perf_counter() - t0)
-            # per-kernel durations: the same launches (every batch item is launched on its own: B = 1 grids), but one item after
-            # the other on ONE stream, so that a kernel's HIP events time it alone rather than beside another item's kernels
+            last = {"depth": depth.clone(), "confidence": conf.clone()}      # what the timed path returned in its last step
+            tm = elapsed_eager = one_view = graph_ok = None
             item = lambda b: net.hot_path([f[b:b + 1] for f in feats_cl_], proj_d[b:b + 1], dv_d[b:b + 1])
-            with ops.EventTimer() as tm:
-                t1 = time.perf_counter()
-                for _ in range(steps):
-                    for b in range(NB):
-                        item(b)
-                torch.cuda.synchronize()
-                elapsed_eager = time.perf_counter() - t1
-            # one view at a time (rounds 1-2's step): a replayed graph of item 0 alone
-            one_view = None
-            if NB > 1 and not args.eager:
-                try:
-                    g1 = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                        item(0)
-                    for _ in range(max(args.warmup, 1) * 8):       # the same warm-up as the headline region: clocks settled on this path
-                        g1.replay()
-                    torch.cuda.synchronize()
-                    t2 = time.perf_counter()
+            if full:
+                # per-kernel durations: the same launches (every batch item is launched on its own: B = 1 grids), but one item after
+                # the other on ONE stream, so that a kernel's HIP events time it alone rather than beside another item's kernels
+                with ops.EventTimer() as tm:
+                    t1 = time.perf_counter()
                     for _ in range(steps):
-                        g1.replay()
+                        for b in range(NB):
+                            item(b)
                     torch.cuda.synchronize()
-                    one_view = (time.perf_counter() - t2) / steps
-                except Exception:   # pragma: no cover
-                    one_view = None
+                    elapsed_eager = time.perf_counter() - t1
+                # one view at a time (rounds 1-2's step): a replayed graph of item 0 alone
+                if NB > 1 and not args.eager:
+                    try:
+                        g1 = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g1, capture_error_mode="thread_local"):
+                            item(0)
+                        for _ in range(max(args.warmup, 1) * 8):       # the same warm-up as the headline region: clocks settled on this path
+                            g1.replay()
+                        torch.cuda.synchronize()
+                        t2 = time.perf_counter()
+                        for _ in range(steps):
+                            g1.replay()
+                        torch.cuda.synchronize()
+                        one_view = (time.perf_counter() - t2) / steps
+                    except Exception:   # pragma: no cover
+                        one_view = None
             gc.enable()
             # the replayed (forked) graph on FRESH inputs against eager one-item launches on one stream, bit for bit: a fast step
             # that replays wrongly must not yield a headline (round 3 saw that with the packed warp build)
-            graph_ok = None
-            if graph is not None:
+            if full and graph is not None:
                 saved = [f.clone() for f in feats_cl_]
                 for f in feats_cl_:
                     f.copy_(torch.roll(f, shifts=(3, 5), dims=(1, 2)))
@@ -762,71 +808,76 @@ def run(args):
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
         regions = [float(x) for x in t_max.tolist()]
         elapsed = sorted(regions)[(len(regions) - 1) // 2]           # the median region (lower median for an even count)
-        return elapsed, tm, depth.clone(), graph is not None, elapsed_eager, one_view, graph_ok, regions
+        return elapsed, tm, depth.clone(), graph is not None, elapsed_eager, one_view, graph_ok, regions, last
 
-    elapsed, tm, depth, graphed, elapsed_eager, one_view, graph_ok, regions = timed_region(args.dtype, feats_cl, args.steps)
-    kern = {k: v for k, v in tm.summary().items() if k != "proj_cams"}
-    if args.dump_events and rank == 0:
-        with open(args.dump_events, "w") as f:
-            for name, e0, e1 in tm.records:
-                f.write(f"{name}\t{e0.elapsed_time(e1) * 1e3:.1f}\n")
-    # the other 16-bit storage format on the same workload (BASELINE.json names bf16; same bytes, same MFMA rate)
+    elapsed, tm, depth, graphed, elapsed_eager, one_view, graph_ok, regions, last = timed_region(args.dtype, feats_cl, args.steps, args.full)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
     alt_name = "bf16" if args.dtype == "f16" else "f16"
-    feats_alt = [ops.to_channels_last(feats[i].to(device), DTYPES[alt_name]) for i in range(V)]
-    alt_elapsed, alt_tm, alt_depth, _, _, alt_one_view, _, alt_regions = timed_region(alt_name, feats_alt, args.steps)
-    net.storage_dtype = DTYPES[args.dtype]
     graph = graphed
+    if args.full:
+        kern = {k: v for k, v in tm.summary().items() if k != "proj_cams"}
+        if args.dump_events and rank == 0:
+            with open(args.dump_events, "w") as f:
+                for name, e0, e1 in tm.records:
+                    f.write(f"{name}\t{e0.elapsed_time(e1) * 1e3:.1f}\n")
+        # the other 16-bit storage format on the same workload (BASELINE.json names bf16; same bytes, same MFMA rate)
+        feats_alt = [ops.to_channels_last(feats[i].to(device), DTYPES[alt_name]) for i in range(V)]
+        alt_elapsed, alt_tm, alt_depth, _, _, alt_one_view, _, alt_regions, _ = timed_region(alt_name, feats_alt, args.steps, True)
+        net.storage_dtype = DTYPES[args.dtype]
 
     sharded, sharded_done = None, True
-    if world > 1 and not args.no_sharded:
+    if world > 1 and args.full and not args.no_sharded:
         sharded, sharded_done = sharded_legs_bounded(dist, device, world, rank, args.sharded_budget)
 
     if rank == 0:
-        total_ms = sum(ms for _, ms in kern.values())
-        name, (n, ms) = max(kern.items(), key=lambda kv: kv[1][1])
-        avg_s = ms / n * 1e-3
-        ab = algorithmic_bytes(name)
-        traffic, traffic_source = pmc_traffic(name)
-        if world == 1 and not args.no_live_traffic:
-            live, note = live_traffic(args.dtype)
-            hit = [v for k, v in (live or {}).items() if name.startswith(k)]
-            if hit:
-                traffic, traffic_source = hit[0], note
-            else:
-                traffic_source = f"{traffic_source} (live capture unavailable: {note})"
-        roof = {"kernel": name, "bound": "hbm", "achieved": ab / avg_s / 1e9 if ab else None, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": (ab / avg_s / 1e9 / HBM_PEAK_GBS) if ab else None,
-                "traffic": traffic, "traffic_source": traffic_source,
-                "avg_us": avg_s * 1e6, "algorithmic_bytes": ab, "share_of_gpu_time": ms / total_ms}
-        # the matrix-core side of the path (north_star: "MFMA utilisation on the 3D conv against gfx950 peak"): the layer with
-        # 68 % of the regulariser's FLOPs, conv0 32 -> 8 at full resolution (2 * 27 * 32 * 8 FLOP per voxel).  Per layer it is
-        # HBM-bound at these channel counts (arithmetic intensity 173 FLOP/B < ridge), so both fractions are given.
-        roof_mfma = None
-        c0 = [k for k in kern if k.startswith("conv3d[32->8,k")]
-        if c0:
-            n0, ms0 = kern[c0[0]]
-            t0s = ms0 / n0 * 1e-3
-            fl = 2.0 * 27 * 32 * 8 * VOX
-            roof_mfma = {"kernel": c0[0], "bound": "mfma", "achieved": fl / t0s / 1e12, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": fl / t0s / 1e12 / MFMA_PEAK_TFLOPS, "avg_us": t0s * 1e6, "flops": fl,
-                         "hbm_frac": algorithmic_bytes(c0[0]) / t0s / 1e9 / HBM_PEAK_GBS}
-        # how much of the sweep the rig gives away: share of the (workgroup, source view) pairs whose source box lies outside the
-        # source image (the view contributes 0 there and the LDS-staged kernel skips it); the DTU-like rig of `alt_geometry` has 0.03
         zero_note = ""
-        try:
-            zs = staging_modes(device, DTYPES[args.dtype], "probe")[0]
-            zero_note = (f" ({zs['ZERO']:.2f} of its (tile, plane chunk, source view) pairs project outside the source image and are skipped; "
-                         "the DTU-like rig -- alt_geometry.dtu / value_dtu_rig -- has 0.03)")
-        except Exception as e:   # pragma: no cover
-            zero_note = f" (staging-mode histogram unavailable: {type(e).__name__})"
+        if args.full:
+            total_ms = sum(ms for _, ms in kern.values())
+            name, (n, ms) = max(kern.items(), key=lambda kv: kv[1][1])
+            avg_s = ms / n * 1e-3
+            ab = algorithmic_bytes(name)
+            traffic, traffic_source = pmc_traffic(name)
+            if world == 1 and not args.no_live_traffic:
+                live, note = live_traffic(args.dtype)
+                hit = [v for k, v in (live or {}).items() if name.startswith(k)]
+                if hit:
+                    traffic, traffic_source = hit[0], note
+                else:
+                    traffic_source = f"{traffic_source} (live capture unavailable: {note})"
+            roof = {"kernel": name, "bound": "hbm", "achieved": ab / avg_s / 1e9 if ab else None, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": (ab / avg_s / 1e9 / HBM_PEAK_GBS) if ab else None,
+                    "traffic": traffic, "traffic_source": traffic_source,
+                    "avg_us": avg_s * 1e6, "algorithmic_bytes": ab, "share_of_gpu_time": ms / total_ms}
+            # the matrix-core side of the path (north_star: "MFMA utilisation on the 3D conv against gfx950 peak"): the layer with
+            # 68 % of the regulariser's FLOPs, conv0 32 -> 8 at full resolution (2 * 27 * 32 * 8 FLOP per voxel).  Per layer it is
+            # HBM-bound at these channel counts (arithmetic intensity 173 FLOP/B < ridge), so both fractions are given.
+            roof_mfma = None
+            c0 = [k for k in kern if k.startswith("conv3d[32->8,k")]
+            if c0:
+                n0, ms0 = kern[c0[0]]
+                t0s = ms0 / n0 * 1e-3
+                fl = 2.0 * 27 * 32 * 8 * VOX
+                roof_mfma = {"kernel": c0[0], "bound": "mfma", "achieved": fl / t0s / 1e12, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": fl / t0s / 1e12 / MFMA_PEAK_TFLOPS, "avg_us": t0s * 1e6, "flops": fl,
+                             "hbm_frac": algorithmic_bytes(c0[0]) / t0s / 1e9 / HBM_PEAK_GBS}
+            # how much of the sweep the rig gives away: share of the (workgroup, source view) pairs whose source box lies outside the
+            # source image (the view contributes 0 there and the LDS-staged kernel skips it); the DTU-like rig of `alt_geometry` has 0.03
+            zero_note = ""
+            try:
+                zs = staging_modes(device, DTYPES[args.dtype], "probe")[0]
+                zero_note = (f" ({zs['ZERO']:.2f} of its (tile, plane chunk, source view) pairs project outside the source image and are skipped; "
+                             "the DTU-like rig -- alt_geometry.dtu / value_dtu_rig -- has 0.03)")
+            except Exception as e:   # pragma: no cover
+                zero_note = f" (staging-mode histogram unavailable: {type(e).__name__})"
         line = {
             "metric": "cost-volume voxels/sec (BxDxHxW), MVSNet hot path", "value": world * NB * VOX * args.steps / elapsed,
             "unit": "voxels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "dtype_note": "16-bit HBM storage and MFMA operands, fp32 accumulation.  bf16 is the format BASELINE.json configuration 2 names "
-                          "(the default of this script since round 6); the other 16-bit format (same bytes, same MFMA rate) is measured in the "
-                          "same run and reported under \"alt\" with its own depth error",
+                          "(the default of this script since round 6); with --full the other 16-bit format (same bytes, same MFMA rate) is "
+                          "measured in the same run and reported under \"alt\" with its own depth error",
             "repeats": {"n": len(regions), "steps_per_region": args.steps, "ms_per_step_min": min(regions) / args.steps * 1e3,
                         "ms_per_step_median": elapsed / args.steps * 1e3, "ms_per_step_max": max(regions) / args.steps * 1e3,
                         "ms_per_step_all": [round(r / args.steps * 1e3, 4) for r in regions],
@@ -838,66 +889,69 @@ def run(args):
                        "voxels_per_step_per_gpu": NB * VOX, "parallelism": f"reference-view shard x{world}, no collective",
                        "batch_mode": ("one view" if NB == 1 else args.batch_mode if (views_mode or args.batch_mode != "views") else
                                       "batched (eager: --batch-mode views needs graph replay)"),
-                       # like-for-like with rounds 1-2 (whose step was ONE reference view): the same path, one view per replay
+                       # like-for-like with rounds 1-2 (whose step was ONE reference view): the same path, one view per replay (--full)
                        "one_view_at_a_time_ms": None if one_view is None else one_view * 1e3,
                        "one_view_at_a_time_voxels_per_s": None if one_view is None else world * VOX / one_view},
             "timing": ("hipGraph replay of the step" if graph else "eager launches") +
                       (f"; a step = one replay of each of {NB} single-branch hipGraphs (one per reference view), each on its own HIP stream; "
                        "consecutive steps are not joined, so the views drift out of phase and one view's warp runs beside another's U-Net "
                        "(wild_deep_mvs_amd.graph.ViewPipeline; the join of the streams and the last step's depth maps are inside the timed "
-                       "region); a step is SHORTER than the sum of its kernels' stand-alone durations below" if views_mode else
+                       "region); a step is SHORTER than the sum of its kernels' stand-alone durations (kernels_us, --full)" if views_mode else
                        f"; the {NB} views of a step run on {NB} HIP streams forked inside the replayed graph: one view's vector-ALU-bound warp "
                        "beside another's MFMA / memory-bound U-Net (MVSNet._hot_path_streams), so a step is SHORTER than the sum of its "
-                       "kernels' stand-alone durations below" if streams_mode else
+                       "kernels' stand-alone durations (kernels_us, --full)" if streams_mode else
                        f"; the {NB} views of a step share ONE launch per layer (batched grids, one stream)" if NB > 1 else "") +
-                      f"; kernels_us / roofline: HIP events of an eager pass of the same {args.steps} steps, one view after the other on one "
-                      f"stream (each launch timed alone; {elapsed_eager / args.steps * 1e3:.3f} ms/step that way)",
-            "one_view_at_a_time": None if one_view is None else {"ms_per_view": one_view * 1e3, "value": world * VOX / one_view, "unit": "voxels/s",
-                                                                 "what": "the step of rounds 1-2: one reference view per replay on one stream"},
-            "graph_replay_equals_eager_on_fresh_inputs": graph_ok,
-            "value_dtu_rig": None,   # filled below: the same step on the DTU-like camera rig (alt_geometry)
-            "value_bf16": None,      # filled below: the same step in bf16 storage, the format BASELINE configuration 2 names
-            "roofline": roof,
-            "roofline_mfma": roof_mfma,
-            "kernels_us": {k: round(ms / n * 1e3, 2) for k, (n, ms) in sorted(kern.items(), key=lambda kv: -kv[1][1])},
+                      (f"; kernels_us / roofline: HIP events of an eager pass of the same {args.steps} steps, one view after the other on one "
+                       f"stream (each launch timed alone; {elapsed_eager / args.steps * 1e3:.3f} ms/step that way)" if args.full else ""),
         }
-        alt_kern = {k: v for k, v in alt_tm.summary().items() if k != "proj_cams"}
-        line["alt"] = {"dtype": alt_name, "value": world * NB * VOX * args.steps / alt_elapsed, "unit": "voxels/s",
-                       "one_view_at_a_time_ms": None if alt_one_view is None else alt_one_view * 1e3,
-                       "ms_per_step": alt_elapsed / args.steps * 1e3, "ms_per_step_all": [round(r / args.steps * 1e3, 4) for r in alt_regions],
-                       "kernels_us": {k: round(ms / n * 1e3, 2) for k, (n, ms) in sorted(alt_kern.items(), key=lambda kv: -kv[1][1])}}
-        line["value_bf16"] = line["alt"]["value"] if alt_name == "bf16" else line["value"]
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"], rel = cpu_baseline(sd, feats, proj, dv, {args.dtype: depth, alt_name: alt_depth})
-            line["depth_rel_l1_vs_oracle"] = rel[args.dtype]
-            line["alt"]["depth_rel_l1_vs_oracle"] = rel[alt_name]
-        else:
-            line["cpu_baseline"] = None
-        # all five BASELINE configurations in their single-GPU forms (parity cases of tests/test_gpu_fullsize.py, not bench lines):
-        # driver-timed ms of the full forward() called like the reference's scripts call it (in-forward hipGraph replay and eager),
-        # with the three heaviest kernels of each against their rooflines; after the headline region
-        line["alt_geometry"] = None
-        if world == 1 and not args.no_other_configs:
-            try:
-                line["alt_geometry"] = geometry_probe(net, device, DTYPES[args.dtype], nb=NB, views=views_mode)
-                line["value_dtu_rig"] = (line["alt_geometry"].get("dtu") or {}).get("value")
-            except Exception as e:   # pragma: no cover
-                line["alt_geometry"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        line["sharded"] = sharded
-        line["other_configs"] = None
-        if world == 1 and not args.no_other_configs:
-            try:
-                sys.path.insert(0, os.path.join(REPO, "scripts"))
-                import run_configs
-                line["other_configs"] = [run_configs.time_config(c) for c in (1, 2, 3, 4, 5)]
-            except Exception as e:   # pragma: no cover  (never lose the headline line to a side measurement)
-                line["other_configs"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        # row f-1 of the scope table (the backward of the path): one MVSNet training step at the headline size, forward in train() +
-        # loss.backward() + Adam, with the PyTorch-ROCm 2-D extractor (the default) and with the extractor on the engine too; each in
-        # its own process (scripts/bench_train.py), after the headline region
-        line["training"] = None
-        if world == 1 and not args.no_training and not args.no_other_configs:      # (measurement children pass --no-other-configs)
-            line["training"] = training_steps()
+        line["value_bf16"] = line["value"] if args.dtype == "bf16" else None     # the format BASELINE configuration 2 names (f16: from "alt", --full)
+        if args.full:
+            line.update({
+                "one_view_at_a_time": None if one_view is None else {"ms_per_view": one_view * 1e3, "value": world * VOX / one_view, "unit": "voxels/s",
+                                                                     "what": "the step of rounds 1-2: one reference view per replay on one stream"},
+                "graph_replay_equals_eager_on_fresh_inputs": graph_ok,
+                "value_dtu_rig": None,   # filled below: the same step on the DTU-like camera rig (alt_geometry)
+                "roofline": roof,
+                "roofline_mfma": roof_mfma,
+                "kernels_us": {k: round(ms / n * 1e3, 2) for k, (n, ms) in sorted(kern.items(), key=lambda kv: -kv[1][1])},
+            })
+            alt_kern = {k: v for k, v in alt_tm.summary().items() if k != "proj_cams"}
+            line["alt"] = {"dtype": alt_name, "value": world * NB * VOX * args.steps / alt_elapsed, "unit": "voxels/s",
+                           "one_view_at_a_time_ms": None if alt_one_view is None else alt_one_view * 1e3,
+                           "ms_per_step": alt_elapsed / args.steps * 1e3, "ms_per_step_all": [round(r / args.steps * 1e3, 4) for r in alt_regions],
+                           "kernels_us": {k: round(ms / n * 1e3, 2) for k, (n, ms) in sorted(alt_kern.items(), key=lambda kv: -kv[1][1])}}
+            line["value_bf16"] = line["alt"]["value"] if alt_name == "bf16" else line["value"]
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"], rel = cpu_baseline(sd, feats, proj, dv, {args.dtype: depth, alt_name: alt_depth})
+                line["depth_rel_l1_vs_oracle"] = rel[args.dtype]
+                line["alt"]["depth_rel_l1_vs_oracle"] = rel[alt_name]
+            else:
+                line["cpu_baseline"] = None
+            # all five BASELINE configurations in their single-GPU forms (parity cases of tests/test_gpu_fullsize.py, not bench lines):
+            # driver-timed ms of the full forward() called like the reference's scripts call it (in-forward hipGraph replay and eager),
+            # with the three heaviest kernels of each against their rooflines; after the headline region
+            line["alt_geometry"] = None
+            if world == 1 and not args.no_other_configs:
+                try:
+                    line["alt_geometry"] = geometry_probe(net, device, DTYPES[args.dtype], nb=NB, views=views_mode)
+                    line["value_dtu_rig"] = (line["alt_geometry"].get("dtu") or {}).get("value")
+                except Exception as e:   # pragma: no cover
+                    line["alt_geometry"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            line["sharded"] = sharded
+            line["other_configs"] = None
+            if world == 1 and not args.no_other_configs:
+                try:
+                    sys.path.insert(0, os.path.join(REPO, "scripts"))
+                    import run_configs
+                    line["other_configs"] = [run_configs.time_config(c) for c in (1, 2, 3, 4, 5)]
+                except Exception as e:   # pragma: no cover  (never lose the headline line to a side measurement)
+                    line["other_configs"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            # row f-1 of the scope table (the backward of the path): one MVSNet training step at the headline size, forward in train() +
+            # loss.backward() + Adam, with the PyTorch-ROCm 2-D extractor (the default) and with the extractor on the engine too; each in
+            # its own process (scripts/bench_train.py), after the headline region
+            line["training"] = None
+            if world == 1 and not args.no_training and not args.no_other_configs:      # (measurement children pass --no-other-configs)
+                line["training"] = training_steps()
         print(json.dumps(line), flush=True)
     if not sharded_done:        # a wedged process group: nothing more can be agreed on; every rank leaves on its own
         sys.stdout.flush()
