@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSCV_ABI_VERSION 9
+#define PSCV_ABI_VERSION 10
 
 /* storage dtypes */
 #define PSCV_F32 0
@@ -357,6 +357,34 @@ int pscv_conv2d_ex(const void* in, int dtype, const uint16_t* packed, const floa
 int pscv_geo_filter(const float* depth, const float* const* src_depth, const int* src_hw, int n_src, const float* cams,
                     int h, int w, float max_reproj_error, float depth_threshold, float min_tri_angle, int num_consistent,
                     unsigned char* mask_depth, unsigned char* mask_disp, unsigned char* geo_mask, int* counts, void* stream);
+
+/*
+ * Consistency fusion of filtered depth maps into one point cloud (ABI 10; the step after the geometric filter).  Replaces the
+ * external fusibile binary that evaluation/fusibile.py:160-181 runs (its normal test off: normal_thresh = 360 with constant normals).
+ * One call = one pass i over the pixels of view i; the caller runs passes 0 .. n_views-1 in order on one stream.  Rule (INTEGRATION.md
+ * section 2d): a pixel p of view i with a valid depth (finite, depth_min < d < depth_max) and used_i(p) = 0 is unprojected to X; every
+ * other view j, in ascending order, projects X to z > 0 and the pixel q = floor(a/z + 0.5, b/z + 0.5) inside view j with a valid depth
+ * d_j(q), and is consistent when |f_i B/z - f_i B/d_j(q)| < disp_thresh (f_i = K_i[0,0], B = |c_i - c_j|, c = -R^T t).  With
+ * n >= num_consistent consistent views the pass emits the mean of X and their unprojected pixels, the rounded mean colour, and sets
+ * used_j(q) = 1 for each of them.
+ *   depth       host array of n_views device pointers, fp32 [hw[2v], hw[2v+1]] (sizes may differ); masked pixels hold 0
+ *   color       host array of n_views device pointers, RGBA8 packed in 32 bits [h_v, w_v] (red in the low byte; alpha ignored)
+ *   used        host array of n_views device pointers, uint8 [h_v, w_v], 0 / 1; pass i reads used_i and writes used_j, j != i
+ *   cams        device fp32 [n_views][PSCV_GEO_CAM_FLOATS] (pscv_geo_filter's blocks: K, K^-1, R, t; intrinsics at each map's size)
+ *   out_xyz     device fp32 [capacity][3], out_rgb uint8 [capacity][3]; out_view, out_pixel int32 [capacity] (each may be NULL):
+ *               the view and the pixel index y w + x the point was emitted from
+ *   counter     device int64: running number of points (0 before pass 0).  Points go to out[counter ...] in row-major pixel order;
+ *               the counter advances by the pass's full count even past capacity, and nothing at or beyond capacity is written,
+ *               so counter > capacity after the last pass means the buffer was too small (the caller's error)
+ *   workspace   device scratch of pscv_fuse_depth_workspace(h_i, w_i) bytes (at least that of the largest view for a whole run)
+ * No host synchronisation: three launches on `stream` (fuse, scan, scatter); the result is bit-reproducible.
+ */
+#define PSCV_FUSE_MAX_VIEWS 64
+long pscv_fuse_depth_workspace(int h, int w);
+int pscv_fuse_depth_pass(int pass, const float* const* depth, const unsigned int* const* color, unsigned char* const* used,
+                         const int* hw, int n_views, const float* cams, float disp_thresh, int num_consistent, float depth_min,
+                         float depth_max, float* out_xyz, unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity,
+                         long long* counter, void* workspace, long workspace_bytes, void* stream);
 
 /*
  * Softmax over the depth axis + expectation(s), fused.

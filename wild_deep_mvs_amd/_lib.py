@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("PSCV_LIB") or os.path.join(_HERE, "libpscv.so")     #
 CSRC = os.path.join(_HERE, "csrc")
 
 # mirror of include/pscv.h
-ABI_VERSION = 9
+ABI_VERSION = 10
 F32, BF16, F16 = 0, 1, 2
 GEOM_PROJ, GEOM_HOMOG = 0, 1
 COST_VARIANCE, COST_VARIANCE_CVP, COST_SOFTMIN, COST_GROUPCORR, COST_WARP_ONLY, COST_VARIANCE_PARTIAL = 0, 1, 2, 3, 4, 5
@@ -26,6 +26,7 @@ MAX_SRC = 16
 CAM_FLOATS = 18
 GEO_MAX_SRC = 32
 GEO_CAM_FLOATS = 30
+FUSE_MAX_VIEWS = 64
 
 EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_cams", "pscv_homog_cams", "pscv_warp_cost",
            "pscv_fuse_pairs", "pscv_fuse_finish", "pscv_geo_filter", "pscv_pack_conv2d_weights", "pscv_conv2d",
@@ -36,7 +37,7 @@ EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_
            "pscv_set_tuning_thread", "pscv_get_tuning", "pscv_conv3d_cat2", "pscv_uncert_net", "pscv_head_index_entropy", "pscv_image_prep", "pscv_conv3d_block8",
            "pscv_bn_stats_grouped", "pscv_bn_finalize_grouped", "pscv_bn_act_grouped", "pscv_bn_bwd_reduce_grouped", "pscv_bn_bwd_coeffs_grouped",
            "pscv_bn_bwd_apply_grouped", "pscv_pack_conv2d_weights_device", "pscv_leaky_relu_bwd", "pscv_leaky_relu_bwd_sum", "pscv_pack_conv2d_weights_device_ex", "pscv_warp_cost_rows",
-           "pscv_tail_sweep", "pscv_tail_sweep_workspace")
+           "pscv_tail_sweep", "pscv_tail_sweep_workspace", "pscv_fuse_depth_workspace", "pscv_fuse_depth_pass")
 
 
 class PscvMissingError(RuntimeError):
@@ -131,6 +132,11 @@ def _declare(lib):
     lib.pscv_conv2d_ex.argtypes = [vp, i, vp, vp, vp, vp, i, i, vp, i, i, i, i, i, i, i, i, i, i, i, f, vp]
     lib.pscv_geo_filter.restype = i
     lib.pscv_geo_filter.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, vp, i, i, f, f, f, i, vp, vp, vp, vp, vp]
+    lib.pscv_fuse_depth_workspace.restype = l
+    lib.pscv_fuse_depth_workspace.argtypes = [i, i]
+    lib.pscv_fuse_depth_pass.restype = i
+    lib.pscv_fuse_depth_pass.argtypes = [i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp, f, i, f, f, vp, vp, vp,
+                                         vp, l, vp, vp, l, vp]
     lib.pscv_warp_cost.restype = i
     lib.pscv_warp_cost.argtypes = [vp, C.POINTER(vp), i, vp, vp, l, i, i, i, f, vp, i, i, i, i, i, i, i, i, i, vp]
     lib.pscv_warp_cost_rows.restype = i

@@ -463,6 +463,130 @@ def geo_filter(depth: torch.Tensor, src_depth: Sequence[torch.Tensor], cams: tor
 
 
 # --------------------------------------------------------------------------------------------
+# depth-map fusion into a point cloud (the step after the geometric filter)
+# --------------------------------------------------------------------------------------------
+def pack_rgba8(colors: torch.Tensor) -> torch.Tensor:
+    """uint8 [h,w,3] -> int32 [h,w] with the bytes R, G, B, 0 (red in the low byte): one 32-bit gather per colour (layout only)."""
+    if colors.dtype != torch.uint8 or colors.dim() != 3 or colors.shape[2] != 3:
+        raise ValueError("pscv.pack_rgba8: uint8 [h,w,3] colours expected")
+    pad = torch.zeros(colors.shape[:2] + (1,), dtype=torch.uint8, device=colors.device)
+    return torch.cat((colors, pad), dim=2).contiguous().view(torch.int32).reshape(colors.shape[:2])
+
+
+def _fuse_inputs(depths, colors, cams):
+    depths = [d.to(torch.float32).contiguous() for d in depths]
+    n = len(depths)
+    if n < 2 or n > L.FUSE_MAX_VIEWS or len(colors) != n:
+        raise ValueError(f"pscv.fuse_depth: 2..{L.FUSE_MAX_VIEWS} depth maps and as many colour images expected, got {n} and {len(colors)}")
+    cams = cams.to(torch.float32).contiguous()
+    _dev(cams, *depths)
+    if tuple(cams.shape) != (n, L.GEO_CAM_FLOATS):
+        raise ValueError(f"pscv.fuse_depth: cams [N,{L.GEO_CAM_FLOATS}] expected (geo_filter_cams), got {tuple(cams.shape)}")
+    packed = []
+    for v, (d, c) in enumerate(zip(depths, colors)):
+        if d.dim() != 2:
+            raise ValueError(f"pscv.fuse_depth: depth map {v} must be [h,w]")
+        _dev(c)
+        if c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
+            packed.append(c.contiguous())
+        elif c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
+            packed.append(pack_rgba8(c))
+        else:
+            raise ValueError(f"pscv.fuse_depth: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
+    hw = (C.c_int * (2 * n))(*[v for d in depths for v in d.shape])
+    ws_bytes = max(int(L.lib().pscv_fuse_depth_workspace(int(d.shape[0]), int(d.shape[1]))) for d in depths)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=depths[0].device)
+    ptrs = ((C.c_void_p * n)(*[d.data_ptr() for d in depths]), (C.c_void_p * n)(*[c.data_ptr() for c in packed]), hw)
+    return depths, packed, cams, ptrs, ws
+
+
+def _check_used(used, depths):
+    if len(used) != len(depths):
+        raise ValueError("pscv.fuse_depth: one used mask per view expected")
+    for v, (u, d) in enumerate(zip(used, depths)):
+        _dev(u)
+        if u.dtype != torch.uint8 or tuple(u.shape) != tuple(d.shape):
+            raise ValueError(f"pscv.fuse_depth: used mask {v} must be uint8 [h,w] at the depth map's size")
+
+
+def _used_ptrs(used):
+    return (C.c_void_p * len(used))(*[u.data_ptr() for u in used])
+
+
+def _fuse_pass(i, depths, ptrs, uptr, cams, ws, params, out, counter):
+    n = len(depths)
+    xyz, rgb, view, pixel = out
+    dptr, cptr, hw = ptrs
+    disp_thresh, num_consistent, depth_min, depth_max = params
+    h, w = depths[i].shape
+    rc = _launch("fuse_depth_pass", lambda: L.lib().pscv_fuse_depth_pass(
+        int(i), dptr, cptr, uptr, hw, n, _p(cams), float(disp_thresh), int(num_consistent), float(depth_min), float(depth_max),
+        _p(xyz), _p(rgb), _p(view), _p(pixel), int(xyz.shape[0]), _p(counter), _p(ws), int(ws.numel()), _stream()),
+        # per (pixel, other view): one depth gather (4 B) + one colour gather (4 B) at most; ~80 flops
+        cost=lambda: (float(h * w * (n - 1) * 8), 80.0 * h * w * (n - 1)))
+    L.check(rc, "pscv_fuse_depth_pass")
+
+
+def _fuse_out(capacity, device, want_view=True):
+    xyz = torch.empty((capacity, 3), dtype=torch.float32, device=device)
+    rgb = torch.empty((capacity, 3), dtype=torch.uint8, device=device)
+    view = torch.empty((capacity,), dtype=torch.int32, device=device) if want_view else None
+    pixel = torch.empty((capacity,), dtype=torch.int32, device=device)
+    return xyz, rgb, view, pixel
+
+
+def _fuse_total(counter, capacity, what):
+    total = int(counter.item())
+    if total > capacity:
+        raise L.PscvError(f"{what}: {total} points do not fit the output capacity of {capacity} (nothing past it was written)")
+    return total
+
+
+def fuse_depth_pass(i: int, depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor,
+                    used: Sequence[torch.Tensor], *, disp_thresh: float = 0.01, num_consistent: int = 3, depth_min: float = 1e-3,
+                    depth_max: float = 1e5, capacity: Optional[int] = None):
+    """Pass ``i`` of ``fuse_depth_maps`` alone: depths N x fp32 [h_v,w_v], colors N x uint8 [h_v,w_v,3], cams [N,30]
+    (``geo_filter_cams``), used N x uint8 [h_v,w_v] (updated in place), all on the GPU -> the points the pass emits, in row-major
+    pixel order: (xyz fp32 [M,3], rgb uint8 [M,3], pixel int32 [M] = y w_i + x).  ``capacity`` (default h_i w_i, the most a pass can
+    emit) is the size of the output buffer; a pass that needs more raises ``PscvError``."""
+    depths, packed, cams, ptrs, ws = _fuse_inputs(depths, colors, cams)
+    _check_used(used, depths)
+    if not 0 <= i < len(depths):
+        raise ValueError(f"pscv.fuse_depth_pass: pass {i} outside [0,{len(depths)})")
+    cap = int(depths[i].numel()) if capacity is None else int(capacity)
+    out = _fuse_out(cap, cams.device, want_view=False)
+    counter = torch.zeros(1, dtype=torch.int64, device=cams.device)
+    _fuse_pass(i, depths, ptrs, _used_ptrs(used), cams, ws, (disp_thresh, num_consistent, depth_min, depth_max), out, counter)
+    m = _fuse_total(counter, cap, "pscv.fuse_depth_pass")
+    return out[0][:m], out[1][:m], out[3][:m]
+
+
+def fuse_depth_maps(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, *, disp_thresh: float = 0.01,
+                    num_consistent: int = 3, depth_min: float = 1e-3, depth_max: float = 1e5, capacity: Optional[int] = None,
+                    want_pixel: bool = False):
+    """Consistency fusion of N filtered depth maps into one point cloud (the fusibile step of the
+    reference's pipeline): depths N x fp32 [h_v,w_v] (masked pixels 0), colors N x uint8 [h_v,w_v,3], cams [N,30]
+    (``geo_filter_cams``; intrinsics at each map's size), all on the GPU, 2 <= N <= 64 -> (xyz fp32 [M,3], rgb uint8 [M,3],
+    view int32 [M]) on the GPU, pass-major then row-major pixel order, bit-reproducible.  N passes of pscv_fuse_depth_pass on the
+    current stream with the running count on the device; the host reads it once at the end.  ``capacity`` (default: the total
+    pixel count, which no run can exceed) sizes the output buffer; a run that needs more raises ``PscvError``.  ``want_pixel``
+    appends the pixel index (y w_v + x) each point was emitted from."""
+    depths, packed, cams, ptrs, ws = _fuse_inputs(depths, colors, cams)
+    dev = cams.device
+    used = [torch.zeros(d.shape, dtype=torch.uint8, device=dev) for d in depths]
+    uptr = _used_ptrs(used)
+    cap = sum(int(d.numel()) for d in depths) if capacity is None else int(capacity)
+    out = _fuse_out(cap, dev)
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    params = (disp_thresh, num_consistent, depth_min, depth_max)
+    for i in range(len(depths)):
+        _fuse_pass(i, depths, ptrs, uptr, cams, ws, params, out, counter)
+    m = _fuse_total(counter, cap, "pscv.fuse_depth_maps")
+    res = (out[0][:m], out[1][:m], out[2][:m])
+    return res + (out[3][:m],) if want_pixel else res
+
+
+# --------------------------------------------------------------------------------------------
 # fused warp + cost
 # --------------------------------------------------------------------------------------------
 def warp_cost(ref: Optional[torch.Tensor], srcs: Sequence[torch.Tensor], cams: torch.Tensor, depth: torch.Tensor, *,

@@ -134,6 +134,60 @@ def make_filter_scene(V: int, H: int, W: int, *, seed: int = 0, behind_view: int
     return {"depth": maps[0], "src_depth": maps[1:], "K": K, "R": R, "t": t}
 
 
+def make_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, perturb: float = 0.004, outliers: bool = True,
+                      half_res_view: int = -1, behind_view: int = -1, spacing: float = 0.25, exact: bool = False) -> Dict[str, object]:
+    """Inputs of the depth-map fusion (the step after the geometric filter): V cameras on a square grid of ``spacing`` in the
+    plane z = 0, each looking along +z with a small tilt towards the grid's centre, all seeing one tilted world plane
+    ``n . X = c0`` at depth ~4 (focal 0.9 W).  Returns ``depths`` (V fp32 maps), ``colors`` (V uint8 [h,w,3]: a texture of the
+    world position, so the views agree on colour up to small noise), ``K``, ``R`` [V,3,3], ``t`` [V,3,1] and the plane ``n``,
+    ``c0``.  Depths are the analytic ray-plane distances; unless ``exact``, each view then gets a smooth multiplicative
+    perturbation of up to ~``perturb`` (independent per view), view 1 a block of gross outliers (x 1.3) and every view a few
+    masked (0) pixels.  ``half_res_view`` renders that view at half resolution (own intrinsics); ``behind_view`` turns that
+    camera round to face a second plane behind the rig, so its points land behind every other camera and the others' behind
+    it."""
+    rng = np.random.default_rng(seed)
+    n = np.array([0.10, -0.06, 1.0])
+    n = n / np.linalg.norm(n)
+    c0 = 4.0 * n[2]
+    g = int(math.ceil(math.sqrt(V)))
+    K, R, t, depths, colors = [], [], [], [], []
+    for v in range(V):
+        h, w = (H // 2, W // 2) if v == half_res_view else (H, W)
+        f = 0.9 * w
+        Kv = np.array([[f, 0.0, w / 2.0 + 0.3 * (v % 3)], [0.0, f, h / 2.0 - 0.2 * (v % 2)], [0.0, 0.0, 1.0]])
+        gx, gy = v % g - (g - 1) / 2.0, v // g - (g - 1) / 2.0
+        c = np.array([gx * spacing, gy * spacing, 0.0])
+        ay, ax = -0.25 * gx * spacing / 4.0, 0.25 * gy * spacing / 4.0       # tilt a quarter of the way towards the centre line
+        if v == behind_view:
+            ay = math.pi - 0.05
+        cy, sy, cx, sx = math.cos(ay), math.sin(ay), math.cos(ax), math.sin(ax)
+        Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+        Rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+        Rv = Rx @ Ry
+        tv = -Rv @ c
+        nv, cv = (n, c0) if v != behind_view else (np.array([0.0, 0.05, 1.0]) / np.linalg.norm([0.0, 0.05, 1.0]), -4.0)
+        ys, xs = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+        p = np.stack((xs, ys, np.ones_like(xs)), axis=-1).reshape(-1, 3)
+        ray = p @ np.linalg.inv(Kv).T @ Rv                                    # R^T K^-1 p, as rows
+        d = ((cv - nv @ c) / (ray @ nv)).reshape(h, w)
+        X = c + d.reshape(-1, 1) * ray
+        col = np.stack((128 + 100 * np.sin(3.1 * X[:, 0]), 128 + 100 * np.sin(2.3 * X[:, 1] + 1.0),
+                        128 + 100 * np.cos(1.7 * (X[:, 0] + X[:, 1]))), axis=-1).reshape(h, w, 3)
+        if not exact:
+            col = col + rng.normal(0.0, 2.0, col.shape)
+            coarse = torch.from_numpy(rng.standard_normal((1, 1, max(h // 10, 2), max(w // 10, 2))))
+            bump = torch.nn.functional.interpolate(coarse, size=(h, w), mode="bilinear", align_corners=False)[0, 0].numpy()
+            d = d * (1.0 + perturb * np.tanh(bump))
+            if v == 1 and outliers:
+                d[h // 4:h // 2, w // 3:w // 2] *= 1.3
+            d[rng.random((h, w)) < 0.01] = 0.0
+        K.append(Kv); R.append(Rv); t.append(tv.reshape(3, 1))
+        depths.append(torch.from_numpy(d.astype(np.float32)).contiguous())
+        colors.append(torch.from_numpy(np.clip(np.rint(col), 0, 255).astype(np.uint8)).contiguous())
+    f32 = lambda a: torch.from_numpy(np.stack(a).astype(np.float32))
+    return {"depths": depths, "colors": colors, "K": f32(K), "R": f32(R), "t": f32(t), "n": n, "c0": c0}
+
+
 def make_scene(B: int, V: int, H: int, W: int, *, seed: int = 0, depth_min: float = None,
                depth_max: float = None, behind_view: int = -1, rig: str = "probe") -> Dict[str, torch.Tensor]:
     """Full sample dict with smooth-ish random images in [0, 1)."""
