@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSCV_ABI_VERSION 10
+#define PSCV_ABI_VERSION 11
 
 /* storage dtypes */
 #define PSCV_F32 0
@@ -385,6 +385,53 @@ int pscv_fuse_depth_pass(int pass, const float* const* depth, const unsigned int
                          const int* hw, int n_views, const float* cams, float disp_thresh, int num_consistent, float depth_min,
                          float depth_max, float* out_xyz, unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity,
                          long long* counter, void* workspace, long workspace_bytes, void* stream);
+
+/*
+ * Point-cloud metrics (ABI 11; the step after fusion).  Replaces the scipy cKDTree calls of evaluation/metrics.py: reduce_pts,
+ * chamfer, chamfer_imw.  The rules are INTEGRATION.md section 2f.  Points are fp32 [n][3]; distances are fp64 from those
+ * coordinates.  All calls are asynchronous on `stream`; every result is bit-reproducible.
+ *
+ * Sparse uniform grid of n points (n < 2^30): cell (floor((x - ox) / cell), ...) with 21 bits per axis (the caller keeps the
+ * points within 2^21 cells of the origin; points outside are clamped into the edge cells), an open-addressing hash table of
+ * >= 2n slots (integer atomicCAS), per-slot counts, a scan and a scatter into slot order.  No sort, nothing dense.
+ *   grid       device buffer of pscv_point_grid_workspace(n) bytes; its first 4 bytes hold the number of occupied cells (uint32)
+ *   payload    optional device int32 [n] carried into slot order (the ranks of pscv_radius_mis_round), may be NULL
+ * A grid is used with the same n, origin and cell it was built with.
+ */
+long pscv_point_grid_workspace(long n);
+int pscv_point_grid_build(const float* pts, long n, double ox, double oy, double oz, double cell, const int* payload, void* grid,
+                          long grid_bytes, void* stream);
+
+/*
+ * Bounded nearest-neighbour distance of m query points to the n_target points of two grids of the same set (same origin): out[i]
+ * = |q_i - p| of the nearest target p with |q_i - p|^2 < maxdist^2 (strict), +inf when there is none.  The search visits rings
+ * 0..fine_rings of the fine grid, then rings 0..coarse_rings of the coarse grid (coarse_rings * coarse_cell >= maxdist +
+ * coarse_cell), pruned by the best distance so far.
+ * bb != NULL selects the DTU blocking of metrics.py::chamfer: host double[6] = bb0 xyz, bb1 xyz; cells [bb0 + x maxdist,
+ * bb0 + x maxdist + maxdist) for x in 0..floor((bb1 - bb0) / maxdist) per axis; a query in no cell, or in a cell whose
+ * occupancy (pscv_dtu_cell_occupancy) is 0, gets maxdist; otherwise only targets in the cell's expanded box count.
+ */
+int pscv_point_nn_dist(const float* query, long m, const void* fine, const void* coarse, long n_target, double ox, double oy,
+                       double oz, double fine_cell, double coarse_cell, int fine_rings, int coarse_rings, double maxdist,
+                       const double* bb, const int* occ, double* out, void* stream);
+/* occ: device int32 [(na_x+1)(na_y+1)(na_z+1)], zeroed by the caller; set to 1 where a target lies in the cell's expanded box
+   [low - maxdist, high + maxdist) (bb: host double[6] as above) */
+int pscv_dtu_cell_occupancy(const float* pts, long n, const double* bb, double maxdist, int* occ, void* stream);
+
+/*
+ * One round of the radius maximal independent set (metrics.py::reduce_pts as the greedy MIS in rank order) over the points of
+ * a grid built with payload = rank (unique ints; lower goes first) and cell > dst.  state_in / state_out: uint8 [n] in slot
+ * order, 0 undecided / 1 kept / 2 removed (all 0 before round 0).  An undecided point with a kept neighbour (|p - q| <= dst in
+ * fp64) becomes removed; with no kept and no lower-ranked undecided neighbour it becomes kept.  *undecided (device int64,
+ * zeroed by the caller) gains the number of points still undecided after the round.
+ */
+int pscv_radius_mis_round(const void* grid, long n, double ox, double oy, double oz, double cell, double dst,
+                          const unsigned char* state_in, unsigned char* state_out, long long* undecided, void* stream);
+/* Final state -> mask uint8 [n] in the points' original order (1 = kept) and kept int32 [n]: the kept indices in increasing
+   order, *n_kept (device int64) of them.  workspace: pscv_radius_mis_workspace(n) bytes. */
+long pscv_radius_mis_workspace(long n);
+int pscv_radius_mis_compact(const void* grid, long n, const unsigned char* state, unsigned char* mask, int* kept,
+                            long long* n_kept, void* workspace, long workspace_bytes, void* stream);
 
 /*
  * Softmax over the depth axis + expectation(s), fused.

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("PSCV_LIB") or os.path.join(_HERE, "libpscv.so")     #
 CSRC = os.path.join(_HERE, "csrc")
 
 # mirror of include/pscv.h
-ABI_VERSION = 10
+ABI_VERSION = 11
 F32, BF16, F16 = 0, 1, 2
 GEOM_PROJ, GEOM_HOMOG = 0, 1
 COST_VARIANCE, COST_VARIANCE_CVP, COST_SOFTMIN, COST_GROUPCORR, COST_WARP_ONLY, COST_VARIANCE_PARTIAL = 0, 1, 2, 3, 4, 5
@@ -37,7 +37,9 @@ EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_
            "pscv_set_tuning_thread", "pscv_get_tuning", "pscv_conv3d_cat2", "pscv_uncert_net", "pscv_head_index_entropy", "pscv_image_prep", "pscv_conv3d_block8",
            "pscv_bn_stats_grouped", "pscv_bn_finalize_grouped", "pscv_bn_act_grouped", "pscv_bn_bwd_reduce_grouped", "pscv_bn_bwd_coeffs_grouped",
            "pscv_bn_bwd_apply_grouped", "pscv_pack_conv2d_weights_device", "pscv_leaky_relu_bwd", "pscv_leaky_relu_bwd_sum", "pscv_pack_conv2d_weights_device_ex", "pscv_warp_cost_rows",
-           "pscv_tail_sweep", "pscv_tail_sweep_workspace", "pscv_fuse_depth_workspace", "pscv_fuse_depth_pass")
+           "pscv_tail_sweep", "pscv_tail_sweep_workspace", "pscv_fuse_depth_workspace", "pscv_fuse_depth_pass",
+           "pscv_point_grid_workspace", "pscv_point_grid_build", "pscv_point_nn_dist", "pscv_dtu_cell_occupancy", "pscv_radius_mis_round",
+           "pscv_radius_mis_workspace", "pscv_radius_mis_compact")
 
 
 class PscvMissingError(RuntimeError):
@@ -137,6 +139,21 @@ def _declare(lib):
     lib.pscv_fuse_depth_pass.restype = i
     lib.pscv_fuse_depth_pass.argtypes = [i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp, f, i, f, f, vp, vp, vp,
                                          vp, l, vp, vp, l, vp]
+    d = C.c_double
+    lib.pscv_point_grid_workspace.restype = l
+    lib.pscv_point_grid_workspace.argtypes = [l]
+    lib.pscv_point_grid_build.restype = i
+    lib.pscv_point_grid_build.argtypes = [vp, l, d, d, d, d, vp, vp, l, vp]
+    lib.pscv_point_nn_dist.restype = i
+    lib.pscv_point_nn_dist.argtypes = [vp, l, vp, vp, l, d, d, d, d, d, i, i, d, vp, vp, vp, vp]
+    lib.pscv_dtu_cell_occupancy.restype = i
+    lib.pscv_dtu_cell_occupancy.argtypes = [vp, l, vp, d, vp, vp]
+    lib.pscv_radius_mis_round.restype = i
+    lib.pscv_radius_mis_round.argtypes = [vp, l, d, d, d, d, d, vp, vp, vp, vp]
+    lib.pscv_radius_mis_workspace.restype = l
+    lib.pscv_radius_mis_workspace.argtypes = [l]
+    lib.pscv_radius_mis_compact.restype = i
+    lib.pscv_radius_mis_compact.argtypes = [vp, l, vp, vp, vp, vp, vp, l, vp]
     lib.pscv_warp_cost.restype = i
     lib.pscv_warp_cost.argtypes = [vp, C.POINTER(vp), i, vp, vp, l, i, i, i, f, vp, i, i, i, i, i, i, i, i, i, vp]
     lib.pscv_warp_cost_rows.restype = i

@@ -587,6 +587,201 @@ def fuse_depth_maps(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tenso
 
 
 # --------------------------------------------------------------------------------------------
+# point-cloud metrics (the step after fusion): grids, bounded nearest neighbour, radius MIS
+# --------------------------------------------------------------------------------------------
+GRID_SPAN = 1 << 21          # cells per axis a grid can address (21-bit key fields)
+
+
+@dataclass
+class PointGrid:
+    """A sparse uniform grid of ``n`` points built by ``point_grid`` (pscv_point_grid_build): ``buf`` is its device buffer,
+    ``origin`` / ``cell`` its lattice.  ``occupied()`` reads the number of non-empty cells (synchronises)."""
+    buf: torch.Tensor
+    n: int
+    origin: tuple
+    cell: float
+
+    def occupied(self) -> int:
+        return int(self.buf[:4].view(torch.int32).item())
+
+
+def _points(pts: torch.Tensor, what: str) -> torch.Tensor:
+    _dev(pts)
+    if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"pscv.{what}: float32 [n,3] points expected, got {pts.dtype} {tuple(pts.shape)}")
+    if pts.shape[0] >= (1 << 30):
+        raise ValueError(f"pscv.{what}: {pts.shape[0]} points (at most 2^30 - 1)")
+    pts = pts.contiguous()
+    if pts.numel() and not bool(torch.isfinite(pts).all()):
+        raise ValueError(f"pscv.{what}: points must be finite")
+    return pts
+
+
+def _extent(*clouds: torch.Tensor):
+    """(min xyz, max xyz) in fp64 over the non-empty clouds, or None."""
+    ne = [c for c in clouds if c.shape[0]]
+    if not ne:
+        return None
+    lo = torch.stack([c.amin(0) for c in ne]).amin(0).double().cpu().numpy()
+    hi = torch.stack([c.amax(0) for c in ne]).amax(0).double().cpu().numpy()
+    return lo, hi
+
+
+def point_grid(pts: torch.Tensor, cell: float, origin=None, payload: Optional[torch.Tensor] = None) -> PointGrid:
+    """Sparse uniform grid of float32 [n,3] points on the GPU (pscv_point_grid_build: hash table of cell keys, counts, scan,
+    scatter; no sort and nothing dense over the bounding box).  ``origin`` defaults to the points' minimum corner less one cell;
+    every point must lie within 2^21 cells of it.  ``payload`` (int32 [n]) is carried into slot order."""
+    pts = _points(pts, "point_grid")
+    n = int(pts.shape[0])
+    cell = float(cell)
+    if not (cell > 0.0 and np.isfinite(cell)):
+        raise ValueError(f"pscv.point_grid: cell edge {cell} must be positive and finite")
+    ext = _extent(pts)
+    if origin is None:
+        origin = (0.0, 0.0, 0.0) if ext is None else tuple(float(v) - cell for v in ext[0])
+    origin = tuple(float(v) for v in origin)
+    if ext is not None:
+        lo = (ext[0] - np.array(origin)) / cell
+        hi = (ext[1] - np.array(origin)) / cell
+        if lo.min() < 0.0 or hi.max() >= GRID_SPAN - 2:
+            raise ValueError(f"pscv.point_grid: the points span cells {lo.min():.0f}..{hi.max():.0f} of the origin; at most 0..{GRID_SPAN - 3}")
+    if payload is not None:
+        _dev(payload)
+        if payload.dtype != torch.int32 or tuple(payload.shape) != (n,):
+            raise ValueError("pscv.point_grid: payload must be int32 [n]")
+        payload = payload.contiguous()
+    nbytes = int(L.lib().pscv_point_grid_workspace(n))
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    rc = _launch("point_grid_build", lambda: L.lib().pscv_point_grid_build(
+        _p(pts), n, origin[0], origin[1], origin[2], cell, _p(payload), _p(buf), nbytes, _stream()),
+        cost=lambda: (float(n * 40), float(n * 20)))
+    L.check(rc, "pscv_point_grid_build")
+    return PointGrid(buf, n, origin, cell)
+
+
+def radius_downsample(pts: torch.Tensor, dst: float, rank: torch.Tensor, *, check_every: int = 4):
+    """Greedy maximal independent set of the radius graph (|p - q| <= dst in fp64) in ``rank`` order -- what the reference's
+    ``metrics.reduce_pts`` computes with rank = the inverse of its random permutation.
+    pts float32 [n,3], rank int32 [n] (a permutation of 0..n-1; lower goes first), both on the GPU -> (kept points float32 [k,3],
+    mask bool [n] in the input order, number of rounds).  Rounds of pscv_radius_mis_round run on the current stream; the host
+    reads the undecided count once every ``check_every`` rounds."""
+    pts = _points(pts, "radius_downsample")
+    n = int(pts.shape[0])
+    _dev(rank)
+    dst = float(dst)
+    if not (dst >= 0.0 and np.isfinite(dst)):
+        raise ValueError(f"pscv.radius_downsample: dst {dst} must be >= 0 and finite")
+    rank = rank.to(torch.int32).contiguous()
+    if tuple(rank.shape) != (n,):
+        raise ValueError(f"pscv.radius_downsample: rank must be [n] = [{n}], got {tuple(rank.shape)}")
+    dev = pts.device
+    if n == 0:
+        return pts[:0], torch.zeros(0, dtype=torch.bool, device=dev), 0
+    if int(rank.min()) != 0 or int(rank.max()) != n - 1 or not bool((torch.bincount(rank, minlength=n) == 1).all()):
+        raise ValueError("pscv.radius_downsample: rank must be a permutation of 0..n-1")
+    lo, hi = _extent(pts)
+    cell = max(dst * (1.0 + 1e-6), float((hi - lo).max() + 1e-6) / (GRID_SPAN - 8))     # >= dst: 27 cells hold a neighbourhood
+    grid = point_grid(pts, cell, payload=rank)
+    state = [torch.zeros(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)]
+    k = max(1, int(check_every))
+    counters = torch.zeros(k, dtype=torch.int64, device=dev)
+    launched = 0
+    while True:
+        counters.zero_()
+        for j in range(k):
+            src, nxt, cnt = state[launched % 2], state[(launched + 1) % 2], counters[j:j + 1]
+            rc = _launch("radius_mis_round", lambda: L.lib().pscv_radius_mis_round(
+                _p(grid.buf), n, grid.origin[0], grid.origin[1], grid.origin[2], grid.cell, dst, _p(src), _p(nxt), _p(cnt), _stream()))
+            L.check(rc, "pscv_radius_mis_round")
+            launched += 1
+        left = counters.cpu().numpy()
+        if left[-1] == 0:
+            rounds = launched - k + 1 + int(np.argmax(left == 0))     # (the rounds after the first empty one change nothing)
+            break
+        if launched > n + k:
+            raise L.PscvError("pscv.radius_downsample: the rounds do not converge")
+    final = state[launched % 2]
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    n_kept = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws_bytes = int(L.lib().pscv_radius_mis_workspace(n))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    rc = _launch("radius_mis_compact", lambda: L.lib().pscv_radius_mis_compact(
+        _p(grid.buf), n, _p(final), _p(mask), _p(kept), _p(n_kept), _p(ws), ws_bytes, _stream()))
+    L.check(rc, "pscv_radius_mis_compact")
+    m = int(n_kept.item())
+    return pts.index_select(0, kept[:m].long()), mask.bool(), rounds
+
+
+def _nn_grids(target: torch.Tensor, maxdist: float, fine_cell: Optional[float], ext):
+    """(fine grid, coarse grid) of the targets with one origin: coarse cells of maxdist / 4; fine cells halved from maxdist / 16
+    until a non-empty cell holds at most ~12 points on average (or as given)."""
+    span = 0.0 if ext is None else float((ext[1] - ext[0]).max())
+    floor_cell = (span + 1e-6) / (GRID_SPAN - 8)
+    coarse = max(maxdist / 4.0, floor_cell)
+    origin = (0.0, 0.0, 0.0) if ext is None else tuple(float(v) - coarse for v in ext[0])
+    if fine_cell is not None:
+        fine = point_grid(target, max(float(fine_cell), floor_cell), origin)
+    else:
+        h = max(coarse / 4.0, floor_cell)
+        fine = point_grid(target, h, origin)
+        for _ in range(8):
+            if target.shape[0] == 0 or target.shape[0] <= 12 * fine.occupied() or h / 2.0 < floor_cell:
+                break
+            h /= 2.0
+            fine = point_grid(target, h, origin)
+    return fine, point_grid(target, coarse, origin)
+
+
+def dtu_cells(bb, maxdist: float):
+    """Cells per axis of the DTU blocking of ``metrics.chamfer``: floor((bb1 - bb0) / maxdist) + 1."""
+    bb = np.asarray(bb, dtype=np.float64).reshape(2, 3)
+    return tuple(int(v) + 1 for v in np.floor((bb[1] - bb[0]) / maxdist))
+
+
+def nn_dist(query: torch.Tensor, target: torch.Tensor, maxdist: float, bb=None, *, fine_cell: Optional[float] = None) -> torch.Tensor:
+    """Bounded nearest-neighbour distance: query float32 [m,3], target float32 [n,3] on the GPU ->
+    float64 [m]: the distance to the nearest target when it is strictly below ``maxdist``, +inf otherwise (``metrics.chamfer_imw``;
+    maxdist = inf is allowed).  ``bb`` ([2,3] fp64, DTU) applies ``metrics.chamfer``'s blocking by cells of ``maxdist``: a query
+    in no cell, or whose cell's expanded box holds no target, gets ``maxdist``, and only the targets in that box count."""
+    query = _points(query, "nn_dist")
+    target = _points(target, "nn_dist")
+    maxdist = float(maxdist)
+    m, n = int(query.shape[0]), int(target.shape[0])
+    dev = query.device
+    out = torch.empty(m, dtype=torch.float64, device=dev)
+    if not maxdist > 0.0:
+        raise ValueError(f"pscv.nn_dist: maxdist {maxdist} must be positive")
+    ext_all = _extent(query, target)
+    if np.isinf(maxdist):
+        if bb is not None:
+            raise ValueError("pscv.nn_dist: the DTU mode needs a finite maxdist")
+        # no distance between the two clouds reaches their joint bounding-box diagonal: a finite bound with the same results
+        maxdist = 1.0 if ext_all is None else float(np.linalg.norm(ext_all[1] - ext_all[0])) * 2.0 + 1.0
+    if m == 0:
+        return out
+    fine, coarse = _nn_grids(target, maxdist, fine_cell, _extent(target))
+    coarse_rings = int(np.ceil(maxdist / coarse.cell)) + 1
+    bb_arg, occ = None, None
+    if bb is not None:
+        bbn = np.ascontiguousarray(np.asarray(bb, dtype=np.float64).reshape(2, 3))
+        cells = dtu_cells(bbn, maxdist)
+        if min(cells) < 1 or max(cells) > 4096:
+            raise ValueError(f"pscv.nn_dist: {cells} DTU cells (bb / maxdist)")
+        bb_host = (C.c_double * 6)(*bbn.reshape(-1).tolist())
+        bb_arg = C.cast(bb_host, C.c_void_p)
+        occ = torch.zeros(int(np.prod(cells)), dtype=torch.int32, device=dev)
+        rc = _launch("dtu_cell_occupancy", lambda: L.lib().pscv_dtu_cell_occupancy(_p(target), n, bb_arg, maxdist, _p(occ), _stream()))
+        L.check(rc, "pscv_dtu_cell_occupancy")
+    o = fine.origin
+    rc = _launch("point_nn_dist", lambda: L.lib().pscv_point_nn_dist(
+        _p(query), m, _p(fine.buf), _p(coarse.buf), n, o[0], o[1], o[2], fine.cell, coarse.cell, 2, coarse_rings, maxdist, bb_arg,
+        _p(occ), _p(out), _stream()))
+    L.check(rc, "pscv_point_nn_dist")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # fused warp + cost
 # --------------------------------------------------------------------------------------------
 def warp_cost(ref: Optional[torch.Tensor], srcs: Sequence[torch.Tensor], cams: torch.Tensor, depth: torch.Tensor, *,

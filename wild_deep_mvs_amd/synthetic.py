@@ -370,3 +370,33 @@ def vis_supervised_loss(out, gt: torch.Tensor, mask: torch.Tensor, depth_min: to
             loss = loss + VIS_LOSS_FACTORS[i] / (n_views - 1) * (torch.sum((l1p * torch.exp(-unc) + unc) * m) / torch.sum(m)
                                                                + torch.sum(l1p * m) / torch.sum(m))
     return loss
+
+
+def make_point_cloud_scene(n_pred: int, n_gt: int, *, seed: int = 0, outlier_frac: float = 0.02, dup_frac: float = 0.3,
+                           extent: float = 400.0, outliers_only: bool = False) -> Dict[str, np.ndarray]:
+    """Inputs of the point-cloud metrics at DTU's millimetre scale: a smooth height-field surface over an ``extent`` square;
+    ``gt`` float32 [n_gt,3] samples it with 0.05 mm noise, ``pred`` float32 [n_pred,3] samples it with 0.3 mm noise over 85 % of
+    the square (the rest is a hole GT covers alone), ``dup_frac`` of them re-sampled within ~0.1 mm of another (what
+    reduce_pts removes) and ``outlier_frac`` of them uniform in the box up to 80 mm off the surface.  ``bb`` [2,3] float64
+    encloses the surface with a margin.  ``outliers_only``: every prediction instead lies 30-70 mm above a flat GT patch (the
+    bounded search's worst case)."""
+    rng = np.random.default_rng(seed)
+    height = lambda x, y: 40.0 * np.sin(x / 70.0) * np.cos(y / 90.0) + 0.05 * x
+    gxy = rng.uniform(0.0, extent, size=(n_gt, 2))
+    if outliers_only:
+        gt = np.concatenate((gxy, rng.normal(0.0, 0.05, (n_gt, 1))), axis=1)
+        pxy = rng.uniform(0.0, extent, size=(n_pred, 2))
+        pred = np.concatenate((pxy, rng.uniform(30.0, 70.0, (n_pred, 1))), axis=1)
+    else:
+        gt = np.concatenate((gxy, (height(gxy[:, 0], gxy[:, 1]) + rng.normal(0.0, 0.05, n_gt))[:, None]), axis=1)
+        n_out = int(n_pred * outlier_frac)
+        n_dup = int(n_pred * dup_frac)
+        n_surf = n_pred - n_out - n_dup
+        pxy = rng.uniform(0.0, extent, size=(n_surf, 2))
+        pxy[:, 0] = pxy[:, 0] * 0.85                                  # the last 15 % along x: a hole in the prediction
+        surf = np.concatenate((pxy, height(pxy[:, 0], pxy[:, 1])[:, None]), axis=1) + rng.normal(0.0, 0.3, (n_surf, 3))
+        dup = surf[rng.integers(0, max(n_surf, 1), n_dup)] + rng.normal(0.0, 0.06, (n_dup, 3))
+        out = rng.uniform([0.0, 0.0, -80.0], [extent, extent, 120.0], size=(n_out, 3))
+        pred = np.concatenate((surf, dup, out))[rng.permutation(n_pred)]
+    bb = np.array([[-20.0, -20.0, -100.0], [extent + 20.0, extent + 20.0, 140.0]])
+    return {"pred": pred.astype(np.float32), "gt": gt.astype(np.float32), "bb": bb}

@@ -1,7 +1,7 @@
 """Binary PLY output of a coloured point cloud: the one format the reconstruction pipeline's fusion step writes and its metrics
 step reads (``x y z`` float32, ``red green blue`` uint8, little-endian).  The header is byte for byte what the reference's
 ``utils/utils_ply.py:write_ply`` produces for float32 xyz and uint8 rgb arrays, so its ``read_ply`` and ``evaluation/metrics.py``
-read the file unchanged."""
+read the file unchanged.  ``read_ply`` is the reader the metrics step uses (any binary property list, like the reference's)."""
 from __future__ import annotations
 
 import os
@@ -33,3 +33,39 @@ def write_point_cloud(path, xyz, rgb) -> None:
         fh.write(ply_header(xyz.shape[0]))
         fh.write(data.tobytes())
     os.replace(tmp, path)
+
+
+# the reference's ply_dtypes (utils/utils_ply.py; its later "uchar" entry wins)
+PLY_DTYPES = {b"int8": "i1", b"char": "i1", b"uint8": "u1", b"uchar": "u1", b"int16": "i2", b"short": "i2", b"uint16": "u2",
+              b"ushort": "u2", b"int32": "i4", b"int": "i4", b"uint32": "u4", b"uint": "u4", b"float32": "f4", b"float": "f4",
+              b"float64": "f8", b"double": "f8"}
+_PLY_FORMATS = {"binary_big_endian": ">", "binary_little_endian": "<"}
+
+
+def read_ply(path) -> np.ndarray:
+    """Structured array of a binary PLY file with one element list (what the reference's ``read_ply`` returns).  The point
+    cloud's coordinates feed float32 kernels, so a file whose ``x``, ``y`` or ``z`` is float64 is rejected rather than rounded."""
+    with open(path, "rb") as fh:
+        if b"ply" not in fh.readline():
+            raise ValueError(f"{path}: not a PLY file")
+        fmt = fh.readline().split()[1].decode()
+        if fmt not in _PLY_FORMATS:
+            raise ValueError(f"{path}: PLY format {fmt!r} is not binary")
+        ext = _PLY_FORMATS[fmt]
+        props, n, line = [], None, b""
+        while b"end_header" not in line:
+            line = fh.readline()
+            if line == b"":
+                raise ValueError(f"{path}: truncated PLY header")
+            if b"element" in line:
+                n = int(line.split()[2])
+            elif b"property" in line:
+                tok = line.split()
+                if tok[1] not in PLY_DTYPES:
+                    raise ValueError(f"{path}: unsupported PLY property type {tok[1].decode()!r}")
+                props.append((tok[2].decode(), ext + PLY_DTYPES[tok[1]]))
+        wide = [name for name, dt in props if name in ("x", "y", "z") and dt.endswith("f8")]
+        if wide:
+            raise ValueError(f"{path}: coordinates {', '.join(wide)} are float64; the metrics run on float32 points and will not "
+                             f"round them silently")
+        return np.fromfile(fh, dtype=props, count=n)
