@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSCV_ABI_VERSION 11
+#define PSCV_ABI_VERSION 12
 
 /* storage dtypes */
 #define PSCV_F32 0
@@ -385,6 +385,38 @@ int pscv_fuse_depth_pass(int pass, const float* const* depth, const unsigned int
                          const int* hw, int n_views, const float* cams, float disp_thresh, int num_consistent, float depth_min,
                          float depth_max, float* out_xyz, unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity,
                          long long* counter, void* workspace, long workspace_bytes, void* stream);
+
+/*
+ * COLMAP-style stereo fusion of depth maps into one point cloud (ABI 12; the YFCC path, where the reference runs the external
+ * `colmap stereo_fusion` from utils/colmap_utils.py:391-400 with max_normal_error 180, i.e. the normal test off).  One call = the
+ * pass of view `view`; the caller runs the views in FindNextImage order on one stream.  Rule: every
+ * seed of the view (0 < d finite, fused = 0; X_s = R^T (d K^-1 (col, row, 1) - t), no +0.5) grows the breadth-first closure of
+ * the pixels of the other unprocessed views that pass |(z - d) / d| <= max_depth_error and (x/z - col)^2 + (y/z - row)^2 <=
+ * max_reproj_error^2 against (x, y, z) = K (R X_s + t), reached through round(P_m X_node) (half away from zero) along `overlap`
+ * from nodes at depth <= max_traversal_depth - 2.  Phase A claims every reached pixel with atomicMin((tag, seed)) on `claim`;
+ * phase B recomputes each closure over its own claims, marks the seed and that cluster fused, and a cluster of at least
+ * min_num_pixels pixels emits the per-coordinate medians of its points, normals R_k^T (1,1,1)/sqrt(3) (normalised; dropped
+ * below FLT_EPSILON) and colours.  Geometry is fp64 from the fp32 inputs.
+ *   depth, color, hw, cams   as pscv_fuse_depth_pass (color RGBA8, red in the low byte)
+ *   fused       host array of n_views device pointers, uint8 [h_v, w_v], 0 / 1, updated in place
+ *   claim       host array of n_views device pointers, uint64 [h_v, w_v]: all bits set before the first pass that uses them
+ *   tag         >= 0, strictly increasing over the calls that share `claim` (a pass's claims then beat every earlier one)
+ *   overlap     host int64 bit masks [n_views]: bit m of overlap[k] when view m follows view k (the diagonal is ignored)
+ *   processed   bit mask: bit v set when view v's pass is done (its pixels are never entered; `view` itself must be clear)
+ *   max_reproj_error in (0, 2] pixels, max_depth_error in (0, 1) relative, max_traversal_depth >= 1
+ *   out_xyz, out_normal fp32 [capacity][3], out_rgb uint8 [capacity][3], out_view, out_pixel int32 [capacity] (normal, view and
+ *               pixel may be NULL): the point, the view and the seed pixel y w + x it was emitted from
+ *   counter     device int64 running point count, as pscv_fuse_depth_pass (counter > capacity after the last pass = overflow)
+ *   workspace   device scratch of pscv_colmap_fuse_workspace(h, w) bytes for the pass's view
+ * No host synchronisation: five launches on `stream` (phase A, phase B, count, scan, scatter); the result is bit-reproducible.
+ */
+long pscv_colmap_fuse_workspace(int h, int w);
+int pscv_colmap_fuse_pass(int view, int tag, const float* const* depth, const unsigned int* const* color,
+                          unsigned char* const* fused, unsigned long long* const* claim, const int* hw, int n_views, const float* cams,
+                          const long* overlap, long processed, float max_depth_error,
+                          float max_reproj_error, int min_num_pixels, int max_traversal_depth, float* out_xyz, float* out_normal,
+                          unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity, long long* counter, void* workspace,
+                          long workspace_bytes, void* stream);
 
 /*
  * Point-cloud metrics (ABI 11; the step after fusion).  Replaces the scipy cKDTree calls of evaluation/metrics.py: reduce_pts,

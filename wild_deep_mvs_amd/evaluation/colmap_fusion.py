@@ -1,0 +1,105 @@
+"""COLMAP-style stereo fusion on MI355X -- drop-in for ``utils/colmap_utils.py:colmap_fusion`` of fdarmon/wild_deep_mvs.
+
+The reference writes COLMAP workspace files and runs the external ``colmap image_undistorter`` and ``colmap stereo_fusion``
+binaries (``utils/colmap_utils.py:324-400``), which are not part of the AMD stack.  Here the fusion is ``pscv_colmap_fuse_pass``,
+two HIP phases per view (INTEGRATION.md section 2g states the rule and its named deviations from COLMAP; it restates
+StereoFusion as the reference configures it -- normal test off, ``max_depth_error``, ``max_reproj_error`` and ``min_num_pixels``
+from the command line, COLMAP's defaults for the rest -- and has not been compared with the binary).
+
+``colmap_fusion(dataloader, args)`` keeps the reference's interface and writes the file its metrics step reads,
+``<data_path>/Points/<model>_<nviews>/<model>_<nviews><scene>.ply``, in COLMAP's fused PLY layout.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from .. import ops
+from ..utils.colmap_model import overlap_from_counts, shared_point_counts
+from ..utils.point_cloud import write_colmap_point_cloud
+from .filtering import depth_folder_name
+from .fusibile import get_mask
+
+CHECK_NUM_IMAGES = 50          # COLMAP's StereoFusionOptions defaults
+MAX_TRAVERSAL_DEPTH = 100
+MAX_NUM_PIXELS = 10000
+
+
+def nearest_colors(img: torch.Tensor, h: int, w: int) -> np.ndarray:
+    """[3,H,W] image in [0,1] -> uint8 [h,w,3]: x 255 truncated to a byte (ToPILImage), sampled nearest-neighbour at the image
+    position (col W / w, row H / h) of each depth-map pixel, rounded half away from zero and clamped (COLMAP's
+    InterpolateNearestNeighbor with its bitmap scale)."""
+    H, W = img.shape[1:]
+    arr = img.detach().cpu().mul(255).byte().permute(1, 2, 0).numpy()
+    xs = np.minimum(np.floor(np.arange(w) * (W / w) + 0.5).astype(np.int64), W - 1)
+    ys = np.minimum(np.floor(np.arange(h) * (H / h) + 0.5).astype(np.int64), H - 1)
+    return np.ascontiguousarray(arr[ys[:, None], xs[None, :]])
+
+
+def view_inputs(args, batch, depth_file):
+    """(masked depth, colours, K at the depth map's size, R, t) of a batch's view 0, as colmap_fusion prepares its workspace."""
+    filename = batch["filename"][0]
+    npz = np.load(depth_file)
+    depth, prob = np.array(npz["depthmap"], dtype=np.float32), np.array(npz["probability"], dtype=np.float32)
+    if args.upsample:
+        up = lambda a: F.interpolate(torch.from_numpy(a)[None, None], mode="bilinear", scale_factor=args.downscale,
+                                     align_corners=False)[0, 0].numpy()
+        depth, prob = up(depth), up(prob)
+    depth[get_mask(args, filename, prob)] = 0
+    img = batch["imgs"][0, 0]
+    h_img, w_img = img.shape[1:]
+    h_d, w_d = depth.shape
+    K = batch["K"][0, 0].clone().to(torch.float64)
+    K[0] *= w_d / w_img
+    K[1] *= h_d / h_img
+    return (np.ascontiguousarray(depth), nearest_colors(img, h_d, w_d), K.to(torch.float32), batch["R"][0, 0].to(torch.float32),
+            batch["t"][0, 0].to(torch.float32).reshape(3, 1))
+
+
+def scene_overlap(args, names):
+    """COLMAP's overlapping images from the sparse model at IntRes/colmap_sparse/<scene> when there is one (shared 3-D points,
+    descending, ties by index, at most CHECK_NUM_IMAGES), else every other view.  -> (lists, description of the source)."""
+    sparse = Path(args.data_path) / "IntRes" / "colmap_sparse" / str(args.scene)
+    if (sparse / "images.bin").exists() and (sparse / "points3D.bin").exists():
+        counts = shared_point_counts(sparse, [n + ".jpg" for n in names])
+        return overlap_from_counts(counts, CHECK_NUM_IMAGES), f"sparse model {sparse}"
+    n = len(names)
+    return [[u for u in range(n) if u != v][:CHECK_NUM_IMAGES] for v in range(n)], "all other views (no sparse model)"
+
+
+def colmap_fusion(dataloader, args):
+    if getattr(args, "colmap", False):
+        raise NotImplementedError("colmap_fusion with args.colmap needs COLMAP's own depth and normal maps (its patch match), "
+                                  "which this port does not produce")
+    folder_name = depth_folder_name(args)
+    ply_dir = Path(args.data_path) / "Points" / folder_name
+    outfile = ply_dir / f"{folder_name}{args.scene}.ply"
+    if outfile.exists() and not args.override:
+        print("Point cloud Fusion already done")
+        return
+    depth_folder = Path(args.data_path) / "IntRes" / "depthmaps" / folder_name / str(args.scene)
+    views, names = [], []
+    for b in dataloader:
+        filename = b["filename"][0]
+        depth_file = depth_folder / f"{filename}_out.npz"
+        if not depth_file.exists():
+            print(f"Could not open {depth_file}")          # the view is left out of the fusion, as in the reference
+            continue
+        views.append(view_inputs(args, b, depth_file))
+        names.append(filename)
+    overlap, source = scene_overlap(args, names)
+    print(f"COLMAP fusion of {len(views)} views, overlap from {source}")
+    depths, colors, K, R, t = zip(*views)
+    with torch.no_grad():
+        cams = ops.geo_filter_cams(torch.stack(K), torch.stack(R), torch.stack(t)).cuda()
+        xyz, normal, rgb, _ = ops.colmap_fuse([torch.from_numpy(d).cuda() for d in depths], [torch.from_numpy(c).cuda() for c in colors],
+                                              cams, overlap, max_depth_error=args.fusion_depth_threshold,
+                                              max_reproj_error=args.fusion_max_reproj_error, min_num_pixels=args.fusion_num_consistent,
+                                              max_traversal_depth=MAX_TRAVERSAL_DEPTH, max_num_pixels=MAX_NUM_PIXELS)
+    ply_dir.mkdir(parents=True, exist_ok=True)
+    write_colmap_point_cloud(outfile, xyz, normal, rgb)
+    print(f"Fused {xyz.shape[0]} points from {len(views)} views -> {outfile}")
+    return args

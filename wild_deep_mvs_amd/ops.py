@@ -9,6 +9,7 @@ Layouts: feature maps ``[B,h,w,C]`` and volumes ``[B,D,h,w,C]`` (channels-last),
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -584,6 +585,158 @@ def fuse_depth_maps(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tenso
     m = _fuse_total(counter, cap, "pscv.fuse_depth_maps")
     res = (out[0][:m], out[1][:m], out[2][:m])
     return res + (out[3][:m],) if want_pixel else res
+
+
+# --------------------------------------------------------------------------------------------
+# COLMAP-style stereo fusion (the YFCC path: utils/colmap_utils.py:colmap_fusion)
+# --------------------------------------------------------------------------------------------
+def colmap_overlap_lists(overlap, n: int) -> List[List[int]]:
+    """N lists of view indices (or an N x N boolean matrix, row k = the views that follow k, in index order) -> N lists without
+    the diagonal or repeats, range-checked."""
+    if hasattr(overlap, "shape") and len(overlap.shape) == 2:
+        a = np.asarray(overlap.cpu() if torch.is_tensor(overlap) else overlap).astype(bool)
+        if a.shape != (n, n):
+            raise ValueError(f"pscv.colmap_fuse: overlap matrix must be {n}x{n}, got {a.shape}")
+        overlap = [np.nonzero(row)[0].tolist() for row in a]
+    if len(overlap) != n:
+        raise ValueError(f"pscv.colmap_fuse: {n} overlap lists expected, got {len(overlap)}")
+    out = []
+    for k, lst in enumerate(overlap):
+        seen, row = set(), []
+        for m in lst:
+            m = int(m)
+            if not 0 <= m < n:
+                raise ValueError(f"pscv.colmap_fuse: overlap[{k}] names view {m} outside [0,{n})")
+            if m != k and m not in seen:
+                seen.add(m)
+                row.append(m)
+        out.append(row)
+    return out
+
+
+def find_next_image_order(overlap: Sequence[Sequence[int]]) -> List[int]:
+    """COLMAP's FindNextImage order over all views: after view ``prev`` the first view of ``overlap[prev]`` not yet processed,
+    else the lowest-index view not yet processed."""
+    n = len(overlap)
+    done = [False] * n
+    order, prev = [], -1
+    for _ in range(n):
+        nxt = next((m for m in overlap[prev] if not done[m]), None) if prev >= 0 else None
+        if nxt is None:
+            nxt = min(v for v in range(n) if not done[v])
+        order.append(nxt)
+        done[nxt] = True
+        prev = nxt
+    return order
+
+
+def _colmap_check(n, max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels):
+    if not 2 <= n <= L.FUSE_MAX_VIEWS:
+        raise ValueError(f"pscv.colmap_fuse: 2..{L.FUSE_MAX_VIEWS} views expected (PSCV_FUSE_MAX_VIEWS), got {n}")
+    if not 0.0 < float(np.float32(max_reproj_error)) <= 2.0:
+        raise ValueError(f"pscv.colmap_fuse: max_reproj_error must lie in (0, 2] pixels, got {max_reproj_error}")
+    if not 0.0 < float(np.float32(max_depth_error)) < 1.0:
+        raise ValueError(f"pscv.colmap_fuse: max_depth_error must lie in (0, 1), got {max_depth_error}")
+    if int(min_num_pixels) < 1:
+        raise ValueError(f"pscv.colmap_fuse: min_num_pixels must be >= 1, got {min_num_pixels}")
+    if int(max_traversal_depth) < 1:
+        raise ValueError(f"pscv.colmap_fuse: max_traversal_depth must be >= 1, got {max_traversal_depth}")
+    window = (2 * int(math.ceil(float(np.float32(max_reproj_error)))) + 1) ** 2
+    if int(max_num_pixels) < 1 + (n - 1) * window:
+        raise ValueError(f"pscv.colmap_fuse: max_num_pixels={max_num_pixels} < 1 + (N-1) x window = {1 + (n - 1) * window}: "
+                         "COLMAP's cap could cut a cluster, which the parallel rule does not model")
+
+
+class _ColmapRun:
+    """Device state shared by the passes of one fusion: packed inputs, fused masks, claim maps, workspace, output, counter."""
+
+    def __init__(self, depths, colors, cams, overlap, fused, capacity, params):
+        self.depths, self.packed, self.cams, ptrs, _ = _fuse_inputs(depths, colors, cams)
+        n = len(self.depths)
+        _colmap_check(n, *params)
+        self.params = params
+        self.overlap = colmap_overlap_lists(overlap, n)
+        self.bits = (C.c_long * n)(*[C.c_long(sum(1 << m for m in row)).value for row in self.overlap])
+        self.dptr, self.cptr, self.hw = ptrs
+        dev = self.cams.device
+        if fused is None:
+            fused = [torch.zeros(d.shape, dtype=torch.uint8, device=dev) for d in self.depths]
+        _check_used(fused, self.depths)
+        self.fused = fused
+        self.fptr = _used_ptrs(fused)
+        self.claim = [torch.full(d.shape, -1, dtype=torch.int64, device=dev) for d in self.depths]
+        self.clptr = _used_ptrs(self.claim)
+        ws_bytes = max(int(L.lib().pscv_colmap_fuse_workspace(int(d.shape[0]), int(d.shape[1]))) for d in self.depths)
+        self.ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        self.cap = sum(int(d.numel()) for d in self.depths) if capacity is None else int(capacity)
+        self.xyz = torch.empty((self.cap, 3), dtype=torch.float32, device=dev)
+        self.normal = torch.empty((self.cap, 3), dtype=torch.float32, device=dev)
+        self.rgb = torch.empty((self.cap, 3), dtype=torch.uint8, device=dev)
+        self.view = torch.empty((self.cap,), dtype=torch.int32, device=dev)
+        self.pixel = torch.empty((self.cap,), dtype=torch.int32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def run_pass(self, view: int, tag: int, processed: int):
+        n = len(self.depths)
+        e, r, mnp, mtd, _ = self.params
+        h, w = self.depths[view].shape
+        rc = _launch("colmap_fuse_pass", lambda: L.lib().pscv_colmap_fuse_pass(
+            int(view), int(tag), self.dptr, self.cptr, self.fptr, self.clptr, self.hw, n, _p(self.cams), self.bits, C.c_long(int(processed)).value,
+            float(e), float(r), int(mnp), int(mtd), _p(self.xyz), _p(self.normal), _p(self.rgb), _p(self.view), _p(self.pixel),
+            self.cap, _p(self.counter), _p(self.ws), int(self.ws.numel()), _stream()),
+            # per (seed, other view): one window of depth + mask reads, twice (phases A and B)
+            cost=lambda: (float(h * w * (n - 1) * 2 * 25 * 5), 0.0))
+        L.check(rc, "pscv_colmap_fuse_pass")
+
+    def result(self, what):
+        m = _fuse_total(self.counter, self.cap, what)
+        return self.xyz[:m], self.normal[:m], self.rgb[:m], self.view[:m], self.pixel[:m]
+
+
+def colmap_fuse_pass(view: int, depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, overlap,
+                     fused: Sequence[torch.Tensor], *, processed: Sequence[int] = (), max_depth_error: float = 0.01,
+                     max_reproj_error: float = 1.0, min_num_pixels: int = 3, max_traversal_depth: int = 100,
+                     max_num_pixels: int = 10000, capacity: Optional[int] = None):
+    """The pass of view ``view`` of ``colmap_fuse`` alone, with explicit state: ``fused`` N x uint8 [h_v,w_v] masks (updated in
+    place) and ``processed`` the views whose passes are done -> (xyz fp32 [M,3], normal fp32 [M,3], rgb uint8 [M,3], pixel int32
+    [M] = y w + x of each seed), row-major seed order.  ``capacity`` (default h w of the view) sizes the output buffer; a pass that
+    needs more raises ``PscvError``."""
+    n = len(depths)
+    if not 0 <= int(view) < n:
+        raise ValueError(f"pscv.colmap_fuse_pass: view {view} outside [0,{n})")
+    proc = 0
+    for v in processed:
+        if not 0 <= int(v) < n or int(v) == int(view):
+            raise ValueError(f"pscv.colmap_fuse_pass: processed view {v} invalid for the pass of view {view}")
+        proc |= 1 << int(v)
+    cap = int(depths[view].numel()) if capacity is None else int(capacity)
+    run = _ColmapRun(depths, colors, cams, overlap, list(fused), cap,
+                     (max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels))
+    run.run_pass(int(view), 0, proc)
+    xyz, normal, rgb, _, pixel = run.result("pscv.colmap_fuse_pass")
+    return xyz, normal, rgb, pixel
+
+
+def colmap_fuse(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, overlap, *, max_depth_error: float,
+                max_reproj_error: float, min_num_pixels: int, max_traversal_depth: int = 100, max_num_pixels: int = 10000,
+                capacity: Optional[int] = None, want_pixel: bool = False):
+    """COLMAP-style stereo fusion of N depth maps into one point cloud (the YFCC fusion of the
+    reference's pipeline): depths N x fp32 [h_v,w_v] (masked pixels 0), colors N x uint8 [h_v,w_v,3], cams [N,30]
+    (``geo_filter_cams``; intrinsics at each map's size), all on the GPU, 2 <= N <= 64; overlap N lists of view indices (COLMAP's
+    overlapping images, best first) or an N x N boolean matrix -> (xyz fp32 [M,3], normal fp32 [M,3], rgb uint8 [M,3], view int32
+    [M]) on the GPU, pass-major (FindNextImage order, computed on the host) then row-major seed order, bit-reproducible.  One
+    pscv_colmap_fuse_pass per view on the current stream; the host reads the point count once at the end.  ``capacity`` (default:
+    the total pixel count, which no run can exceed) sizes the output; a run that needs more raises ``PscvError``.  ``want_pixel``
+    appends the seed pixel index (y w_v + x) of each point."""
+    run = _ColmapRun(depths, colors, cams, overlap, None, capacity,
+                     (max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels))
+    processed = 0
+    for tag, v in enumerate(find_next_image_order(run.overlap)):
+        run.run_pass(v, tag, processed)
+        processed |= 1 << v
+    xyz, normal, rgb, view, pixel = run.result("pscv.colmap_fuse")
+    res = (xyz, normal, rgb, view)
+    return res + (pixel,) if want_pixel else res
 
 
 # --------------------------------------------------------------------------------------------

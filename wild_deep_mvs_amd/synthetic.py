@@ -400,3 +400,64 @@ def make_point_cloud_scene(n_pred: int, n_gt: int, *, seed: int = 0, outlier_fra
         pred = np.concatenate((surf, dup, out))[rng.permutation(n_pred)]
     bb = np.array([[-20.0, -20.0, -100.0], [extent + 20.0, extent + 20.0, 140.0]])
     return {"pred": pred.astype(np.float32), "gt": gt.astype(np.float32), "bb": bb}
+
+
+def make_yfcc_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, overlap: str = "all", k_overlap: int = 3,
+                           perturb: float = 0.003, outlier_view: int = 1, mask_frac: float = 0.02,
+                           spacing: float = 0.25) -> Dict[str, object]:
+    """Inputs of the COLMAP-style fusion on an "in the wild" subset: ``make_fusion_scene``'s rig and tilted plane, but every view
+    has its own size (ragged: height and width each 70-100 % of H, W, own intrinsics, focal 0.9 w), view ``outlier_view`` a
+    block of gross outliers (x 1.25), every view ``mask_frac`` masked (0) pixels and one masked rectangle.  ``overlap`` picks
+    the graph COLMAP would take from a sparse model: "all" (every other view, nearest camera centre first, ties by index),
+    "knn" (the ``k_overlap`` nearest views only: sparse and not symmetric in general) or "chain" (v-1 and v+1).  Returns
+    ``depths``, ``colors`` (uint8 [h,w,3]), ``K``, ``R`` [V,3,3], ``t`` [V,3,1] (float32 tensors) and ``overlap`` (V lists)."""
+    rng = np.random.default_rng(seed)
+    n = np.array([0.10, -0.06, 1.0])
+    n = n / np.linalg.norm(n)
+    c0 = 4.0 * n[2]
+    g = int(math.ceil(math.sqrt(V)))
+    K, R, t, depths, colors, centres = [], [], [], [], [], []
+    for v in range(V):
+        h, w = int(round(H * rng.uniform(0.7, 1.0))), int(round(W * rng.uniform(0.7, 1.0)))
+        f = 0.9 * w
+        Kv = np.array([[f, 0.0, w / 2.0 + rng.uniform(-0.5, 0.5)], [0.0, f * rng.uniform(0.98, 1.02), h / 2.0 + rng.uniform(-0.5, 0.5)],
+                       [0.0, 0.0, 1.0]])
+        gx, gy = v % g - (g - 1) / 2.0, v // g - (g - 1) / 2.0
+        c = np.array([gx * spacing, gy * spacing, 0.0]) + rng.normal(0.0, 0.02 * spacing, 3)
+        ay, ax = -0.25 * gx * spacing / 4.0 + rng.normal(0.0, 0.01), 0.25 * gy * spacing / 4.0 + rng.normal(0.0, 0.01)
+        cy, sy, cx, sx = math.cos(ay), math.sin(ay), math.cos(ax), math.sin(ax)
+        Rv = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]]) @ np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+        tv = -Rv @ c
+        ys, xs = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+        p = np.stack((xs, ys, np.ones_like(xs)), axis=-1).reshape(-1, 3)
+        ray = p @ np.linalg.inv(Kv).T @ Rv
+        d = ((c0 - n @ c) / (ray @ n)).reshape(h, w)
+        X = c + d.reshape(-1, 1) * ray
+        col = np.stack((128 + 100 * np.sin(3.1 * X[:, 0]), 128 + 100 * np.sin(2.3 * X[:, 1] + 1.0),
+                        128 + 100 * np.cos(1.7 * (X[:, 0] + X[:, 1]))), axis=-1).reshape(h, w, 3) + rng.normal(0.0, 2.0, (h, w, 3))
+        coarse = torch.from_numpy(rng.standard_normal((1, 1, max(h // 8, 2), max(w // 8, 2))))
+        bump = torch.nn.functional.interpolate(coarse, size=(h, w), mode="bilinear", align_corners=False)[0, 0].numpy()
+        d = d * (1.0 + perturb * np.tanh(bump))
+        if v == outlier_view:
+            d[h // 4:h // 2, w // 3:w // 2] *= 1.25
+        d[rng.random((h, w)) < mask_frac] = 0.0
+        r0, c0_ = int(rng.integers(0, max(h - 4, 1))), int(rng.integers(0, max(w - 6, 1)))
+        d[r0:r0 + 3, c0_:c0_ + 5] = 0.0
+        K.append(Kv); R.append(Rv); t.append(tv.reshape(3, 1)); centres.append(c)
+        depths.append(torch.from_numpy(d.astype(np.float32)).contiguous())
+        colors.append(torch.from_numpy(np.clip(np.rint(col), 0, 255).astype(np.uint8)).contiguous())
+    cen = np.stack(centres)
+    dist = np.linalg.norm(cen[:, None] - cen[None], axis=-1)
+    lists = []
+    for v in range(V):
+        others = sorted((u for u in range(V) if u != v), key=lambda u: (dist[v, u], u))
+        if overlap == "all":
+            lists.append(others)
+        elif overlap == "knn":
+            lists.append(others[:k_overlap])
+        elif overlap == "chain":
+            lists.append([u for u in (v - 1, v + 1) if 0 <= u < V])
+        else:
+            raise ValueError(f"make_yfcc_fusion_scene: unknown overlap {overlap!r}")
+    f32 = lambda a: torch.from_numpy(np.stack(a).astype(np.float32))
+    return {"depths": depths, "colors": colors, "K": f32(K), "R": f32(R), "t": f32(t), "overlap": lists}

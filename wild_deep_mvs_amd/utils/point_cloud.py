@@ -35,6 +35,37 @@ def write_point_cloud(path, xyz, rgb) -> None:
     os.replace(tmp, path)
 
 
+_COLMAP_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
+                           ("green", "u1"), ("blue", "u1")])
+
+
+def colmap_ply_header(n: int) -> bytes:
+    """The header COLMAP's stereo fusion writes for a binary fused point cloud (``float x y z nx ny nz``, ``uchar red green blue``)."""
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n}"]
+    lines += [f"property float {c}" for c in ("x", "y", "z", "nx", "ny", "nz")] + [f"property uchar {c}" for c in ("red", "green", "blue")]
+    return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
+
+
+def write_colmap_point_cloud(path, xyz, normal, rgb) -> None:
+    """xyz, normal [M,3] (cast to float32), rgb [M,3] uint8 -> binary little-endian PLY in COLMAP's fused layout at ``path``."""
+    xyz = np.asarray(getattr(xyz, "cpu", lambda: xyz)(), dtype=np.float32).reshape(-1, 3)
+    normal = np.asarray(getattr(normal, "cpu", lambda: normal)(), dtype=np.float32).reshape(-1, 3)
+    rgb = np.asarray(getattr(rgb, "cpu", lambda: rgb)())
+    if rgb.dtype != np.uint8 or rgb.shape != xyz.shape or normal.shape != xyz.shape:
+        raise ValueError(f"write_colmap_point_cloud: normal float [M,3] and rgb uint8 [M,3] expected for {xyz.shape[0]} points")
+    data = np.empty(xyz.shape[0], dtype=_COLMAP_VERTEX)
+    for k, c in enumerate("xyz"):
+        data[c] = xyz[:, k]
+        data["n" + c] = normal[:, k]
+    for k, c in enumerate(("red", "green", "blue")):
+        data[c] = rgb[:, k]
+    tmp = f"{path}.part"
+    with open(tmp, "wb") as fh:
+        fh.write(colmap_ply_header(xyz.shape[0]))
+        fh.write(data.tobytes())
+    os.replace(tmp, path)
+
+
 # the reference's ply_dtypes (utils/utils_ply.py; its later "uchar" entry wins)
 PLY_DTYPES = {b"int8": "i1", b"char": "i1", b"uint8": "u1", b"uchar": "u1", b"int16": "i2", b"short": "i2", b"uint16": "u2",
               b"ushort": "u2", b"int32": "i4", b"int": "i4", b"uint32": "u4", b"uint": "u4", b"float32": "f4", b"float": "f4",
