@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSCV_ABI_VERSION 12
+#define PSCV_ABI_VERSION 13
 
 /* storage dtypes */
 #define PSCV_F32 0
@@ -385,6 +385,49 @@ int pscv_fuse_depth_pass(int pass, const float* const* depth, const unsigned int
                          const int* hw, int n_views, const float* cams, float disp_thresh, int num_consistent, float depth_min,
                          float depth_max, float* out_xyz, unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity,
                          long long* counter, void* workspace, long workspace_bytes, void* stream);
+
+/*
+ * PatchMatch multi-view stereo (ABI 13; the COLMAP baseline of the reconstruction pipeline, where the reference runs the external
+ * `colmap patch_match_stereo` from utils/colmap_utils.py:282-322).  The rule is INTEGRATION.md section 2h: per reference pixel p a
+ * plane hypothesis (d > 0, unit normal n in the reference frame facing the camera) stored as fp32 state [h][w][4] = (d, nx, ny,
+ * nz); per source s the bilateral-weighted NCC over the (2 radius / step + 1)^2 window through the plane's homography, c_s =
+ * clamp(1 - NCC, 0, 2), 2 when the centre projects behind or outside s, a weighted variance is < 1e-5 or the triangulation angle
+ * is < 1 deg; in geometric mode c_s + 0.3 min(e_s, 3) with e_s the forward-backward error against s's depth map; the aggregated
+ * cost is the mean of the top_k smallest.
+ *   ref         device fp32 grey [h][w] of the reference view
+ *   src         host array of n_src device pointers, fp32 grey [h_s][w_s]; src_hw host int [n_src][2] = (h_s, w_s)
+ *   cams        device fp32 [n_src+1][PSCV_GEO_CAM_FLOATS] (K, K^-1, R, t), row 0 = the reference view
+ *   src_depth   host array of n_src device pointers, fp32 [h_s][w_s] photometric depth maps; NULL = photometric mode
+ *   1 <= n_src <= PSCV_PM_MAX_SRC, 1 <= radius <= PSCV_PM_MAX_RADIUS, 1 <= step <= radius, 1 <= top_k <= min(n_src,
+ *   PSCV_PM_MAX_TOPK), 0 < depth_min < depth_max
+ * pscv_patch_match_init       state <- candidate 10 at every pixel (iteration word 0xffffffff, colour 0)
+ * pscv_patch_match_cost       per-source photometric costs out_cost [n_src][h][w], errors out_err [n_src][h][w] (geometric mode;
+ *                             may be NULL) and the aggregated cost out_agg [h][w] (may be NULL) of the hypotheses in state
+ * pscv_patch_match_half_step  one red-black half-step in place on the pixels with (row + col) % 2 == colour: candidates 0-10
+ *                             (current; planes of the pixels at (0,+-1), (+-1,0), (0,+-3), (+-3,0); perturbation by delta of the
+ *                             inverse-depth range and theta radians; random), the lowest cost wins, ties to the lowest index;
+ *                             random draws hash (seed, view, pixel, iteration, colour, slot).  out_choice int [h][w] and out_cand
+ *                             fp32 [h][w][11][4] (0 = skipped) receive the chosen index and the candidates when not NULL.
+ * pscv_patch_match_filter     COLMAP's filter: a pixel is kept when >= 2 sources have c_s <= 0.9, an angle >= 3 deg and e_s <= 1 px
+ *                             (src_depth required); out_depth [h][w], out_normal [h][w][3] (0 elsewhere), out_count [h][w] (may
+ *                             be NULL) the passing sources.
+ * No host synchronisation: one launch each on `stream`.  seed, view, iteration are used as 32-bit unsigned words.
+ */
+#define PSCV_PM_MAX_SRC 31
+#define PSCV_PM_MAX_RADIUS 8
+#define PSCV_PM_MAX_TOPK 8
+int pscv_patch_match_init(float* state, int h, int w, const float* cams, float depth_min, float depth_max, int seed, int view,
+                          void* stream);
+int pscv_patch_match_cost(const float* state, const float* ref, int h, int w, const float* const* src, const int* src_hw, int n_src,
+                          const float* cams, const float* const* src_depth, int radius, int step, int top_k, float* out_cost,
+                          float* out_err, float* out_agg, void* stream);
+int pscv_patch_match_half_step(float* state, const float* ref, int h, int w, const float* const* src, const int* src_hw, int n_src,
+                               const float* cams, const float* const* src_depth, float depth_min, float depth_max, int radius,
+                               int step, int top_k, int seed, int view, int iteration, int colour, float delta, float theta,
+                               int* out_choice, float* out_cand, void* stream);
+int pscv_patch_match_filter(const float* state, const float* ref, int h, int w, const float* const* src, const int* src_hw,
+                            int n_src, const float* cams, const float* const* src_depth, int radius, int step, float* out_depth,
+                            float* out_normal, int* out_count, void* stream);
 
 /*
  * COLMAP-style stereo fusion of depth maps into one point cloud (ABI 12; the YFCC path, where the reference runs the external

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("PSCV_LIB") or os.path.join(_HERE, "libpscv.so")     #
 CSRC = os.path.join(_HERE, "csrc")
 
 # mirror of include/pscv.h
-ABI_VERSION = 12
+ABI_VERSION = 13
 F32, BF16, F16 = 0, 1, 2
 GEOM_PROJ, GEOM_HOMOG = 0, 1
 COST_VARIANCE, COST_VARIANCE_CVP, COST_SOFTMIN, COST_GROUPCORR, COST_WARP_ONLY, COST_VARIANCE_PARTIAL = 0, 1, 2, 3, 4, 5
@@ -27,6 +27,7 @@ CAM_FLOATS = 18
 GEO_MAX_SRC = 32
 GEO_CAM_FLOATS = 30
 FUSE_MAX_VIEWS = 64
+PM_MAX_SRC, PM_MAX_RADIUS, PM_MAX_TOPK = 31, 8, 8
 
 EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_cams", "pscv_homog_cams", "pscv_warp_cost",
            "pscv_fuse_pairs", "pscv_fuse_finish", "pscv_geo_filter", "pscv_pack_conv2d_weights", "pscv_conv2d",
@@ -39,7 +40,8 @@ EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_
            "pscv_bn_bwd_apply_grouped", "pscv_pack_conv2d_weights_device", "pscv_leaky_relu_bwd", "pscv_leaky_relu_bwd_sum", "pscv_pack_conv2d_weights_device_ex", "pscv_warp_cost_rows",
            "pscv_tail_sweep", "pscv_tail_sweep_workspace", "pscv_fuse_depth_workspace", "pscv_fuse_depth_pass",
            "pscv_point_grid_workspace", "pscv_point_grid_build", "pscv_point_nn_dist", "pscv_dtu_cell_occupancy", "pscv_radius_mis_round",
-           "pscv_radius_mis_workspace", "pscv_radius_mis_compact", "pscv_colmap_fuse_workspace", "pscv_colmap_fuse_pass")
+           "pscv_radius_mis_workspace", "pscv_radius_mis_compact", "pscv_colmap_fuse_workspace", "pscv_colmap_fuse_pass",
+           "pscv_patch_match_init", "pscv_patch_match_cost", "pscv_patch_match_half_step", "pscv_patch_match_filter")
 
 
 class PscvMissingError(RuntimeError):
@@ -141,6 +143,15 @@ def _declare(lib):
                                          vp, l, vp, vp, l, vp]
     lib.pscv_colmap_fuse_workspace.restype = l
     lib.pscv_colmap_fuse_workspace.argtypes = [i, i]
+    lib.pscv_patch_match_init.restype = i
+    lib.pscv_patch_match_init.argtypes = [vp, i, i, vp, f, f, i, i, vp]
+    lib.pscv_patch_match_cost.restype = i
+    lib.pscv_patch_match_cost.argtypes = [vp, vp, i, i, C.POINTER(vp), C.POINTER(i), i, vp, C.POINTER(vp), i, i, i, vp, vp, vp, vp]
+    lib.pscv_patch_match_half_step.restype = i
+    lib.pscv_patch_match_half_step.argtypes = [vp, vp, i, i, C.POINTER(vp), C.POINTER(i), i, vp, C.POINTER(vp), f, f, i, i, i, i, i,
+                                               i, i, f, f, vp, vp, vp]
+    lib.pscv_patch_match_filter.restype = i
+    lib.pscv_patch_match_filter.argtypes = [vp, vp, i, i, C.POINTER(vp), C.POINTER(i), i, vp, C.POINTER(vp), i, i, vp, vp, vp, vp]
     lib.pscv_colmap_fuse_pass.restype = i
     lib.pscv_colmap_fuse_pass.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp,
                                           C.POINTER(l), l, f, f, i, i, vp, vp, vp, vp, vp, l, vp, vp, l, vp]

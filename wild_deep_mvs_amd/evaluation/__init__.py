@@ -1,4 +1,4 @@
 """Mirror of the reference's ``evaluation`` package for the steps that follow the plane-sweep path:
 the geometric-consistency filter (``filtering``), the fusion of the filtered depth maps into a point cloud (``fusibile`` for DTU,
-``colmap_fusion`` for YFCC) and the point-cloud metrics (``metrics``: radius downsampling and bounded Chamfer distances).  COLMAP's
-sparse reconstruction and patch match are out of scope."""
+``colmap_fusion`` for YFCC), the point-cloud metrics (``metrics``: radius downsampling and bounded Chamfer distances) and the
+COLMAP baseline's PatchMatch stereo (``colmap_stereo``).  COLMAP's sparse reconstruction is out of scope."""

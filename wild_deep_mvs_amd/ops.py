@@ -740,6 +740,187 @@ def colmap_fuse(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], 
 
 
 # --------------------------------------------------------------------------------------------
+# PatchMatch multi-view stereo (the COLMAP baseline: utils/colmap_utils.py:depthmap_colmap)
+# --------------------------------------------------------------------------------------------
+PM_DELTA0, PM_THETA0_DEG = 0.25, 30.0      # candidate 9: inverse-depth fraction and normal angle, halved every iteration
+
+
+def patch_match_schedule(t: int):
+    """(delta_t, theta_t) of pass-local iteration t: delta_t = 0.25 / 2^t of the inverse-depth range,
+    theta_t = 30 deg / 2^t."""
+    return PM_DELTA0 * 0.5 ** t, math.radians(PM_THETA0_DEG) * 0.5 ** t
+
+
+def _u32(x: int) -> int:
+    """A 32-bit unsigned word as the C ABI's int."""
+    return C.c_int(int(x) & 0xFFFFFFFF).value
+
+
+class _PmInputs:
+    """Validated device inputs of one reference view: grey images, camera blocks, pointer arrays, limits."""
+
+    def __init__(self, ref, srcs, cams, src_depths, radius, step, top_k, depth_range=None, what="pscv.patch_match"):
+        srcs = list(srcs)
+        S = len(srcs)
+        if not 1 <= S <= L.PM_MAX_SRC:
+            raise ValueError(f"{what}: 1..{L.PM_MAX_SRC} source views expected (PSCV_PM_MAX_SRC), got {S}")
+        if not 1 <= int(radius) <= L.PM_MAX_RADIUS:
+            raise ValueError(f"{what}: window radius {radius} outside [1,{L.PM_MAX_RADIUS}] (the LDS tile's halo)")
+        if not 1 <= int(step) <= int(radius):
+            raise ValueError(f"{what}: window step {step} outside [1,radius={radius}]")
+        top_k = min(S, 3) if top_k is None else int(top_k)
+        if not 1 <= top_k <= min(S, L.PM_MAX_TOPK):
+            raise ValueError(f"{what}: top_k={top_k} outside [1,min(S={S},{L.PM_MAX_TOPK})]")
+        if depth_range is not None:
+            dmin, dmax = (float(np.float32(x)) for x in depth_range)
+            if not 0.0 < dmin < dmax or not math.isfinite(dmax):
+                raise ValueError(f"{what}: need 0 < depth_min < depth_max, got {depth_range}")
+        _dev(ref, cams, *srcs)
+        for t in [ref, cams] + srcs:
+            if t.dtype != torch.float32:
+                raise ValueError(f"{what}: fp32 images and cameras expected, got {t.dtype}")
+        if ref.dim() != 2 or any(s.dim() != 2 for s in srcs):
+            raise ValueError(f"{what}: grey images must be [h,w]")
+        if tuple(cams.shape) != (S + 1, L.GEO_CAM_FLOATS):
+            raise ValueError(f"{what}: cams [S+1,{L.GEO_CAM_FLOATS}] expected (geo_filter_cams, reference first), got {tuple(cams.shape)}")
+        self.ref, self.srcs, self.cams = ref, srcs, cams
+        self.h, self.w = ref.shape
+        self.S, self.radius, self.step, self.top_k = S, int(radius), int(step), top_k
+        self.sptr = (C.c_void_p * S)(*[s.data_ptr() for s in srcs])
+        self.hw = (C.c_int * (2 * S))(*[v for s in srcs for v in s.shape])
+        self.dptr = None
+        self.src_depths = None
+        if src_depths is not None:
+            src_depths = list(src_depths)
+            if len(src_depths) != S:
+                raise ValueError(f"{what}: {S} source depth maps expected, got {len(src_depths)}")
+            _dev(*src_depths)
+            for s, d in zip(srcs, src_depths):
+                if d.dtype != torch.float32 or tuple(d.shape) != tuple(s.shape):
+                    raise ValueError(f"{what}: source depth maps must be fp32 of their image's size")
+            self.src_depths = src_depths
+            self.dptr = (C.c_void_p * S)(*[d.data_ptr() for d in src_depths])
+
+    def check_state(self, state, what):
+        _dev(state)
+        if state.dtype != torch.float32 or tuple(state.shape) != (self.h, self.w, 4):
+            raise ValueError(f"{what}: state must be fp32 [h,w,4] = (depth, normal), got {state.dtype} {tuple(state.shape)}")
+
+    def taps(self):
+        return (2 * (self.radius // self.step) + 1) ** 2
+
+
+def patch_match_init(h: int, w: int, cams: torch.Tensor, depth_min: float, depth_max: float, *, seed: int = 0,
+                     view: int = 0) -> torch.Tensor:
+    """Random initial state fp32 [h,w,4] (candidate 10 of section 2h at every pixel); cams row 0 = the reference view."""
+    if not 0.0 < float(np.float32(depth_min)) < float(np.float32(depth_max)):
+        raise ValueError(f"pscv.patch_match_init: need 0 < depth_min < depth_max, got {depth_min}, {depth_max}")
+    _dev(cams)
+    if cams.dtype != torch.float32 or cams.dim() != 2 or cams.shape[1] != L.GEO_CAM_FLOATS:
+        raise ValueError("pscv.patch_match_init: cams [V,30] fp32 expected")
+    state = torch.empty((int(h), int(w), 4), dtype=torch.float32, device=cams.device)
+    rc = _launch("patch_match_init", lambda: L.lib().pscv_patch_match_init(_p(state), int(h), int(w), _p(cams), float(depth_min),
+                                                                          float(depth_max), _u32(seed), _u32(view), _stream()))
+    L.check(rc, "pscv_patch_match_init")
+    return state
+
+
+def patch_match_cost(state: torch.Tensor, ref: torch.Tensor, srcs: Sequence[torch.Tensor], cams: torch.Tensor, *,
+                     src_depths: Optional[Sequence[torch.Tensor]] = None, radius: int = 5, step: int = 1,
+                     top_k: Optional[int] = None):
+    """Costs of the hypotheses in ``state`` fp32 [h,w,4] (depth, normal): ref grey fp32 [h,w], srcs S x grey fp32 [h_s,w_s], cams
+    [S+1,30] (``geo_filter_cams``, reference first), all on the GPU -> (c_s fp32 [S,h,w] photometric, e_s fp32 [S,h,w] or None
+    (with ``src_depths``), aggregated cost fp32 [h,w]: mean of the ``top_k`` (default min(S,3)) smallest c_s, + 0.3 min(e_s, 3)
+    in geometric mode).  An invalid source costs exactly 2."""
+    x = _PmInputs(ref, srcs, cams, src_depths, radius, step, top_k, what="pscv.patch_match_cost")
+    x.check_state(state, "pscv.patch_match_cost")
+    cost = torch.empty((x.S, x.h, x.w), dtype=torch.float32, device=ref.device)
+    err = torch.empty_like(cost) if src_depths is not None else None
+    agg = torch.empty((x.h, x.w), dtype=torch.float32, device=ref.device)
+    rc = _launch("patch_match_cost", lambda: L.lib().pscv_patch_match_cost(
+        _p(state), _p(ref), x.h, x.w, x.sptr, x.hw, x.S, _p(cams), x.dptr, x.radius, x.step, x.top_k, _p(cost), _p(err), _p(agg),
+        _stream()), cost=lambda: (float(x.h * x.w * x.S * x.taps() * 16), float(x.h * x.w * x.S * x.taps() * 30)))
+    L.check(rc, "pscv_patch_match_cost")
+    return cost, err, agg
+
+
+def patch_match_half_step(state: torch.Tensor, ref: torch.Tensor, srcs: Sequence[torch.Tensor], cams: torch.Tensor,
+                          depth_min: float, depth_max: float, *, colour: int, iteration: int, delta: float, theta: float,
+                          seed: int = 0, view: int = 0, src_depths: Optional[Sequence[torch.Tensor]] = None, radius: int = 5,
+                          step: int = 1, top_k: Optional[int] = None, want_choice: bool = False, want_candidates: bool = False,
+                          _x: Optional[_PmInputs] = None):
+    """One red-black half-step of section 2h, in place on ``state`` (the pixels with (row + col) % 2 == colour).  ``iteration`` is
+    the 32-bit word the random draws hash; ``delta`` / ``theta`` the perturbation of candidate 9.  Returns (choice int32 [h,w] or
+    None, candidates fp32 [h,w,11,4] or None) as asked."""
+    x = _x or _PmInputs(ref, srcs, cams, src_depths, radius, step, top_k, (depth_min, depth_max), "pscv.patch_match_half_step")
+    if _x is None:
+        x.check_state(state, "pscv.patch_match_half_step")
+    if colour not in (0, 1):
+        raise ValueError(f"pscv.patch_match_half_step: colour {colour} is not 0 or 1")
+    choice = torch.full((x.h, x.w), -1, dtype=torch.int32, device=ref.device) if want_choice else None
+    cand = torch.zeros((x.h, x.w, 11, 4), dtype=torch.float32, device=ref.device) if want_candidates else None
+    rc = _launch("patch_match_half_step", lambda: L.lib().pscv_patch_match_half_step(
+        _p(state), _p(ref), x.h, x.w, x.sptr, x.hw, x.S, _p(cams), x.dptr, float(depth_min), float(depth_max), x.radius, x.step,
+        x.top_k, _u32(seed), _u32(view), _u32(iteration), int(colour), float(delta), float(theta), _p(choice), _p(cand), _stream()),
+        # per pixel of the colour: 11 candidates x S sources x taps bilinear gathers (16 B) and ~30 flops each
+        cost=lambda: (float(x.h * x.w // 2 * 11 * x.S * x.taps() * 16), float(x.h * x.w // 2 * 11 * x.S * x.taps() * 30)))
+    L.check(rc, "pscv_patch_match_half_step")
+    return choice, cand
+
+
+def patch_match(ref: torch.Tensor, srcs: Sequence[torch.Tensor], cams: torch.Tensor, depth_min: float, depth_max: float, *,
+                num_iterations: int = 8, seed: int = 0, view: int = 0, src_depths: Optional[Sequence[torch.Tensor]] = None,
+                state: Optional[torch.Tensor] = None, radius: int = 5, step: int = 1, top_k: Optional[int] = None) -> torch.Tensor:
+    """PatchMatch stereo of one reference view -> state fp32 [h,w,4] (depth, normal in the reference
+    frame).  Photometric pass: from the random initialisation (or ``state``).  Geometric pass (``src_depths``, the sources'
+    photometric depth maps): from ``state``, the view's photometric result, with c_s + 0.3 min(e_s, 3).  ``num_iterations`` red +
+    black half-steps on the current stream, no host synchronisation; the result is bit-reproducible."""
+    pas = 0 if src_depths is None else 1
+    x = _PmInputs(ref, srcs, cams, src_depths, radius, step, top_k, (depth_min, depth_max), "pscv.patch_match")
+    if int(num_iterations) < 0 or int(num_iterations) > 0xFFFF:
+        raise ValueError(f"pscv.patch_match: num_iterations={num_iterations} outside [0,65535]")
+    if state is None:
+        if pas:
+            raise ValueError("pscv.patch_match: the geometric pass starts from the view's photometric state")
+        state = patch_match_init(x.h, x.w, cams, depth_min, depth_max, seed=seed, view=view)
+    else:
+        x.check_state(state, "pscv.patch_match")
+        state = state.clone()
+    for t in range(int(num_iterations)):
+        delta, theta = patch_match_schedule(t)
+        for colour in (0, 1):
+            patch_match_half_step(state, ref, srcs, cams, depth_min, depth_max, colour=colour, iteration=(pas << 16) | t,
+                                  delta=delta, theta=theta, seed=seed, view=view, _x=x)
+    return state
+
+
+def patch_match_filter(state: torch.Tensor, ref: torch.Tensor, srcs: Sequence[torch.Tensor], cams: torch.Tensor,
+                       src_depths: Sequence[torch.Tensor], *, radius: int = 5, step: int = 1, want_count: bool = False):
+    """COLMAP's filter on ``state`` (section 2h): a pixel is kept when at least 2 sources have c_s <= 0.9, a triangulation angle
+    >= 3 deg and e_s <= 1 px against ``src_depths`` -> (depth fp32 [h,w], normal fp32 [h,w,3]), 0 where filtered out (and the
+    int32 [h,w] count of passing sources with ``want_count``)."""
+    if src_depths is None:
+        raise ValueError("pscv.patch_match_filter: the sources' depth maps are required")
+    x = _PmInputs(ref, srcs, cams, src_depths, radius, step, 1, what="pscv.patch_match_filter")
+    x.check_state(state, "pscv.patch_match_filter")
+    depth = torch.empty((x.h, x.w), dtype=torch.float32, device=ref.device)
+    normal = torch.empty((x.h, x.w, 3), dtype=torch.float32, device=ref.device)
+    count = torch.empty((x.h, x.w), dtype=torch.int32, device=ref.device) if want_count else None
+    rc = _launch("patch_match_filter", lambda: L.lib().pscv_patch_match_filter(
+        _p(state), _p(ref), x.h, x.w, x.sptr, x.hw, x.S, _p(cams), x.dptr, x.radius, x.step, _p(depth), _p(normal), _p(count),
+        _stream()), cost=lambda: (float(x.h * x.w * x.S * x.taps() * 16), float(x.h * x.w * x.S * x.taps() * 30)))
+    L.check(rc, "pscv_patch_match_filter")
+    return (depth, normal, count) if want_count else (depth, normal)
+
+
+def grey_image(img: torch.Tensor) -> torch.Tensor:
+    """[3,H,W] image in [0,1] -> fp32 grey [H,W] on the same device: x 255 truncated to bytes (the ToPILImage path), then
+    (0.299 R + 0.587 G + 0.114 B) / 255 (plumbing, section 2h)."""
+    b = torch.floor(img.to(torch.float32) * 255.0).clamp(0, 255)
+    return ((0.299 * b[0] + 0.587 * b[1] + 0.114 * b[2]) / 255.0).to(torch.float32).contiguous()
+
+
+# --------------------------------------------------------------------------------------------
 # point-cloud metrics (the step after fusion): grids, bounded nearest neighbour, radius MIS
 # --------------------------------------------------------------------------------------------
 GRID_SPAN = 1 << 21          # cells per axis a grid can address (21-bit key fields)

@@ -461,3 +461,123 @@ def make_yfcc_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, overlap: st
             raise ValueError(f"make_yfcc_fusion_scene: unknown overlap {overlap!r}")
     f32 = lambda a: torch.from_numpy(np.stack(a).astype(np.float32))
     return {"depths": depths, "colors": colors, "K": f32(K), "R": f32(R), "t": f32(t), "overlap": lists}
+
+
+def _pm_texture(X: np.ndarray, freqs: np.ndarray, phases: np.ndarray) -> np.ndarray:
+    """Procedural colour in [0,1] of world points X [N,3]: per channel tanh of a sum of 3-D sinusoids (freqs [3,k,3], phases
+    [3,k]), so every view sees the same surface pattern."""
+    return np.stack([0.5 + 0.45 * np.tanh((np.sin(X @ freqs[c].T + phases[c][None])).sum(1) / math.sqrt(freqs.shape[1] / 2.0))
+                     for c in range(3)], axis=0)
+
+
+def make_patch_match_scene(V: int, H: int, W: int, *, seed: int = 0, spacing: float = 0.4, noise: float = 0.002
+                           ) -> Dict[str, object]:
+    """A photo-consistent scene for the PatchMatch stereo with ground truth.  A tilted background plane (depth about 5) and an
+    occluding sphere in front (depth about 2.7-3.5), textured by ``_pm_texture`` in world coordinates except an untextured disc on
+    the plane (constant grey, radius 1); V pinhole cameras on a ragged grid (``spacing`` apart, jittered, each looking at a jittered point
+    of the scene), all H x W with focal 0.9 W; colours averaged over 2 x 2 samples per pixel; per-view gain and bias and Gaussian noise (``noise``) on the [0,1] image.
+
+    Returns ``imgs`` [V,3,H,W] in [0,1], ``K``, ``R`` [V,3,3], ``t`` [V,3,1], ``depth_min``, ``depth_max`` [V] (0.8 x / 1.25 x
+    the view's true range), ``src`` (per view: every other view, nearest camera centre first), the ground truth ``depth`` [V,H,W]
+    and ``normal`` [V,H,W,3] (camera frame, facing the camera), ``untextured`` [V,H,W] bool (pixels whose 11 x 11 window lies
+    wholly on the disc) and ``vis`` [V,H,W] int (the
+    number of other views that see the pixel's point unoccluded inside their image) -- float32 / bool / int64 tensors."""
+    rng = np.random.default_rng(seed)
+    pn = np.array([0.2, -0.15, -1.0])
+    pn /= np.linalg.norm(pn)
+    p0 = np.array([0.0, 0.0, 5.0])
+    sc, sr = np.array([0.3, 0.15, 3.6]), 0.8
+    u_ax = np.cross(pn, [0.0, 1.0, 0.0]); u_ax /= np.linalg.norm(u_ax)
+    disc = p0 + 1.5 * u_ax + 1.0 * np.cross(pn, u_ax)           # centre of the untextured disc on the plane, radius 1
+    mags = rng.uniform(12.0, 36.0, (3, 10))
+    dirs = rng.standard_normal((3, 10, 3))
+    freqs = dirs / np.linalg.norm(dirs, axis=-1, keepdims=True) * mags[..., None]
+    phases = rng.uniform(0.0, 2.0 * math.pi, (3, 10))
+    g = int(math.ceil(math.sqrt(V)))
+    Ks, Rs, ts, cs = [], [], [], []
+    for v in range(V):
+        f = 0.9 * W
+        Ks.append(np.array([[f, 0.0, W / 2.0 + rng.uniform(-1, 1)], [0.0, f * rng.uniform(0.98, 1.02), H / 2.0 + rng.uniform(-1, 1)],
+                            [0.0, 0.0, 1.0]]))
+        c = np.array([(v % g - (g - 1) / 2.0) * spacing, (v // g - (g - 1) / 2.0) * spacing, 0.0]) + rng.normal(0.0, 0.15 * spacing, 3)
+        z = np.array([0.0, 0.0, 4.5]) + rng.normal(0.0, 0.3, 3) - c
+        z /= np.linalg.norm(z)
+        x = np.cross([0.0, 1.0, 0.0], z); x /= np.linalg.norm(x)
+        Rv = np.stack([x, np.cross(z, x), z])
+        Rs.append(Rv); ts.append(-Rv @ c); cs.append(c)
+    ys, xs = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    pix = np.stack((xs, ys, np.ones_like(xs)), axis=-1).reshape(-1, 3)
+    depth, normal, world, imgs, untex = [], [], [], [], []
+    for v in range(V):
+        r = pix @ np.linalg.inv(Ks[v]).T @ Rs[v]                      # world ray per pixel with camera-frame z = 1
+        c = cs[v]
+        lam_p = (pn @ (p0 - c)) / (r @ pn)
+        oc = c - sc
+        a, b, cc = (r * r).sum(1), 2.0 * (r @ oc), oc @ oc - sr * sr
+        disc_ = b * b - 4 * a * cc
+        lam_s = np.where(disc_ >= 0, (-b - np.sqrt(np.maximum(disc_, 0.0))) / (2 * a), np.inf)
+        hit_s = (lam_s > 0) & (lam_s < lam_p)
+        lam = np.where(hit_s, lam_s, lam_p)
+        X = c + lam[:, None] * r
+        nw = np.where(hit_s[:, None], (X - sc) / sr, pn[None])
+        nc = nw @ Rs[v].T
+        nc = np.where(((nc * (pix @ np.linalg.inv(Ks[v]).T)).sum(1) > 0)[:, None], -nc, nc)
+        flat = ~hit_s & (np.linalg.norm(X - disc, axis=1) < 1.0)
+        col = np.zeros((3, H * W))
+        for sy, sx in ((-0.25, -0.25), (-0.25, 0.25), (0.25, -0.25), (0.25, 0.25)):     # 2 x 2 supersampling of the texture
+            rs = (pix + np.array([sx, sy, 0.0])) @ np.linalg.inv(Ks[v]).T @ Rs[v]
+            lp = (pn @ (p0 - c)) / (rs @ pn)
+            bs = 2.0 * (rs @ oc)
+            ds_ = bs * bs - 4 * (rs * rs).sum(1) * cc
+            ls = np.where(ds_ >= 0, (-bs - np.sqrt(np.maximum(ds_, 0.0))) / (2 * (rs * rs).sum(1)), np.inf)
+            ls = np.where((ls > 0) & (ls < lp), ls, lp)
+            Xs = c + ls[:, None] * rs
+            col += 0.25 * np.where((np.linalg.norm(Xs - disc, axis=1) < 1.0)[None], 0.5, _pm_texture(Xs, freqs, phases))
+        gain, bias = rng.uniform(0.75, 1.15), rng.uniform(-0.05, 0.08)
+        img = np.clip(gain * col + bias + rng.normal(0.0, noise, col.shape), 0.0, 1.0)
+        depth.append(lam.reshape(H, W)); normal.append(nc.reshape(H, W, 3)); world.append(X)
+        # untextured for a window matcher: the whole 11 x 11 window lies on the disc (erosion by 5 pixels)
+        fl = flat.reshape(H, W)
+        er = fl.copy()
+        for dy in range(-5, 6):
+            for dx in range(-5, 6):
+                er &= np.roll(fl, (dy, dx), axis=(0, 1))
+        er[:5] = er[-5:] = False
+        er[:, :5] = er[:, -5:] = False
+        imgs.append(img.reshape(3, H, W)); untex.append(er)
+    vis = np.zeros((V, H * W), dtype=np.int64)
+    for v in range(V):
+        for s in range(V):
+            if s == v:
+                continue
+            y = (world[v] @ Rs[s].T + ts[s]) @ Ks[s].T
+            ok = y[:, 2] > 0
+            u, w_ = y[:, 0] / np.where(ok, y[:, 2], 1.0), y[:, 1] / np.where(ok, y[:, 2], 1.0)
+            qx, qy = np.floor(u + 0.5).astype(np.int64), np.floor(w_ + 0.5).astype(np.int64)
+            ok &= (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+            ds = depth[s][np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1)]
+            vis[v] += ok & (np.abs(ds - y[:, 2]) <= 0.01 * y[:, 2])
+    cen = np.stack(cs)
+    src = [sorted((u for u in range(V) if u != v), key=lambda u: (float(np.linalg.norm(cen[u] - cen[v])), u)) for v in range(V)]
+    f32 = lambda a: torch.from_numpy(np.stack(a).astype(np.float32))
+    dep = np.stack(depth)
+    return {"imgs": f32(imgs), "K": f32(Ks), "R": f32(Rs), "t": f32([t.reshape(3, 1) for t in ts]),
+            "depth_min": torch.from_numpy((0.8 * dep.reshape(V, -1).min(1)).astype(np.float32)),
+            "depth_max": torch.from_numpy((1.25 * dep.reshape(V, -1).max(1)).astype(np.float32)),
+            "src": src, "depth": f32(depth), "normal": f32(normal), "untextured": torch.from_numpy(np.stack(untex)),
+            "vis": torch.from_numpy(vis.reshape(V, H, W))}
+
+
+def patch_match_batches(scene: Mapping[str, object], names: Sequence[str] = None, max_src: int = None):
+    """Dataloader batches of a ``make_patch_match_scene`` scene, shaped like the YFCC loader's (batch size 1): per reference view
+    v, ``imgs`` [1,1+S,3,H,W], ``K``, ``R`` [1,1+S,3,3], ``t`` [1,1+S,3,1], ``depth_min``, ``depth_max`` [1,1+S], ``filename`` [name]
+    and ``src_filenames`` [[name] per source], sources = ``scene["src"][v]`` (the first ``max_src``)."""
+    V = scene["imgs"].shape[0]
+    names = [f"{v:08d}" for v in range(V)] if names is None else list(names)
+    out = []
+    for v in range(V):
+        ids = [v] + list(scene["src"][v])[:max_src]
+        out.append({"imgs": scene["imgs"][ids][None], "K": scene["K"][ids][None], "R": scene["R"][ids][None],
+                    "t": scene["t"][ids][None], "depth_min": scene["depth_min"][ids][None], "depth_max": scene["depth_max"][ids][None],
+                    "filename": [names[v]], "src_filenames": [[names[u]] for u in ids[1:]]})
+    return out
