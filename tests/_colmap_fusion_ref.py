@@ -10,13 +10,11 @@ from collections import deque
 
 import numpy as np
 
+from tests._fusion_ref import cam_rows
+
 PIX_LIMIT = float(1 << 30)
 INV_SQRT3 = 0.57735026918962573
 FLT_EPS = float(np.finfo(np.float32).eps)
-
-
-def cam_rows(cams):
-    return np.asarray(cams, dtype=np.float32).astype(np.float64)
 
 
 def unproject(c, x, y, d):

@@ -31,8 +31,13 @@ def read_ply(path):
         return np.fromfile(fh, dtype=props, count=n)
 
 
+def cam_rows(cams):
+    """Camera blocks [N,30] (K, K^-1, R, t) as float64 rows of their fp32 values."""
+    return np.asarray(cams, dtype=np.float32).astype(np.float64)
+
+
 def cam_parts(cams):
-    c = np.asarray(cams, dtype=np.float32).astype(np.float64)
+    c = cam_rows(cams)
     K, Ki, R, t = c[:, 0:9].reshape(-1, 3, 3), c[:, 9:18].reshape(-1, 3, 3), c[:, 18:27].reshape(-1, 3, 3), c[:, 27:30]
     return K, Ki, R, t
 

@@ -12,6 +12,8 @@ import math
 
 import numpy as np
 
+from tests._fusion_ref import cam_parts
+
 SIGMA_COLOR = 0.2
 MIN_VAR = 1e-5
 MIN_TRI_DEG = 1.0
@@ -72,15 +74,10 @@ def grey(img):
     return ((np.float32(0.299) * b[0] + np.float32(0.587) * b[1] + np.float32(0.114) * b[2]) / np.float32(255.0)).astype(np.float32)
 
 
-def _blocks(cams):
-    c = np.asarray(cams, dtype=np.float32).astype(np.float64)
-    return c[:, 0:9].reshape(-1, 3, 3), c[:, 9:18].reshape(-1, 3, 3), c[:, 18:27].reshape(-1, 3, 3), c[:, 27:30]
-
-
 def source_geometry(cams):
     """Per source s (rows 1..S): A = K_s R_rel K_r^-1, b = K_s t_rel, C = -R_rel^T t_rel (s's centre in r's frame),
     G = K_r R_rel^T K_s^-1, c = K_r C, with R_rel = R_s R_r^T, t_rel = t_s - R_rel t_r.  Also K_r^-1."""
-    K, Ki, R, t = _blocks(cams)
+    K, Ki, R, t = cam_parts(cams)
     out = []
     for s in range(1, K.shape[0]):
         Rr = R[s] @ R[0].T

@@ -6,8 +6,8 @@
 //      every pixel it reaches with a 64-bit atomicMin of (pass tag, seed index) on the claim map;
 //   B  each seed recomputes its closure over the pixels whose claim is its own, marks its seed pixel and that cluster fused, and
 //      when the cluster holds at least min_num_pixels pixels stages one point (exact per-coordinate medians) at its seed's slot.
-// Then count (per 64-pixel segment), scan (one workgroup; the running offset stays on the device) and scatter, as in
-// depth_fusion.hip.  Output order is pass-major, then row-major seed order; nothing depends on atomics order or scheduling.
+// Then count (per 64-pixel segment), scan (one workgroup, geo_common.h; the running offset stays on the device) and scatter, as
+// in depth_fusion.hip.  Output order is pass-major, then row-major seed order; nothing depends on atomics order or scheduling.
 //
 // Mapping: a wave holds 64 / P seeds, P = next_pow2(n_views) lanes per seed, lane m of a group owns view m.  The lane projects
 // the seed's point X_s into view m once and keeps a bitmask of the (2W+1)^2 window pixels around the projection that pass the
@@ -21,7 +21,7 @@
 // numpy restatement in tests/_colmap_fusion_ref.py reproduces every value bit for bit.
 //
 // Replaces (fdarmon/wild_deep_mvs): utils/colmap_utils.py:391-400, the external `colmap stereo_fusion` run.
-#include "pscv_common.h"
+#include "geo_common.h"
 
 namespace pscv {
 
@@ -46,23 +46,25 @@ struct CfArgs {
 
 // R^T (d K^-1 (x, y, 1) - t)
 __device__ __forceinline__ void cf_unproject(const float* c, double x, double y, double d, double& X, double& Y, double& Z) {
+    const float *Ki = c + CAM_KINV, *R = c + CAM_R, *t = c + CAM_T;
     const double px = x * d, py = y * d, pz = d;
-    const double a0 = (double)c[9] * px + (double)c[10] * py + (double)c[11] * pz;
-    const double a1 = (double)c[12] * px + (double)c[13] * py + (double)c[14] * pz;
-    const double a2 = (double)c[15] * px + (double)c[16] * py + (double)c[17] * pz;
-    const double b0 = a0 - (double)c[27], b1 = a1 - (double)c[28], b2 = a2 - (double)c[29];
-    X = (double)c[18] * b0 + (double)c[21] * b1 + (double)c[24] * b2;
-    Y = (double)c[19] * b0 + (double)c[22] * b1 + (double)c[25] * b2;
-    Z = (double)c[20] * b0 + (double)c[23] * b1 + (double)c[26] * b2;
+    const double a0 = (double)Ki[0] * px + (double)Ki[1] * py + (double)Ki[2] * pz;
+    const double a1 = (double)Ki[3] * px + (double)Ki[4] * py + (double)Ki[5] * pz;
+    const double a2 = (double)Ki[6] * px + (double)Ki[7] * py + (double)Ki[8] * pz;
+    const double b0 = a0 - (double)t[0], b1 = a1 - (double)t[1], b2 = a2 - (double)t[2];
+    X = (double)R[0] * b0 + (double)R[3] * b1 + (double)R[6] * b2;
+    Y = (double)R[1] * b0 + (double)R[4] * b1 + (double)R[7] * b2;
+    Z = (double)R[2] * b0 + (double)R[5] * b1 + (double)R[8] * b2;
 }
 // K (R X + t)
 __device__ __forceinline__ void cf_project(const float* c, double X, double Y, double Z, double& x, double& y, double& z) {
-    const double e0 = (double)c[18] * X + (double)c[19] * Y + (double)c[20] * Z + (double)c[27];
-    const double e1 = (double)c[21] * X + (double)c[22] * Y + (double)c[23] * Z + (double)c[28];
-    const double e2 = (double)c[24] * X + (double)c[25] * Y + (double)c[26] * Z + (double)c[29];
-    x = (double)c[0] * e0 + (double)c[1] * e1 + (double)c[2] * e2;
-    y = (double)c[3] * e0 + (double)c[4] * e1 + (double)c[5] * e2;
-    z = (double)c[6] * e0 + (double)c[7] * e1 + (double)c[8] * e2;
+    const float *K = c + CAM_K, *R = c + CAM_R, *t = c + CAM_T;
+    const double e0 = (double)R[0] * X + (double)R[1] * Y + (double)R[2] * Z + (double)t[0];
+    const double e1 = (double)R[3] * X + (double)R[4] * Y + (double)R[5] * Z + (double)t[1];
+    const double e2 = (double)R[6] * X + (double)R[7] * Y + (double)R[8] * Z + (double)t[2];
+    x = (double)K[0] * e0 + (double)K[1] * e1 + (double)K[2] * e2;
+    y = (double)K[3] * e0 + (double)K[4] * e1 + (double)K[5] * e2;
+    z = (double)K[6] * e0 + (double)K[7] * e1 + (double)K[8] * e2;
 }
 __device__ __forceinline__ bool cf_depth_ok(float d) { return d > 0.0f && d <= 3.402823466e38f; }   // (false for NaN, inf)
 constexpr double CF_PIX_LIMIT = 1073741824.0;   // 2^30: a projection further out is no pixel of any view
@@ -220,9 +222,10 @@ __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
     const bool emit = seed && total >= a.min_pixels;
     // the lane's normal: R_m^T (1, 1, 1) / sqrt(3) rounded to fp32 (the constant normal maps of the reference's network path)
     constexpr double INV_SQRT3 = 0.57735026918962573;
-    const float nrm[3] = {(float)((double)cm[18] * INV_SQRT3 + (double)cm[21] * INV_SQRT3 + (double)cm[24] * INV_SQRT3),
-                          (float)((double)cm[19] * INV_SQRT3 + (double)cm[22] * INV_SQRT3 + (double)cm[25] * INV_SQRT3),
-                          (float)((double)cm[20] * INV_SQRT3 + (double)cm[23] * INV_SQRT3 + (double)cm[26] * INV_SQRT3)};
+    const float* Rm = cm + CAM_R;
+    const float nrm[3] = {(float)((double)Rm[0] * INV_SQRT3 + (double)Rm[3] * INV_SQRT3 + (double)Rm[6] * INV_SQRT3),
+                          (float)((double)Rm[1] * INV_SQRT3 + (double)Rm[4] * INV_SQRT3 + (double)Rm[7] * INV_SQRT3),
+                          (float)((double)Rm[2] * INV_SQRT3 + (double)Rm[5] * INV_SQRT3 + (double)Rm[8] * INV_SQRT3)};
     const bool any_emit = __ballot(emit) != 0ull;
     float med[3] = {0.0f, 0.0f, 0.0f}, mnr[3] = {0.0f, 0.0f, 0.0f};
     uint32_t mcol[3] = {0, 0, 0};
@@ -317,32 +320,6 @@ __global__ __launch_bounds__(CF_AUX_THREADS) void colmap_count_kernel(const uint
     if ((threadIdx.x & 63) == 0 && p < npix) seg_count[p >> 6] = __popcll(b);
 }
 
-// exclusive scan of seg_count in one workgroup (depth_fusion.hip's scan): offsets are counter + prefix; the counter advances
-__global__ __launch_bounds__(CF_SCAN_THREADS) void colmap_scan_kernel(const int* __restrict__ seg_count, long long* seg_off,
-                                                                      long long* counter, int nseg) {
-    __shared__ long long part[CF_SCAN_THREADS];
-    const int per = (nseg + CF_SCAN_THREADS - 1) / CF_SCAN_THREADS;
-    const int b = threadIdx.x * per, e = min(b + per, nseg);
-    long long s = 0;
-    for (int k = b; k < e; ++k) s += seg_count[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < CF_SCAN_THREADS; off <<= 1) {        // Hillis-Steele, inclusive
-        const long long v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const long long base = *counter;
-    long long run = base + part[threadIdx.x] - s;
-    for (int k = b; k < e; ++k) {
-        seg_off[k] = run;
-        run += seg_count[k];
-    }
-    __syncthreads();                                               // every lane has read the counter
-    if (threadIdx.x == CF_SCAN_THREADS - 1) *counter = base + part[threadIdx.x];
-}
-
 // one lane per pixel of view i: an emitting seed goes to out[offset[segment] + its rank among the segment's emitting seeds]
 __global__ __launch_bounds__(CF_AUX_THREADS) void colmap_scatter_kernel(const uint8_t* __restrict__ flag, const long long* __restrict__ seg_off,
                                                                         const float4* __restrict__ stage, long npix, int view,
@@ -367,7 +344,6 @@ __global__ __launch_bounds__(CF_AUX_THREADS) void colmap_scatter_kernel(const ui
 }  // namespace pscv
 
 namespace {
-long cf_up(long b) { return (b + 255) / 256 * 256; }
 long cf_nseg(long npix) { return (npix + 63) / 64; }
 }
 
@@ -375,7 +351,7 @@ extern "C" long pscv_colmap_fuse_workspace(int h, int w) {
     if (h <= 0 || w <= 0) return -1;
     const long npix = (long)h * w, nseg = cf_nseg(npix);
     // flags uint8, counts int32, offsets int64, staging 2 x float4 per pixel; each part 256-byte aligned
-    return cf_up(npix) + cf_up(nseg * 4) + cf_up(nseg * 8) + cf_up(npix * 32);
+    return pscv::align256(npix) + pscv::align256(nseg * 4) + pscv::align256(nseg * 8) + pscv::align256(npix * 32);
 }
 
 extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* depth, const unsigned int* const* color,
@@ -401,20 +377,12 @@ extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* dept
     PSCV_CHECK_ARG(capacity >= 0 && (capacity == 0 || (out_xyz && out_rgb)), "pscv_colmap_fuse_pass: bad output buffer (capacity %ld)",
                    capacity);
     CfArgs a;
+    if (fill_views(a, a.fused, "pscv_colmap_fuse_pass", n_views, depth, color, fused, hw)) return -1;
     for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
         const bool on = v < n_views;
-        a.depth[v] = on ? depth[v] : nullptr;
-        a.color[v] = on ? color[v] : nullptr;
-        a.fused[v] = on ? fused[v] : nullptr;
         a.claim[v] = on ? claim[v] : nullptr;
-        a.h[v] = on ? hw[2 * v] : 1;
-        a.w[v] = on ? hw[2 * v + 1] : 1;
         a.overlap[v] = on ? ((unsigned long long)overlap[v] & ~(1ull << v)) & (n_views == 64 ? ~0ull : ((1ull << n_views) - 1ull)) : 0ull;
-        if (on) {
-            PSCV_CHECK_ARG(depth[v] && color[v] && fused[v] && claim[v], "pscv_colmap_fuse_pass: view %d has a null pointer", v);
-            PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31),
-                           "pscv_colmap_fuse_pass: view %d has bad size %dx%d", v, a.h[v], a.w[v]);
-        }
+        PSCV_CHECK_ARG(!on || claim[v], "pscv_colmap_fuse_pass: view %d has a null pointer", v);
     }
     const long npix = (long)a.h[view] * a.w[view], nseg = cf_nseg(npix);
     PSCV_CHECK_ARG(workspace_bytes >= pscv_colmap_fuse_workspace(a.h[view], a.w[view]),
@@ -422,9 +390,9 @@ extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* dept
                    pscv_colmap_fuse_workspace(a.h[view], a.w[view]));
     char* ws = static_cast<char*>(workspace);
     a.flag = reinterpret_cast<uint8_t*>(ws);
-    int* seg_count = reinterpret_cast<int*>(ws + cf_up(npix));
-    long long* seg_off = reinterpret_cast<long long*>(ws + cf_up(npix) + cf_up(nseg * 4));
-    a.stage = reinterpret_cast<float4*>(ws + cf_up(npix) + cf_up(nseg * 4) + cf_up(nseg * 8));
+    int* seg_count = reinterpret_cast<int*>(ws + align256(npix));
+    long long* seg_off = reinterpret_cast<long long*>(ws + align256(npix) + align256(nseg * 4));
+    a.stage = reinterpret_cast<float4*>(ws + align256(npix) + align256(nseg * 4) + align256(nseg * 8));
     a.cams = cams;
     a.processed = processed;
     a.key = ((unsigned long long)(0xffffffffu - (unsigned)tag) << 32);   // an earlier (lower) tag has a larger key and loses every atomicMin
@@ -448,7 +416,8 @@ extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* dept
     const unsigned aux = (unsigned)((npix + CF_AUX_THREADS - 1) / CF_AUX_THREADS);
     hipLaunchKernelGGL(colmap_count_kernel, dim3(aux), dim3(CF_AUX_THREADS), 0, st, a.flag, npix, seg_count);
     PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (count)");
-    hipLaunchKernelGGL(colmap_scan_kernel, dim3(1), dim3(CF_SCAN_THREADS), 0, st, seg_count, seg_off, counter, (int)nseg);
+    hipLaunchKernelGGL((scan_kernel<CF_SCAN_THREADS, long long, true>), dim3(1), dim3(CF_SCAN_THREADS), 0, st, seg_count, seg_off, counter,
+                       (int)nseg);
     PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (scan)");
     hipLaunchKernelGGL(colmap_scatter_kernel, dim3(aux), dim3(CF_AUX_THREADS), 0, st, a.flag, seg_off, a.stage, npix, view,
                        (long long)capacity, out_xyz, out_normal, out_rgb, out_view, out_pixel);

@@ -16,7 +16,7 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): evaluation/fusibile.py:160-181, the external CUDA-only `fusibile` binary it runs
 // (normal test off: normal_thresh = 360 with fake_gipuma_normal's constant normals).
-#include "pscv_common.h"
+#include "geo_common.h"
 
 namespace pscv {
 
@@ -35,43 +35,17 @@ struct FuseArgs {
     float disp_thresh, depth_min, depth_max;
 };
 
-// M v (explicit fmaf: the marking loop recomputes a projection and must get the counting loop's bits)
-__device__ __forceinline__ void fu_mat_vec(const float* M, float x, float y, float z, float& ox, float& oy, float& oz) {
-    ox = fmaf(M[2], z, fmaf(M[1], y, M[0] * x));
-    oy = fmaf(M[5], z, fmaf(M[4], y, M[3] * x));
-    oz = fmaf(M[8], z, fmaf(M[7], y, M[6] * x));
-}
-// M^T v
-__device__ __forceinline__ void fu_matT_vec(const float* M, float x, float y, float z, float& ox, float& oy, float& oz) {
-    ox = fmaf(M[6], z, fmaf(M[3], y, M[0] * x));
-    oy = fmaf(M[7], z, fmaf(M[4], y, M[1] * x));
-    oz = fmaf(M[8], z, fmaf(M[5], y, M[2] * x));
-}
 __device__ __forceinline__ bool fu_valid(float d, float lo, float hi) { return d > lo && d < hi; }   // (false for NaN, +-inf)
 // K (R X + t) rounded to the nearest pixel of a view of size hj x wj: false when behind the camera or outside
 __device__ __forceinline__ bool fu_project(const float* cam, float X, float Y, float Z, int hj, int wj, float& z, int& qx, int& qy) {
-    const float* K = cam;
-    const float* R = cam + 18;
-    const float* t = cam + 27;
-    float cx, cy, cz, a, b;
-    fu_mat_vec(R, X, Y, Z, cx, cy, cz);
-    fu_mat_vec(K, cx + t[0], cy + t[1], cz + t[2], a, b, z);
+    float a, b;
+    cam_point(cam, X, Y, Z, a, b, z);
     if (!(z > 0.0f)) return false;
     const float fx = floorf(a / z + 0.5f), fy = floorf(b / z + 0.5f);
     if (!(fx >= 0.0f && fx < (float)wj && fy >= 0.0f && fy < (float)hj)) return false;
     qx = (int)fx; qy = (int)fy;
     return true;
 }
-// R^T (d K^-1 (x, y, 1) - t)
-__device__ __forceinline__ void fu_unproject(const float* cam, float x, float y, float d, float& X, float& Y, float& Z) {
-    const float* Ki = cam + 9;
-    const float* R = cam + 18;
-    const float* t = cam + 27;
-    float ax, ay, az;
-    fu_mat_vec(Ki, x * d, y * d, d, ax, ay, az);
-    fu_matT_vec(R, ax - t[0], ay - t[1], az - t[2], X, Y, Z);
-}
-
 __global__ __launch_bounds__(FUSE_THREADS) void fuse_depth_kernel(const FuseArgs a) {
     __shared__ float cam_lds[PSCV_FUSE_MAX_VIEWS * PSCV_GEO_CAM_FLOATS];
     __shared__ float fb_lds[PSCV_FUSE_MAX_VIEWS];       // f_i * |c_i - c_j|
@@ -82,10 +56,10 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_depth_kernel(const FuseArgs
     if (threadIdx.x < a.n) {
         const float* cj = cam_lds + threadIdx.x * PSCV_GEO_CAM_FLOATS;
         float xi, yi, zi, xj, yj, zj;                    // -c = R^T t
-        fu_matT_vec(ci + 18, ci[27], ci[28], ci[29], xi, yi, zi);
-        fu_matT_vec(cj + 18, cj[27], cj[28], cj[29], xj, yj, zj);
+        matT_vec(ci + CAM_R, ci[CAM_T], ci[CAM_T + 1], ci[CAM_T + 2], xi, yi, zi);
+        matT_vec(cj + CAM_R, cj[CAM_T], cj[CAM_T + 1], cj[CAM_T + 2], xj, yj, zj);
         const float dx = xi - xj, dy = yi - yj, dz = zi - zj;
-        fb_lds[threadIdx.x] = ci[0] * sqrtf(dx * dx + dy * dy + dz * dz);
+        fb_lds[threadIdx.x] = ci[CAM_K] * sqrtf(dx * dx + dy * dy + dz * dz);
     }
     __syncthreads();
 
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_depth_kernel(const FuseArgs
         const float d = a.depth[i][pix];
         if (fu_valid(d, a.depth_min, a.depth_max) && a.used[i][pix] == 0) {
             float X, Y, Z;
-            fu_unproject(ci, (float)x, (float)y, d, X, Y, Z);
+            cam_unproject(ci, (float)x, (float)y, d, X, Y, Z);
             float sx = 0.0f, sy = 0.0f, sz = 0.0f;
             uint32_t sr = 0, sg = 0, sb = 0;
             int n = 0;
@@ -119,7 +93,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_depth_kernel(const FuseArgs
                 const float fb = fb_lds[j];
                 if (!(fabsf(fb / z - fb / dj) < a.disp_thresh)) continue;
                 float Xj, Yj, Zj;
-                fu_unproject(cj, (float)qx, (float)qy, dj, Xj, Yj, Zj);
+                cam_unproject(cj, (float)qx, (float)qy, dj, Xj, Yj, Zj);
                 sx += Xj; sy += Yj; sz += Zj;
                 const uint32_t c = a.color[j][q];
                 sr += c & 0xffu; sg += (c >> 8) & 0xffu; sb += (c >> 16) & 0xffu;
@@ -160,32 +134,6 @@ __global__ __launch_bounds__(FUSE_THREADS) void fuse_depth_kernel(const FuseArgs
     }
 }
 
-// exclusive scan of seg_count in one workgroup; offsets are counter + prefix; the counter advances by the pass's total
-__global__ __launch_bounds__(FUSE_SCAN_THREADS) void fuse_scan_kernel(const int* __restrict__ seg_count, long long* seg_off,
-                                                                      long long* counter, int nseg) {
-    __shared__ long long part[FUSE_SCAN_THREADS];
-    const int per = (nseg + FUSE_SCAN_THREADS - 1) / FUSE_SCAN_THREADS;
-    const int b = threadIdx.x * per, e = min(b + per, nseg);
-    long long s = 0;
-    for (int k = b; k < e; ++k) s += seg_count[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < FUSE_SCAN_THREADS; off <<= 1) {       // Hillis-Steele, inclusive
-        const long long v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    const long long base = *counter;
-    long long run = base + part[threadIdx.x] - s;
-    for (int k = b; k < e; ++k) {
-        seg_off[k] = run;
-        run += seg_count[k];
-    }
-    __syncthreads();                                               // every lane has read the counter
-    if (threadIdx.x == FUSE_SCAN_THREADS - 1) *counter = base + part[threadIdx.x];
-}
-
 __global__ __launch_bounds__(256) void fuse_scatter_kernel(const int* __restrict__ seg_count, const long long* __restrict__ seg_off,
                                                            const float4* __restrict__ stage, long nslot, int view, int nsx, int w,
                                                            long long capacity, float* out_xyz, uint8_t* out_rgb, int* out_view,
@@ -219,8 +167,7 @@ extern "C" long pscv_fuse_depth_workspace(int h, int w) {
     if (h <= 0 || w <= 0) return -1;
     const long nseg = fuse_nseg(h, w);
     // counts int32, offsets int64, staging float4 per slot; each part 256-byte aligned
-    auto up = [](long b) { return (b + 255) / 256 * 256; };
-    return up(nseg * 4) + up(nseg * 8) + up(nseg * pscv::FUSE_TW * 16);
+    return pscv::align256(nseg * 4) + pscv::align256(nseg * 8) + pscv::align256(nseg * pscv::FUSE_TW * 16);
 }
 
 extern "C" int pscv_fuse_depth_pass(int pass, const float* const* depth, const unsigned int* const* color,
@@ -237,28 +184,15 @@ extern "C" int pscv_fuse_depth_pass(int pass, const float* const* depth, const u
                    capacity);
     PSCV_CHECK_ARG(num_consistent >= 0, "pscv_fuse_depth_pass: num_consistent=%d < 0", num_consistent);
     FuseArgs a;
-    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n_views;
-        a.depth[v] = on ? depth[v] : nullptr;
-        a.color[v] = on ? color[v] : nullptr;
-        a.used[v] = on ? used[v] : nullptr;
-        a.h[v] = on ? hw[2 * v] : 1;
-        a.w[v] = on ? hw[2 * v + 1] : 1;
-        if (on) {
-            PSCV_CHECK_ARG(depth[v] && color[v] && used[v], "pscv_fuse_depth_pass: view %d has a null pointer", v);
-            PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31),
-                           "pscv_fuse_depth_pass: view %d has bad size %dx%d", v, a.h[v], a.w[v]);
-        }
-    }
+    if (fill_views(a, a.used, "pscv_fuse_depth_pass", n_views, depth, color, used, hw)) return -1;
     const int h = a.h[pass], w = a.w[pass];
     const long nseg = fuse_nseg(h, w);
     PSCV_CHECK_ARG(workspace_bytes >= pscv_fuse_depth_workspace(h, w), "pscv_fuse_depth_pass: workspace of %ld bytes < %ld",
                    workspace_bytes, pscv_fuse_depth_workspace(h, w));
     char* ws = static_cast<char*>(workspace);
-    auto up = [](long b) { return (b + 255) / 256 * 256; };
     int* seg_count = reinterpret_cast<int*>(ws);
-    long long* seg_off = reinterpret_cast<long long*>(ws + up(nseg * 4));
-    float4* stage = reinterpret_cast<float4*>(ws + up(nseg * 4) + up(nseg * 8));
+    long long* seg_off = reinterpret_cast<long long*>(ws + align256(nseg * 4));
+    float4* stage = reinterpret_cast<float4*>(ws + align256(nseg * 4) + align256(nseg * 8));
     a.cams = cams;
     a.seg_count = seg_count;
     a.stage = stage;
@@ -268,7 +202,8 @@ extern "C" int pscv_fuse_depth_pass(int pass, const float* const* depth, const u
     hipLaunchKernelGGL(fuse_depth_kernel, dim3((unsigned)a.nsx, (unsigned)((h + FUSE_TH - 1) / FUSE_TH)), dim3(FUSE_THREADS), 0, s, a);
     PSCV_CHECK_LAUNCH("pscv_fuse_depth_pass (fuse)");
     PSCV_CHECK_ARG(nseg < (1L << 31), "pscv_fuse_depth_pass: %ld segments", nseg);
-    hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(FUSE_SCAN_THREADS), 0, s, seg_count, seg_off, counter, (int)nseg);
+    hipLaunchKernelGGL((scan_kernel<FUSE_SCAN_THREADS, long long, true>), dim3(1), dim3(FUSE_SCAN_THREADS), 0, s, seg_count, seg_off, counter,
+                       (int)nseg);
     PSCV_CHECK_LAUNCH("pscv_fuse_depth_pass (scan)");
     const long nslot = nseg * FUSE_TW;
     hipLaunchKernelGGL(fuse_scatter_kernel, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, s, seg_count, seg_off, stage, nslot,

@@ -1,0 +1,92 @@
+// Shared pieces of the evaluation kernels (geo_filter, depth_fusion, colmap_fusion, patch_match, point_metrics).  gfx950.
+#pragma once
+#include "pscv_common.h"
+
+namespace pscv {
+
+// ---- the camera block of ops.geo_filter_cams: PSCV_GEO_CAM_FLOATS floats, K, K^-1, R (row-major 3x3 each), t ----------------
+constexpr int CAM_K = 0, CAM_KINV = 9, CAM_R = 18, CAM_T = 27;
+
+// M v, accumulated k = 0, 1, 2 like a 3-wide GEMM row (explicit fmaf: callers that recompute a projection get the same bits)
+__device__ __forceinline__ void mat_vec(const float* M, float x, float y, float z, float& ox, float& oy, float& oz) {
+    ox = fmaf(M[2], z, fmaf(M[1], y, M[0] * x));
+    oy = fmaf(M[5], z, fmaf(M[4], y, M[3] * x));
+    oz = fmaf(M[8], z, fmaf(M[7], y, M[6] * x));
+}
+// M^T v
+__device__ __forceinline__ void matT_vec(const float* M, float x, float y, float z, float& ox, float& oy, float& oz) {
+    ox = fmaf(M[6], z, fmaf(M[3], y, M[0] * x));
+    oy = fmaf(M[7], z, fmaf(M[4], y, M[1] * x));
+    oz = fmaf(M[8], z, fmaf(M[5], y, M[2] * x));
+}
+// R^T (d K^-1 (x, y, 1) - t)
+__device__ __forceinline__ void cam_unproject(const float* cam, float x, float y, float d, float& X, float& Y, float& Z) {
+    const float* t = cam + CAM_T;
+    float ax, ay, az;
+    mat_vec(cam + CAM_KINV, x * d, y * d, d, ax, ay, az);
+    matT_vec(cam + CAM_R, ax - t[0], ay - t[1], az - t[2], X, Y, Z);
+}
+// K (R X + t): the homogeneous pixel (not divided by z)
+__device__ __forceinline__ void cam_point(const float* cam, float X, float Y, float Z, float& px, float& py, float& pz) {
+    const float* t = cam + CAM_T;
+    float cx, cy, cz;
+    mat_vec(cam + CAM_R, X, Y, Z, cx, cy, cz);
+    mat_vec(cam + CAM_K, cx + t[0], cy + t[1], cz + t[2], px, py, pz);
+}
+
+// ---- one-workgroup exclusive scan ------------------------------------------------------------------------------------------
+// (internal linkage: every translation unit keeps its own copy in its own code object)
+namespace {
+// off[k] = base + count[0] + ... + count[k-1]: with COUNTER, base = *counter and the counter then advances by the total;
+// without, base = 0 and counter is not used
+template <int THREADS, typename Off, bool COUNTER>
+__global__ __launch_bounds__(THREADS) void scan_kernel(const int* __restrict__ count, Off* off, long long* counter, int n) {
+    __shared__ long long part[THREADS];
+    const int per = (n + THREADS - 1) / THREADS;
+    const int b = threadIdx.x * per, e = min(b + per, n);
+    long long s = 0;
+    for (int k = b; k < e; ++k) s += count[k];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < THREADS; o <<= 1) {                       // Hillis-Steele, inclusive
+        const long long v = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    const long long base = COUNTER ? *counter : 0;
+    long long run = base + part[threadIdx.x] - s;
+    for (int k = b; k < e; ++k) {
+        off[k] = (Off)run;
+        run += count[k];
+    }
+    __syncthreads();                                               // every lane has read the counter
+    if (COUNTER && threadIdx.x == THREADS - 1) *counter = base + part[threadIdx.x];
+}
+}  // namespace
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+inline long align256(long bytes) { return (bytes + 255) / 256 * 256; }
+
+// The per-view table of a fusion pass (depth, color, h, w and the caller's mask array `amask`) for views [0, n); the entries past
+// n are null, 1 x 1.  Returns -1 with the error set when a view has a null pointer or a bad size.
+template <typename Args, typename Mask>
+int fill_views(Args& a, Mask* (&amask)[PSCV_FUSE_MAX_VIEWS], const char* what, int n, const float* const* depth,
+               const unsigned int* const* color, Mask* const* mask, const int* hw) {
+    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
+        const bool on = v < n;
+        a.depth[v] = on ? depth[v] : nullptr;
+        a.color[v] = on ? color[v] : nullptr;
+        amask[v] = on ? mask[v] : nullptr;
+        a.h[v] = on ? hw[2 * v] : 1;
+        a.w[v] = on ? hw[2 * v + 1] : 1;
+        if (on) {
+            PSCV_CHECK_ARG(depth[v] && color[v] && mask[v], "%s: view %d has a null pointer", what, v);
+            PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31), "%s: view %d has bad size %dx%d", what, v,
+                           a.h[v], a.w[v]);
+        }
+    }
+    return 0;
+}
+
+}  // namespace pscv

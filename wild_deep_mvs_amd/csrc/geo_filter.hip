@@ -9,7 +9,7 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): evaluation/filtering.py:60-83 with utils/utils_3D.py unproject :116-141,
 // project_all :64-74, normalize :243-272, unproj_all :144-160, project :96-113, compute_triangulation_angles :300-315.
-#include "pscv_common.h"
+#include "geo_common.h"
 
 namespace pscv {
 
@@ -26,19 +26,6 @@ struct GeoArgs {
     float max_reproj, depth_thr, min_tri;
 };
 
-// row-vector times matrix^T, i.e. M v, accumulated k = 0, 1, 2 like a 3-wide GEMM row
-__device__ __forceinline__ void mat_vec(const float* M, float x, float y, float z, float& ox, float& oy, float& oz) {
-    ox = fmaf(M[2], z, fmaf(M[1], y, M[0] * x));
-    oy = fmaf(M[5], z, fmaf(M[4], y, M[3] * x));
-    oz = fmaf(M[8], z, fmaf(M[7], y, M[6] * x));
-}
-// row-vector times matrix, i.e. M^T v
-__device__ __forceinline__ void matT_vec(const float* M, float x, float y, float z, float& ox, float& oy, float& oz) {
-    ox = fmaf(M[6], z, fmaf(M[3], y, M[0] * x));
-    oy = fmaf(M[7], z, fmaf(M[4], y, M[1] * x));
-    oz = fmaf(M[8], z, fmaf(M[5], y, M[2] * x));
-}
-
 __global__ __launch_bounds__(256) void geo_filter_kernel(const GeoArgs a) {
     __shared__ float cam_lds[(PSCV_GEO_MAX_SRC + 1) * PSCV_GEO_CAM_FLOATS];
     for (int i = threadIdx.x; i < (a.n_src + 1) * PSCV_GEO_CAM_FLOATS; i += 256) cam_lds[i] = a.cams[i];
@@ -49,30 +36,24 @@ __global__ __launch_bounds__(256) void geo_filter_kernel(const GeoArgs a) {
     const float xf = (float)x, yf = (float)y;
     const float d = a.depth[pix];
 
-    const float* K0 = cam_lds;
-    const float* Ki0 = cam_lds + 9;
-    const float* R0 = cam_lds + 18;
-    const float* t0 = cam_lds + 27;
+    const float* c0 = cam_lds;
+    const float* t0 = c0 + CAM_T;
     // X = R_0^T (K_0^-1 (x, y, 1) d - t_0)                                             utils_3D.py:116-141
-    float ax, ay, az, X, Y, Z;
-    mat_vec(Ki0, xf * d, yf * d, d, ax, ay, az);
-    matT_vec(R0, ax - t0[0], ay - t0[1], az - t0[2], X, Y, Z);
+    float X, Y, Z;
+    cam_unproject(c0, xf, yf, d, X, Y, Z);
     // reference ray: X - c_0, c_0 = -R_0^T t_0                                          utils_3D.py:308
     float c0x, c0y, c0z;
-    matT_vec(R0, t0[0], t0[1], t0[2], c0x, c0y, c0z);
+    matT_vec(c0 + CAM_R, t0[0], t0[1], t0[2], c0x, c0y, c0z);
     const float r1x = X + c0x, r1y = Y + c0y, r1z = Z + c0z;
     const float n1 = fmaxf(sqrtf(r1x * r1x + r1y * r1y + r1z * r1z), 1e-12f);
 
     int n_depth = 0, n_disp = 0, n_geo = 0;
     for (int i = 0; i < a.n_src; ++i) {
-        const float* K = cam_lds + (i + 1) * PSCV_GEO_CAM_FLOATS;
-        const float* Ki = K + 9;
-        const float* R = K + 18;
-        const float* t = K + 27;
+        const float* ci = cam_lds + (i + 1) * PSCV_GEO_CAM_FLOATS;
+        const float* t = ci + CAM_T;
         // p = K_i (R_i X + t_i)                                                         utils_3D.py:64-74
-        float cx, cy, cz, px, py, pz;
-        mat_vec(R, X, Y, Z, cx, cy, cz);
-        mat_vec(K, cx + t[0], cy + t[1], cz + t[2], px, py, pz);
+        float px, py, pz;
+        cam_point(ci, X, Y, Z, px, py, pz);
         const float zc = fmaxf(pz, 1e-6f);
         const float u = px / zc, v = py / zc;
         // normalize with (size - 1), sample with align_corners=False                   utils_3D.py:267-268, filtering.py:66-68
@@ -98,18 +79,16 @@ __global__ __launch_bounds__(256) void geo_filter_kernel(const GeoArgs a) {
             if (vx1 && vy1) dw = fmaf(sp[y1 * ws + x1], se, dw);
         }
         // X' = R_i^T (K_i^-1 (u, v, 1) d_i - t_i);  q = K_0 (R_0 X' + t_0)              utils_3D.py:144-160, 96-106
-        float bx, by, bz, Xr, Yr, Zr, ex, ey, ez, qx, qy, qz;
-        mat_vec(Ki, u * dw, v * dw, dw, bx, by, bz);
-        matT_vec(R, bx - t[0], by - t[1], bz - t[2], Xr, Yr, Zr);
-        mat_vec(R0, Xr, Yr, Zr, ex, ey, ez);
-        mat_vec(K0, ex + t0[0], ey + t0[1], ez + t0[2], qx, qy, qz);
+        float Xr, Yr, Zr, qx, qy, qz;
+        cam_unproject(ci, u, v, dw, Xr, Yr, Zr);
+        cam_point(c0, Xr, Yr, Zr, qx, qy, qz);
         const float zr = qz + 1e-6f;
         const float rx = qx / zr - xf, ry = qy / zr - yf;
         const bool disp_ok = sqrtf(rx * rx + ry * ry) < a.max_reproj;                                   // filtering.py:73-74
         const bool depth_ok = fabsf(zr - d) < fmaxf(zr, d) * a.depth_thr && zr > 0.0f && pz > 0.0f;     // filtering.py:76-77
         // triangulation angle between X - c_0 and X - c_i, degrees                      utils_3D.py:300-315
         float cix, ciy, ciz;
-        matT_vec(R, t[0], t[1], t[2], cix, ciy, ciz);
+        matT_vec(ci + CAM_R, t[0], t[1], t[2], cix, ciy, ciz);
         const float r2x = X + cix, r2y = Y + ciy, r2z = Z + ciz;
         const float n2 = fmaxf(sqrtf(r2x * r2x + r2y * r2y + r2z * r2z), 1e-12f);
         float cosv = (r1x * r2x + r1y * r2y + r1z * r2z) / n1 / n2;

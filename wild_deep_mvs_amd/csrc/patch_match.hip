@@ -17,7 +17,7 @@
 // centre samples stay in registers.  The window sums are fp64 (the taps are fp32): windows near the variance threshold cancel.  Source samples are bilinear gathers from the fp32 grey images through the caches.
 //
 // Randomness is a counter hash (lowbias32 chained over seed, view, pixel, iteration, colour, slot), reproduced bit for bit in numpy.
-#include "pscv_common.h"
+#include "geo_common.h"
 
 namespace pscv {
 
@@ -91,22 +91,24 @@ __device__ __forceinline__ void mat3mul(const float* a, const float* b, float* o
 __device__ void pm_source_block(const float* cams, int s, float* o) {
     const float* r = cams;
     const float* c = cams + (s + 1) * PSCV_GEO_CAM_FLOATS;
+    const float *rR = r + CAM_R, *rt = r + CAM_T, *cR = c + CAM_R, *ct = c + CAM_T;
     float Rr[9], RrT[9], tmp[9], RrtT[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)
-            Rr[3 * i + j] = c[18 + 3 * i] * r[18 + 3 * j] + c[18 + 3 * i + 1] * r[18 + 3 * j + 1] + c[18 + 3 * i + 2] * r[18 + 3 * j + 2];
+            Rr[3 * i + j] = cR[3 * i] * rR[3 * j] + cR[3 * i + 1] * rR[3 * j + 1] + cR[3 * i + 2] * rR[3 * j + 2];
     float tr[3], C[3];
-    for (int i = 0; i < 3; ++i) tr[i] = c[27 + i] - (Rr[3 * i] * r[27] + Rr[3 * i + 1] * r[28] + Rr[3 * i + 2] * r[29]);
+    for (int i = 0; i < 3; ++i) tr[i] = ct[i] - (Rr[3 * i] * rt[0] + Rr[3 * i + 1] * rt[1] + Rr[3 * i + 2] * rt[2]);
     for (int i = 0; i < 3; ++i) C[i] = -(Rr[i] * tr[0] + Rr[3 + i] * tr[1] + Rr[6 + i] * tr[2]);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) RrT[3 * i + j] = Rr[3 * j + i];
-    mat3mul(c + 0, Rr, tmp);                  // K_s R_rel
-    mat3mul(tmp, r + 9, o + 0);               // .. K_r^-1
-    for (int i = 0; i < 3; ++i) o[9 + i] = c[3 * i] * tr[0] + c[3 * i + 1] * tr[1] + c[3 * i + 2] * tr[2];
+    const float *rK = r + CAM_K, *cK = c + CAM_K;
+    mat3mul(cK, Rr, tmp);                     // K_s R_rel
+    mat3mul(tmp, r + CAM_KINV, o + 0);        // .. K_r^-1
+    for (int i = 0; i < 3; ++i) o[9 + i] = cK[3 * i] * tr[0] + cK[3 * i + 1] * tr[1] + cK[3 * i + 2] * tr[2];
     for (int i = 0; i < 3; ++i) o[12 + i] = C[i];
-    mat3mul(r + 0, RrT, RrtT);                // K_r R_rel^T
-    mat3mul(RrtT, c + 9, o + 15);             // .. K_s^-1
-    for (int i = 0; i < 3; ++i) o[24 + i] = r[3 * i] * C[0] + r[3 * i + 1] * C[1] + r[3 * i + 2] * C[2];
+    mat3mul(rK, RrT, RrtT);                   // K_r R_rel^T
+    mat3mul(RrtT, c + CAM_KINV, o + 15);      // .. K_s^-1
+    for (int i = 0; i < 3; ++i) o[24 + i] = rK[3 * i] * C[0] + rK[3 * i + 1] * C[1] + rK[3 * i + 2] * C[2];
     o[27] = 0.0f;
 }
 
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(PM_THREADS) void patch_match_kernel(const PmArgs a)
         tile[lr * PM_TILE_W + lc] = a.ref[(long)gr * a.w + gc];
     }
     if (tid < a.n_src) pm_source_block(a.cams, tid, geo + tid * PM_GEO);
-    if (tid < 9) kinv[tid] = a.cams[9 + tid];
+    if (tid < 9) kinv[tid] = a.cams[CAM_KINV + tid];
     __syncthreads();
 
     PmPixel px;
@@ -427,7 +429,7 @@ __global__ __launch_bounds__(PM_THREADS) void patch_match_init_kernel(const PmAr
     const long pix = (long)blockIdx.x * PM_THREADS + threadIdx.x;
     if (pix >= (long)a.h * a.w) return;
     const int row = (int)(pix / a.w), col = (int)(pix - (long)row * a.w);
-    const float* k = a.cams + 9;
+    const float* k = a.cams + CAM_KINV;
     float m[3];
     for (int i = 0; i < 3; ++i) m[i] = k[3 * i] * (float)col + k[3 * i + 1] * (float)row + k[3 * i + 2];
     a.state[pix] = pm_random(a, m, (uint32_t)pix, PM_INIT_ITERATION, 0u);

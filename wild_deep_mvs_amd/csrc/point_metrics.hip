@@ -20,7 +20,7 @@
 // This file is compiled with -ffp-contract=off: the DTU cell bounds must be the reference's fp64 sums, not fused products.
 //
 // Replaces (fdarmon/wild_deep_mvs): evaluation/metrics.py reduce_pts, chamfer, chamfer_imw (scipy cKDTree).
-#include "pscv_common.h"
+#include "geo_common.h"
 
 namespace pscv {
 
@@ -119,30 +119,6 @@ __global__ __launch_bounds__(PM_THREADS) void pm_chunk_sum_kernel(const T* __res
     }
     s = pm_block_sum(s, lds);
     if (threadIdx.x == 0) bsum[blockIdx.x] = s;
-}
-
-// exclusive scan of the chunk sums in one workgroup (depth_fusion.hip's pattern); the total goes to *total when given
-__global__ __launch_bounds__(PM_SCAN1_THREADS) void pm_scan_chunks_kernel(const int* __restrict__ bsum, int* __restrict__ boff, int nb,
-                                                                          long long* total) {
-    __shared__ long long part[PM_SCAN1_THREADS];
-    const int per = (nb + PM_SCAN1_THREADS - 1) / PM_SCAN1_THREADS;
-    const int b = threadIdx.x * per, e = min(b + per, nb);
-    long long s = 0;
-    for (int k = b; k < e; ++k) s += bsum[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < PM_SCAN1_THREADS; off <<= 1) {
-        const long long v = threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    long long run = part[threadIdx.x] - s;
-    for (int k = b; k < e; ++k) {
-        boff[k] = (int)run;
-        run += bsum[k];
-    }
-    if (total && threadIdx.x == PM_SCAN1_THREADS - 1) *total = part[threadIdx.x];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -391,7 +367,6 @@ struct GridLayout {
     long cap, nb;
     long hdr, keys, counts, cells, slot_of, pos, pts, payload, bsum, boff, total;
 };
-inline long pm_up(long b) { return (b + 255) / 256 * 256; }
 inline GridLayout grid_layout(long n) {
     GridLayout L;
     L.cap = 1024;
@@ -399,15 +374,15 @@ inline GridLayout grid_layout(long n) {
     L.nb = (L.cap + PM_CHUNK - 1) / PM_CHUNK;
     long o = 0;
     L.hdr = o; o += 256;
-    L.keys = o; o += pm_up(L.cap * 8);
-    L.counts = o; o += pm_up(L.cap * 4);
-    L.cells = o; o += pm_up(L.cap * 8);
-    L.slot_of = o; o += pm_up(n * 4);
-    L.pos = o; o += pm_up(n * 4);
-    L.pts = o; o += pm_up(n * 16);
-    L.payload = o; o += pm_up(n * 4);
-    L.bsum = o; o += pm_up(L.nb * 4);
-    L.boff = o; o += pm_up(L.nb * 4);
+    L.keys = o; o += align256(L.cap * 8);
+    L.counts = o; o += align256(L.cap * 4);
+    L.cells = o; o += align256(L.cap * 8);
+    L.slot_of = o; o += align256(n * 4);
+    L.pos = o; o += align256(n * 4);
+    L.pts = o; o += align256(n * 16);
+    L.payload = o; o += align256(n * 4);
+    L.bsum = o; o += align256(L.nb * 4);
+    L.boff = o; o += align256(L.nb * 4);
     L.total = o;
     return L;
 }
@@ -460,7 +435,8 @@ extern "C" int pscv_point_grid_build(const float* pts, long n, double ox, double
     }
     hipLaunchKernelGGL(pm_chunk_sum_kernel<int>, dim3((unsigned)L.nb), dim3(PM_THREADS), 0, s, counts, L.cap, bsum);
     PSCV_CHECK_LAUNCH("pscv_point_grid_build (chunk sums)");
-    hipLaunchKernelGGL(pm_scan_chunks_kernel, dim3(1), dim3(PM_SCAN1_THREADS), 0, s, bsum, boff, (int)L.nb, (long long*)nullptr);
+    hipLaunchKernelGGL((scan_kernel<PM_SCAN1_THREADS, int, false>), dim3(1), dim3(PM_SCAN1_THREADS), 0, s, bsum, boff, nullptr,
+                       (int)L.nb);
     PSCV_CHECK_LAUNCH("pscv_point_grid_build (scan)");
     hipLaunchKernelGGL(pm_cells_kernel, dim3((unsigned)L.nb), dim3(PM_THREADS), 0, s, counts, L.cap, boff, cells);
     PSCV_CHECK_LAUNCH("pscv_point_grid_build (cells)");
@@ -541,7 +517,7 @@ extern "C" int pscv_radius_mis_round(const void* grid, long n, double ox, double
 
 extern "C" long pscv_radius_mis_workspace(long n) {
     if (n < 0 || n >= pscv::PM_MAX_POINTS) return -1;
-    return 2 * pscv::pm_up(pscv::mis_nb(n) * 4) + 256;
+    return 2 * pscv::align256(pscv::mis_nb(n) * 4) + 256;
 }
 
 extern "C" int pscv_radius_mis_compact(const void* grid, long n, const unsigned char* state, unsigned char* mask, int* kept,
@@ -552,20 +528,19 @@ extern "C" int pscv_radius_mis_compact(const void* grid, long n, const unsigned 
     PSCV_CHECK_ARG(workspace_bytes >= pscv_radius_mis_workspace(n), "pscv_radius_mis_compact: workspace of %ld bytes < %ld",
                    workspace_bytes, pscv_radius_mis_workspace(n));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (n == 0) {
-        PSCV_CHECK_ARG(hipMemsetAsync(n_kept, 0, sizeof(long long), s) == hipSuccess, "pscv_radius_mis_compact: memset failed");
-        return 0;
-    }
+    // the scan adds the kept count to *n_kept
+    PSCV_CHECK_ARG(hipMemsetAsync(n_kept, 0, sizeof(long long), s) == hipSuccess, "pscv_radius_mis_compact: memset failed");
+    if (n == 0) return 0;
     const long nb = mis_nb(n);
     int* bsum = static_cast<int*>(workspace);
-    int* boff = reinterpret_cast<int*>(static_cast<char*>(workspace) + pm_up(nb * 4));
+    int* boff = reinterpret_cast<int*>(static_cast<char*>(workspace) + align256(nb * 4));
     const GridLayout L = grid_layout(n);
     hipLaunchKernelGGL(pm_mis_mask_kernel, dim3(pm_blocks(n)), dim3(PM_THREADS), 0, s,
                        reinterpret_cast<const float4*>(static_cast<const char*>(grid) + L.pts), n, state, mask);
     PSCV_CHECK_LAUNCH("pscv_radius_mis_compact (mask)");
     hipLaunchKernelGGL(pm_chunk_sum_kernel<unsigned char>, dim3((unsigned)nb), dim3(PM_THREADS), 0, s, mask, n, bsum);
     PSCV_CHECK_LAUNCH("pscv_radius_mis_compact (chunk sums)");
-    hipLaunchKernelGGL(pm_scan_chunks_kernel, dim3(1), dim3(PM_SCAN1_THREADS), 0, s, bsum, boff, (int)nb, n_kept);
+    hipLaunchKernelGGL((scan_kernel<PM_SCAN1_THREADS, int, true>), dim3(1), dim3(PM_SCAN1_THREADS), 0, s, bsum, boff, n_kept, (int)nb);
     PSCV_CHECK_LAUNCH("pscv_radius_mis_compact (scan)");
     hipLaunchKernelGGL(pm_compact_kernel, dim3((unsigned)nb), dim3(PM_THREADS), 0, s, mask, n, boff, kept);
     PSCV_CHECK_LAUNCH("pscv_radius_mis_compact (compact)");

@@ -437,24 +437,40 @@ def geo_filter_cams(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor) -> torch.
     return blocks.contiguous()
 
 
+def _maps(maps, what):
+    """fp32 [h,w] device maps -> (the list, c_void_p array of their addresses, c_int array of their (h, w) pairs)."""
+    maps = list(maps)
+    _dev(*maps)
+    for m in maps:
+        if m.dtype != torch.float32 or m.dim() != 2:
+            raise ValueError(f"{what}: fp32 [h,w] maps expected, got {m.dtype} {tuple(m.shape)}")
+    return maps, (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps]), (C.c_int * (2 * len(maps)))(*[v for m in maps for v in m.shape])
+
+
+def _check_cams(cams, rows, what):
+    """cams: fp32 camera blocks [rows, GEO_CAM_FLOATS] (``geo_filter_cams``); rows None accepts any number."""
+    if cams.dtype != torch.float32 or cams.dim() != 2 or cams.shape[1] != L.GEO_CAM_FLOATS or (rows is not None and cams.shape[0] != rows):
+        raise ValueError(f"{what}: fp32 cams [{'V' if rows is None else rows},{L.GEO_CAM_FLOATS}] expected (geo_filter_cams), "
+                         f"got {cams.dtype} {tuple(cams.shape)}")
+
+
 def geo_filter(depth: torch.Tensor, src_depth: Sequence[torch.Tensor], cams: torch.Tensor, *, max_reproj_error: float = 1.0,
                depth_threshold: float = 0.01, min_tri_angle: float = 1.0, num_consistent: int = 3,
                want_counts: bool = False):
     """depth [h,w] fp32, src_depth N x [h_i,w_i] fp32, cams [N+1,30] (``geo_filter_cams``), all on the GPU ->
     (mask_depth, mask_disp, geo_mask) bool [h,w] (and int32 counts [3,h,w] with ``want_counts``): the masks of
     evaluation/filtering.py:73-83 in one launch (pscv_geo_filter)."""
-    src_depth = [s.to(torch.float32).contiguous() for s in src_depth]
     depth = depth.to(torch.float32).contiguous()
     cams = cams.to(torch.float32).contiguous()
-    _dev(depth, cams, *src_depth)
+    _dev(depth, cams)
+    src_depth, ptrs, hw = _maps([s.to(torch.float32).contiguous() for s in src_depth], "pscv.geo_filter")
     n = len(src_depth)
-    if n < 1 or n > L.GEO_MAX_SRC or tuple(cams.shape) != (n + 1, L.GEO_CAM_FLOATS) or depth.dim() != 2:
-        raise ValueError(f"pscv.geo_filter: depth [h,w], 1..{L.GEO_MAX_SRC} source maps and cams [N+1,{L.GEO_CAM_FLOATS}] expected")
+    if n < 1 or n > L.GEO_MAX_SRC or depth.dim() != 2:
+        raise ValueError(f"pscv.geo_filter: depth [h,w] and 1..{L.GEO_MAX_SRC} source maps expected")
+    _check_cams(cams, n + 1, "pscv.geo_filter")
     h, w = depth.shape
     masks = torch.empty((3, h, w), dtype=torch.uint8, device=depth.device)
     counts = torch.empty((3, h, w), dtype=torch.int32, device=depth.device) if want_counts else None
-    ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in src_depth])
-    hw = (C.c_int * (2 * n))(*[v for s in src_depth for v in s.shape])
     rc = _launch("geo_filter", lambda: L.lib().pscv_geo_filter(
         _p(depth), ptrs, hw, n, _p(cams), h, w, float(max_reproj_error), float(depth_threshold), float(min_tri_angle),
         int(num_consistent), _p(masks[0]), _p(masks[1]), _p(masks[2]), _p(counts), _stream()))
@@ -480,13 +496,11 @@ def _fuse_inputs(depths, colors, cams):
     if n < 2 or n > L.FUSE_MAX_VIEWS or len(colors) != n:
         raise ValueError(f"pscv.fuse_depth: 2..{L.FUSE_MAX_VIEWS} depth maps and as many colour images expected, got {n} and {len(colors)}")
     cams = cams.to(torch.float32).contiguous()
-    _dev(cams, *depths)
-    if tuple(cams.shape) != (n, L.GEO_CAM_FLOATS):
-        raise ValueError(f"pscv.fuse_depth: cams [N,{L.GEO_CAM_FLOATS}] expected (geo_filter_cams), got {tuple(cams.shape)}")
+    _dev(cams)
+    depths, dptr, hw = _maps(depths, "pscv.fuse_depth")
+    _check_cams(cams, n, "pscv.fuse_depth")
     packed = []
     for v, (d, c) in enumerate(zip(depths, colors)):
-        if d.dim() != 2:
-            raise ValueError(f"pscv.fuse_depth: depth map {v} must be [h,w]")
         _dev(c)
         if c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
             packed.append(c.contiguous())
@@ -494,10 +508,9 @@ def _fuse_inputs(depths, colors, cams):
             packed.append(pack_rgba8(c))
         else:
             raise ValueError(f"pscv.fuse_depth: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
-    hw = (C.c_int * (2 * n))(*[v for d in depths for v in d.shape])
     ws_bytes = max(int(L.lib().pscv_fuse_depth_workspace(int(d.shape[0]), int(d.shape[1]))) for d in depths)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=depths[0].device)
-    ptrs = ((C.c_void_p * n)(*[d.data_ptr() for d in depths]), (C.c_void_p * n)(*[c.data_ptr() for c in packed]), hw)
+    ptrs = (dptr, (C.c_void_p * n)(*[c.data_ptr() for c in packed]), hw)
     return depths, packed, cams, ptrs, ws
 
 
@@ -669,11 +682,8 @@ class _ColmapRun:
         ws_bytes = max(int(L.lib().pscv_colmap_fuse_workspace(int(d.shape[0]), int(d.shape[1]))) for d in self.depths)
         self.ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.cap = sum(int(d.numel()) for d in self.depths) if capacity is None else int(capacity)
-        self.xyz = torch.empty((self.cap, 3), dtype=torch.float32, device=dev)
+        self.xyz, self.rgb, self.view, self.pixel = _fuse_out(self.cap, dev)
         self.normal = torch.empty((self.cap, 3), dtype=torch.float32, device=dev)
-        self.rgb = torch.empty((self.cap, 3), dtype=torch.uint8, device=dev)
-        self.view = torch.empty((self.cap,), dtype=torch.int32, device=dev)
-        self.pixel = torch.empty((self.cap,), dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
 
     def run_pass(self, view: int, tag: int, processed: int):
@@ -775,31 +785,23 @@ class _PmInputs:
             dmin, dmax = (float(np.float32(x)) for x in depth_range)
             if not 0.0 < dmin < dmax or not math.isfinite(dmax):
                 raise ValueError(f"{what}: need 0 < depth_min < depth_max, got {depth_range}")
-        _dev(ref, cams, *srcs)
-        for t in [ref, cams] + srcs:
-            if t.dtype != torch.float32:
-                raise ValueError(f"{what}: fp32 images and cameras expected, got {t.dtype}")
-        if ref.dim() != 2 or any(s.dim() != 2 for s in srcs):
-            raise ValueError(f"{what}: grey images must be [h,w]")
-        if tuple(cams.shape) != (S + 1, L.GEO_CAM_FLOATS):
-            raise ValueError(f"{what}: cams [S+1,{L.GEO_CAM_FLOATS}] expected (geo_filter_cams, reference first), got {tuple(cams.shape)}")
+        _dev(ref, cams)
+        srcs, self.sptr, self.hw = _maps(srcs, what)
+        if ref.dtype != torch.float32 or ref.dim() != 2:
+            raise ValueError(f"{what}: the reference must be a fp32 [h,w] grey image, got {ref.dtype} {tuple(ref.shape)}")
+        _check_cams(cams, S + 1, what)
         self.ref, self.srcs, self.cams = ref, srcs, cams
         self.h, self.w = ref.shape
         self.S, self.radius, self.step, self.top_k = S, int(radius), int(step), top_k
-        self.sptr = (C.c_void_p * S)(*[s.data_ptr() for s in srcs])
-        self.hw = (C.c_int * (2 * S))(*[v for s in srcs for v in s.shape])
         self.dptr = None
         self.src_depths = None
         if src_depths is not None:
             src_depths = list(src_depths)
             if len(src_depths) != S:
                 raise ValueError(f"{what}: {S} source depth maps expected, got {len(src_depths)}")
-            _dev(*src_depths)
-            for s, d in zip(srcs, src_depths):
-                if d.dtype != torch.float32 or tuple(d.shape) != tuple(s.shape):
-                    raise ValueError(f"{what}: source depth maps must be fp32 of their image's size")
-            self.src_depths = src_depths
-            self.dptr = (C.c_void_p * S)(*[d.data_ptr() for d in src_depths])
+            self.src_depths, self.dptr, _ = _maps(src_depths, what)
+            if any(d.shape != s.shape for s, d in zip(srcs, src_depths)):
+                raise ValueError(f"{what}: source depth maps must be fp32 of their image's size")
 
     def check_state(self, state, what):
         _dev(state)
@@ -816,8 +818,7 @@ def patch_match_init(h: int, w: int, cams: torch.Tensor, depth_min: float, depth
     if not 0.0 < float(np.float32(depth_min)) < float(np.float32(depth_max)):
         raise ValueError(f"pscv.patch_match_init: need 0 < depth_min < depth_max, got {depth_min}, {depth_max}")
     _dev(cams)
-    if cams.dtype != torch.float32 or cams.dim() != 2 or cams.shape[1] != L.GEO_CAM_FLOATS:
-        raise ValueError("pscv.patch_match_init: cams [V,30] fp32 expected")
+    _check_cams(cams, None, "pscv.patch_match_init")
     state = torch.empty((int(h), int(w), 4), dtype=torch.float32, device=cams.device)
     rc = _launch("patch_match_init", lambda: L.lib().pscv_patch_match_init(_p(state), int(h), int(w), _p(cams), float(depth_min),
                                                                           float(depth_max), _u32(seed), _u32(view), _stream()))
@@ -1037,7 +1038,7 @@ def radius_downsample(pts: torch.Tensor, dst: float, rank: torch.Tensor, *, chec
     final = state[launched % 2]
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
     kept = torch.empty(n, dtype=torch.int32, device=dev)
-    n_kept = torch.zeros(1, dtype=torch.int64, device=dev)
+    n_kept = torch.empty(1, dtype=torch.int64, device=dev)
     ws_bytes = int(L.lib().pscv_radius_mis_workspace(n))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     rc = _launch("radius_mis_compact", lambda: L.lib().pscv_radius_mis_compact(
