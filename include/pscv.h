@@ -75,7 +75,8 @@ int pscv_abi_version(void);
 
 /* Tuning knobs for measurement runs (not part of the reference's surface).  A knob holds ONE process-wide value (a relaxed
  * atomic; every launching host thread reads it, including PyTorch's autograd thread and DataParallel's replica threads) and an
- * optional per-thread override (pscv_set_tuning_thread).  Kernel selection never depends on anything else that is mutable.  Keys:
+ * optional per-thread override (pscv_set_tuning_thread).  Kernel selection never depends on anything else that is mutable.
+ * The knobs themselves (key, symbol, default) are the PSCV_KNOB_TABLE of csrc/pscv_common.h; every key of it has ONE entry here.  Keys:
  *   "warp_q2"   1 (default): 32-channel 16-bit sweeps run on the quad-mapped kernel (one texel per lane quad, two depth
  *               planes per quad); 0: always the generic kernel.  "warp_lpv" != 0 also selects the generic kernel.
  *   "warp_lpv"  lanes sharing one voxel in the generic pscv_warp_cost kernel (1, 2 or 4 for C=32; 0 = default)
@@ -100,18 +101,25 @@ int pscv_abi_version(void);
  *   "sweep_dc"  depth planes per workgroup of the depth-sweep convs (0 = default heuristic)
  *   "sweepc_slots" resident-workgroup target that sizes the depth chunks of the 8|16 -> 8 depth-sweep conv (0 = 768)
  *   "sweepc_pd" prefetch distance in iterations (1..3) of the same kernel (0 = 1)
- *   "sweep_th16" 1: the 32->8 depth-sweep conv uses 16-row tiles / 512 threads; 0 (default): 8-row tiles / 256 threads
+ *   "sweep_th16" 1: the 32->8 depth-sweep conv uses 16-row tiles / 512 threads; 0 (default): 8-row tiles / 256 threads (measured 116 us
+ *               against 107 us at the headline size: one workgroup per CU hides less latency)
  *   "sweep_kdm" 1: the 32->8 depth-sweep conv runs the kd-in-rows formulation (32x32x16 MFMAs whose rows hold the three depth
  *               taps; one input plane per iteration, 3-slot ring, three workgroups per CU) with depth chunks sized for 768 resident
  *               workgroups; 2: sized for 1024; 0 (default): the plane-pair kernel.  Same products, another fp32 summation order
- *               (1e-4 apart before the 16-bit store).  "sweep_kdm_pd": planes in flight per workgroup of that kernel, 1 (default) | 2
+ *               (1e-4 apart before the 16-bit store).
+ *   "sweep_kdm_pd"  planes in flight per workgroup of the kd-in-rows kernel: 2, or 1 (0 = default = 1)
  *   "warp_bwd_direct" 1: pscv_warp_cost_bwd issues one global float atomic per tap; 0 (default): accumulates per-workgroup
  *               LDS patches and flushes them coalesced
  *   "c1_sweep"  1 (default): 1-channel heads with 8 input channels and at least three 6-plane blocks per depth chunk run the
  *               depth-sweep variant; 0: always the brick variant; 2: the sweep at any depth
+ *   "c1_nb"     6-plane blocks per workgroup of the 1-channel heads (0 = default: 1 or 2 for the brick variant, one resident round of
+ *               workgroups for the depth sweep; values above 2 reach the depth sweep only)
  *   "conv_s2_sweep"  1 (default): stride-2 layers with 8 input channels and <= 32 output channels on volumes of >= 64 Ki output
  *               voxels run the stride-2 depth-sweep kernel; 0: always the brick kernel; 2: the sweep at any size (same packed weights, same result up to
- *               fp32 summation order).  "s2s_slots": resident-workgroup target that sizes its depth chunks (0 = 768)
+ *               fp32 summation order)
+ *   "s2s_slots"  resident-workgroup target that sizes the depth chunks of the stride-2 depth-sweep kernel (0 = 768)
+ *   "block8_slots"  low 16 bits: resident-workgroup target that sizes the depth chunks of pscv_conv3d_block8 (0 = 768); the bits
+ *               above them are debug flags of that kernel (0 in any normal run)
  *   "conv2d_wlds"  1 (default): 64-channel k3 s1 2-D layers with 32 | 64 output channels and >= 512 tiles run the persistent
  *               kernel that keeps the layer's packed weights in LDS; 0: always conv2d_kernel; 2: at any size (same bits)
  *   "conv_wide"  1 (default): stride-1 3-D layers with 64 input and 32 | 64 output channels on volumes of >= 512 tiles (4 x 4 x 16
@@ -121,7 +129,13 @@ int pscv_abi_version(void);
  *               0: 4 x 4 x 16; 2: at any size
  *   "tail_nbk"  6-plane blocks per depth chunk of pscv_tail_sweep (0 = default: one resident round of workgroups)
  *   "conv_small_tiles"  1 (default): small volumes use 1x4x16 tiles with the output channels split over
- *               blockIdx.y; 0: always the large-tile variant */
+ *               blockIdx.y; 0: always the large-tile variant
+ *   "conv_small_nt"  1 | 2 | 4: 16-channel output tiles per workgroup of the small-volume and stride-2 variants (0 = default choice)
+ *   "softargmin_small"  1 (default): pscv_softargmin on depth axes of <= 32 planes (fp32 logits, no probability or partial outputs)
+ *               runs the one-thread-per-pixel kernel; 0: always the slice kernel
+ *   "fuse_c0"   ablation bits for builds made with -DPSCV_ABLATE (measurement only: the conv depth sweep, the weight gradient and
+ *               the warp backward each skip a part of their work per bit, and results are wrong with any bit set); no effect on a
+ *               normal build */
 int pscv_set_tuning(const char* key, int value);
 
 /* The same knobs for the CALLING host thread only (enable = 1: this thread reads `value` instead of the process-wide one;

@@ -53,10 +53,9 @@ def main():
         layer = ops.Conv3dLayer.build(wt, kind=L.CONV_S1, device=dev, relu=True, dtype=dt)
         out = torch.empty(1, D, h, w, 8, dtype=dt, device=dev)
         for dc in (8, 12, 16, 24, 32, 48, 64, 96):
-            L.set_tuning("sweep_dc", dc)
-            us = timeit(lambda: ops.conv3d(x, layer, out=out), args.reps)
+            with L.tuning(sweep_dc=dc):
+                us = timeit(lambda: ops.conv3d(x, layer, out=out), args.reps)
             print(f"conv0 sweep dc={dc:3d}: {us:8.1f} us")
-        L.set_tuning("sweep_dc", 0)
         return
     if args.only == "cvp":
         # the 64-channel layers of CVP-MVSNet (config 4): FeaturePyramid 64 -> 64 at 5 x 1024 x 1280 and the refinement U-Net's
@@ -84,13 +83,11 @@ def main():
                 layer = ops.Conv3dLayer.build(wt, kind=L.CONV_S1, device=dev, relu=True, dtype=dt)
                 ops.SWEEP16 = False
                 for pd in (1, 2, 3):
-                    L.set_tuning("sweepc_pd", pd)
                     row = []
                     for slots in (512, 768, 1024, 2048):
-                        L.set_tuning("sweepc_slots", slots)
-                        row.append(f"{slots}: {timeit(lambda: ops.conv3d(x, layer, out=out), args.reps):6.1f}")
+                        with L.tuning(sweepc_pd=pd, sweepc_slots=slots):
+                            row.append(f"{slots}: {timeit(lambda: ops.conv3d(x, layer, out=out), args.reps):6.1f}")
                     print(f"    prefetch distance {pd}  " + "  ".join(row))
-                L.set_tuning("sweepc_pd", 0); L.set_tuning("sweepc_slots", 0)
         t2 = timeit(lambda: ops.conv2d(x2, l2), args.reps)
         t3 = timeit(lambda: ops.conv3d(x3, l3), args.reps)
         f2 = 5 * 1024 * 1280 * 64 * 64 * 9 * 2 / 1e12
@@ -120,14 +117,11 @@ def main():
                 if True:
                     layer = ops.Conv3dLayer.build(wt, kind=L.CONV_S1, device=dev, relu_post=True, dtype=dt)
                     for pd in ((1, 2, 3) if args.reps > 20 else ()):
-                        L.set_tuning("sweepc_pd", pd)
                         row = []
                         for slots in (512, 768, 1024, 2048):
-                            L.set_tuning("sweepc_slots", slots)
-                            row.append(f"{slots}: {timeit(lambda: ops.conv3d(x, layer, skip=sk, out=out), args.reps):6.1f}")
+                            with L.tuning(sweepc_pd=pd, sweepc_slots=slots):
+                                row.append(f"{slots}: {timeit(lambda: ops.conv3d(x, layer, skip=sk, out=out), args.reps):6.1f}")
                         print(f"    prefetch distance {pd}, us by resident-workgroup target  " + "  ".join(row))
-                    L.set_tuning("sweepc_slots", 0)
-                    L.set_tuning("sweepc_pd", 0)
         return
     for name, ci, co, kind, s, skip in layers:
         if args.only and args.only not in name:
@@ -160,16 +154,14 @@ def main():
         out = torch.empty(1, D, h, w, 32, dtype=dt, device=dev)
         nbytes = 5 * 32 * h * w * 2 + out.numel() * 2
         for ppd in (16,):
-            L.set_tuning("warp_lpv", 0); L.set_tuning("warp_tiled", 1); L.set_tuning("warp_ppd", ppd)
-            us = timeit(lambda: ops.warp_cost(fcl[0], fcl[1:], cm, dv, cost=L.COST_VARIANCE, out=out), args.reps)
+            with L.tuning(warp_lpv=0, warp_tiled=1, warp_ppd=ppd):
+                us = timeit(lambda: ops.warp_cost(fcl[0], fcl[1:], cm, dv, cost=L.COST_VARIANCE, out=out), args.reps)
             rows.append((f"warp_cost variance TILED ppd={ppd}", us, nbytes / us / 1e3, 0))
-            L.set_tuning("warp_tiled", -1)
         for lpv in (4, 2, 1):
             for ppd in (4, 8, 16):
-                L.set_tuning("warp_lpv", lpv); L.set_tuning("warp_ppd", ppd)
-                us = timeit(lambda: ops.warp_cost(fcl[0], fcl[1:], cm, dv, cost=L.COST_VARIANCE, out=out), args.reps)
+                with L.tuning(warp_lpv=lpv, warp_ppd=ppd):
+                    us = timeit(lambda: ops.warp_cost(fcl[0], fcl[1:], cm, dv, cost=L.COST_VARIANCE, out=out), args.reps)
                 rows.append((f"warp_cost variance lpv={lpv} ppd={ppd}", us, nbytes / us / 1e3, 0))
-        L.set_tuning("warp_lpv", 0); L.set_tuning("warp_ppd", 0)
     # ---- softargmin ----
     if not args.only or "soft" in args.only:
         logits = torch.randn(1, D, h, w, generator=g).to(dev)

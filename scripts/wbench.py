@@ -60,9 +60,8 @@ def main():
         for ppd in args.ppd:
             for variant in (args.variants if tiled else [0]):
                 out = torch.empty(1, D, h, w, 32, dtype=dt, device=dev)
-                L.set_tuning("warp_tiled", tiled); L.set_tuning("warp_ppd", ppd); L.set_tuning("warp_tile", variant)
                 hist = torch.zeros(16, dtype=torch.int32, device=dev)
-                try:
+                with L.tuning(warp_tiled=tiled, warp_ppd=ppd, warp_tile=variant):
                     if tiled:
                         import ctypes
                         fn = L.lib().pscv_debug_wl_mode_hist
@@ -73,8 +72,6 @@ def main():
                         fn(None)
                         print("   staging modes per view [DIRECT, GEN, FAST, ZERO]:", hist.view(4, 4).tolist())
                     us = timeit(lambda: ops.warp_cost(fcl[0], fcl[1:], cm, dv, cost=L.COST_VARIANCE, out=out), args.reps)
-                finally:
-                    L.set_tuning("warp_tiled", -1); L.set_tuning("warp_ppd", 0); L.set_tuning("warp_tile", 0)
                 if tiled and variant != args.variants[0]:
                     ne = (outs[name].view(torch.int16) != out.view(torch.int16)).sum().item()
                     print(f"   variant {variant} vs {args.variants[0]}: {ne} stored values differ")

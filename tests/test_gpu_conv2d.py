@@ -57,7 +57,6 @@ def test_conv2d_leaky_relu_layers_of_the_cvp_pyramid(env, ci, co, wlds):
     their kernels: weight fragments streamed per wave through the prefetch ring (conv2d_wlds = 0) and the persistent kernel
     with the layer's weights resident in LDS (2 = at any size; ragged 45 x 70 maps: partial tiles, 2 x 12 tiles over the CUs)."""
     L, ops = env
-    L.set_tuning("conv2d_wlds", wlds)
     g = torch.Generator().manual_seed(ci + co)
     B, H, W = 2, 45, 70
     x = torch.randn(B, ci, H, W, generator=g)
@@ -68,11 +67,9 @@ def test_conv2d_leaky_relu_layers_of_the_cvp_pyramid(env, ci, co, wlds):
     layer = ops.Conv2dLayer.build(w, stride=1, device="cuda", conv_bias=bias, leaky=0.1, dtype=dtype)
     xcl = torch.zeros(B, H, W, layer.c_in, dtype=dtype)
     xcl[..., :ci] = x.permute(0, 2, 3, 1).to(dtype)
-    try:
+    with L.tuning(conv2d_wlds=wlds):
         got = ops.conv2d(xcl.cuda(), layer, out_dtype=torch.float32)
         got16 = ops.conv2d(xcl.cuda(), layer)
-    finally:
-        L.set_tuning("conv2d_wlds", 1)
     check_close(f"leaky conv2d {ci}->{co}", got.permute(0, 3, 1, 2).cpu(), ref, max_abs=3e-5 * float(ref.abs().max()) + 1e-6, rel_l2=1e-5)
     assert torch.equal(got16, got.to(dtype))
     assert float((ref < 0).float().mean()) > 0.2     # the negative branch is exercised
@@ -114,13 +111,10 @@ def test_weights_in_lds_kernel_with_residual_equals_streaming_kernel(env, ci, co
     skip_wide = torch.randn(B, H, W, co + 8, generator=g).to(dtype).cuda()
     res = {}
     for wl in (0, 2):
-        L.set_tuning("conv2d_wlds", wl)
-        try:
+        with L.tuning(conv2d_wlds=wl):
             out = torch.full((B, H, W, co + 16), -3.0, dtype=dtype, device="cuda")
             ops.conv2d(x, layer, skip=skip_wide, skip_coff=8, out=out, out_coff=8)
             res[wl] = (out, ops.conv2d(x, layer, skip=skip_wide[..., 8:].contiguous()), ops.conv2d(x, layer))
-        finally:
-            L.set_tuning("conv2d_wlds", 1)
     for a, b in zip(res[0], res[2]):
         assert torch.equal(a, b)
     out = res[2][0]

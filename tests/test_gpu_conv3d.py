@@ -37,7 +37,6 @@ def test_conv3d_plain(env, cin, cout, kind, dtype, small_tiles):
     """small_tiles=1: 1x4x16 tiles with the output channels split over blockIdx.y (what small volumes get);
     small_tiles=0: the large-tile variant (what the full-resolution layers get)."""
     L, ops = env
-    L.set_tuning("conv_small_tiles", small_tiles)
     g = torch.Generator().manual_seed(cin * 1000 + cout * 10 + kind)
     D, H, W = (6, 10, 21) if kind == L.CONV_S1 else (7, 9, 35) if kind == L.CONV_S2 else (3, 5, 19)
     B = 2
@@ -46,10 +45,8 @@ def test_conv3d_plain(env, cin, cout, kind, dtype, small_tiles):
     wshape = (cin, cout, 3, 3, 3) if transposed else (cout, cin, 3, 3, 3)
     w = bf16_round(torch.randn(wshape, generator=g) / np.sqrt(27 * cin))
     layer = ops.Conv3dLayer.build(w, kind=kind, transposed=transposed, device="cuda", dtype=dtype)
-    try:
+    with L.tuning(conv_small_tiles=small_tiles):
         y = ops.conv3d(ops.to_channels_last(x.cuda(), dtype), layer, out_dtype=torch.float32)   # bf16-exact values are fp16-exact
-    finally:
-        L.set_tuning("conv_small_tiles", 1)
     ref = _ref_conv(x, w, kind, transposed, L)
     check_close(f"conv3d {cin}->{cout} kind {kind} {dtype} operands, fp32 out", y.permute(0, 4, 1, 2, 3).cpu(), ref, max_abs=2e-3, rel_l2=1e-4)
 
@@ -171,11 +168,8 @@ def test_sweep_kernel_matches_brick_kernel_and_aten(env, shape, th16, dtype):
         finally:
             ops.USE_SWEEP_KERNEL = True
         assert layer.kind == (L.CONV_S1P8 if use else L.CONV_S1)
-        L.set_tuning("sweep_th16", th16)       # 16-row / 512-thread tiles (when H >= 16) or 8-row / 256-thread tiles
-        try:
+        with L.tuning(sweep_th16=th16):      # 16-row / 512-thread tiles (when H >= 16) or 8-row / 256-thread tiles
             outs[use] = ops.conv3d(xcl, layer, skip=scl, out_dtype=torch.float32).permute(0, 4, 1, 2, 3).cpu()
-        finally:
-            L.set_tuning("sweep_th16", 0)
     check_close(f"sweep vs ATen {shape} {dtype}", outs[True], ref, max_abs=3e-3, rel_l2=2e-4)
     check_close(f"sweep vs brick {shape} {dtype}", outs[True], outs[False], max_abs=1e-4)
 
@@ -208,13 +202,10 @@ def test_kd_in_rows_sweep_matches_plane_pair_sweep_and_aten(env, shape, dc, pd, 
     assert layer.kind == L.CONV_S1P8
     outs = {}
     for kdm in (0, 1, 2):
-        L.set_tuning("sweep_kdm", kdm); L.set_tuning("sweep_dc", dc if kdm else 0); L.set_tuning("sweep_kdm_pd", pd)
-        try:
+        with L.tuning(sweep_kdm=kdm, sweep_dc=dc if kdm else 0, sweep_kdm_pd=pd):
             out = torch.full((2, D, H, W, 8), float("nan"), dtype=torch.float32 if out_f32 else dtype, device="cuda")
             ops.conv3d(xcl, layer, skip=scl, out=out)
             outs[kdm] = out.float().permute(0, 4, 1, 2, 3).cpu()
-        finally:
-            L.set_tuning("sweep_kdm", 0); L.set_tuning("sweep_dc", 0); L.set_tuning("sweep_kdm_pd", 0)
     ulp = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
     for kdm in (1, 2):
         check_close(f"kd-in-rows({kdm}) vs ATen {shape} {dtype}", outs[kdm], ref, max_abs=3e-3 if out_f32 else None, rel_l2=2e-4 if out_f32 else 2 * ulp)
@@ -225,11 +216,8 @@ def test_kd_in_rows_sweep_matches_plane_pair_sweep_and_aten(env, shape, dc, pd, 
     # NaN in, NaN out (relu_floor keeps it) -- and only where the receptive field holds it
     xn = xcl.clone()
     xn[0, D // 2, H // 2, W // 2, 3] = float("nan")
-    L.set_tuning("sweep_kdm", 1)
-    try:
+    with L.tuning(sweep_kdm=1):
         yn = ops.conv3d(xn, layer, skip=scl, out_dtype=torch.float32)
-    finally:
-        L.set_tuning("sweep_kdm", 0)
     nan = torch.isnan(yn[0]).any(-1)
     d0, h0, w0 = D // 2, H // 2, W // 2
     exp = torch.zeros_like(nan)
@@ -271,11 +259,8 @@ def test_narrow_sweep_kernel_matches_brick_kernel_and_aten(env, cin, shape, tran
             ops.USE_SWEEP_KERNEL = True
         assert layer.kind == (L.CONV_S1P8 if use else L.CONV_S1)
         out = torch.full((2, D, H, W, 16), 7.0, dtype=dtype, device="cuda")     # the conv writes channels [8, 16)
-        L.set_tuning("sweep_dc", dc)
-        try:
+        with L.tuning(sweep_dc=dc):
             ops.conv3d(xcl, layer, in_coff=8, skip=scl, skip_coff=4, out=out, out_coff=8)
-        finally:
-            L.set_tuning("sweep_dc", 0)
         assert bool((out[..., :8] == 7.0).all())
         outs[use] = out[..., 8:].float().permute(0, 4, 1, 2, 3).cpu()
     ulp = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
@@ -315,11 +300,8 @@ def test_sweep16_kernel_matches_brick_kernel_and_aten(env, shape, transposed, dc
             ops.USE_SWEEP_KERNEL, ops.SWEEP16 = True, False
         assert layer.kind == (L.CONV_S1P8 if use else L.CONV_S1)
         out = torch.full((2, D, H, W, 24), 7.0, dtype=dtype, device="cuda")
-        L.set_tuning("sweep_dc", dc)
-        try:
+        with L.tuning(sweep_dc=dc):
             ops.conv3d(xcl, layer, in_coff=8, skip=scl, skip_coff=4, out=out, out_coff=4)
-        finally:
-            L.set_tuning("sweep_dc", 0)
         assert bool((out[..., :4] == 7.0).all()) and bool((out[..., 20:] == 7.0).all())
         outs[use] = out[..., 4:20].float().permute(0, 4, 1, 2, 3).cpu()
     ulp = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
@@ -438,11 +420,8 @@ def test_stride2_sweep_kernel_matches_brick_kernel_and_aten(env, cout, shape, dc
     outs = {}
     for sweep in (2, 0):                 # 2: the sweep at any size; 0: the brick kernel
         out = torch.full((2, Do, Ho, Wo, cout + 8), 7.0, dtype=odt, device="cuda")
-        L.set_tuning("conv_s2_sweep", sweep); L.set_tuning("s2s_slots", dc_slots * 2 * ((Ho + 7) // 8) * ((Wo + 15) // 16))
-        try:
+        with L.tuning(conv_s2_sweep=sweep, s2s_slots=dc_slots * 2 * ((Ho + 7) // 8) * ((Wo + 15) // 16)):
             ops.conv3d(xcl, layer, in_coff=8, skip=scl, skip_coff=4, out=out, out_coff=4, out_dtype=odt)
-        finally:
-            L.set_tuning("conv_s2_sweep", 1); L.set_tuning("s2s_slots", 0)
         assert bool((out[..., :4] == 7.0).all()) and bool((out[..., 4 + cout:] == 7.0).all())
         outs[sweep] = out[..., 4:4 + cout].float().permute(0, 4, 1, 2, 3).cpu()
     ulp = 0.0 if out_f32 else (2 ** -8 if dtype == torch.bfloat16 else 2 ** -11)
@@ -452,11 +431,8 @@ def test_stride2_sweep_kernel_matches_brick_kernel_and_aten(env, cout, shape, dc
     plain = {}
     ref_plain = F.relu(F.batch_norm(conv, mean, var, gamma, beta, training=False, eps=1e-5))
     for sweep in (2, 0):
-        L.set_tuning("conv_s2_sweep", sweep)
-        try:
+        with L.tuning(conv_s2_sweep=sweep):
             plain[sweep] = ops.conv3d(xcl, layer, in_coff=8).float().permute(0, 4, 1, 2, 3).cpu()
-        finally:
-            L.set_tuning("conv_s2_sweep", 1)
     u16 = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
     check_close(f"s2 sweep (plain) vs ATen {shape} -> {cout} {dtype}", plain[2], ref_plain, max_abs=u16 * float(ref_plain.abs().max()) + 2e-3)
     check_close(f"s2 sweep (plain) vs brick {shape} -> {cout} {dtype}", plain[2], plain[0], max_abs=u16 * float(ref_plain.abs().max()) + 1e-4)
@@ -485,11 +461,8 @@ def test_one_channel_head_depth_sweep_matches_brick_variant_and_aten(env, shape,
     assert layer.kind == L.CONV_S1C1
     outs = {}
     for sweep in (2, 0):                # 2: the sweep at any depth; 0: the brick variant
-        L.set_tuning("c1_sweep", sweep)
-        try:
+        with L.tuning(c1_sweep=sweep):
             y = ops.conv3d(xcl, layer, in_coff=8, skip=scl, out_dtype=out_dtype)
-        finally:
-            L.set_tuning("c1_sweep", 1)
         outs[sweep] = y.float().permute(0, 4, 1, 2, 3).cpu()
     tol = 3e-3 if out_dtype is not None else (2 ** -8 if dtype == torch.bfloat16 else 2 ** -11) * float(ref.abs().max()) + 1e-3
     check_close(f"c1 sweep vs ATen {shape} {dtype}", outs[2], ref, max_abs=tol)
@@ -512,12 +485,9 @@ def test_fused_prob_softargmin_tail_equals_separate_launches(env, shape, dtype):
     dv = torch.stack([torch.linspace(2.0, 6.0, D), torch.linspace(1.0, 9.0, D)]).cuda().contiguous()
     xcl = ops.to_channels_last(x.cuda(), dtype)
     layer = ops.Conv3dLayer.build(w, kind=L.CONV_S1, device="cuda", conv_bias=bias, dtype=dtype)
-    L.set_tuning("c1_sweep", 2)
-    try:
+    with L.tuning(c1_sweep=2):
         fused = ops.prob_softargmin(xcl, layer, dv)
         logits = ops.conv3d(xcl, layer, out_dtype=torch.float32).view(2, D, H, W)
-    finally:
-        L.set_tuning("c1_sweep", 1)
     assert fused is not None
     sep = ops.softargmin(logits, dv, want_conf=True, conf_mode=0)
     assert torch.equal(fused["logits"], logits)
@@ -555,18 +525,12 @@ def test_tail_sweep_equals_the_two_layers(env, shape, with_skip, dtype):
     scl = ops.to_channels_last(skip.cuda(), dtype) if with_skip else None
     outs = {}
     for nbk in (0, 2, 1):
-        L.set_tuning("tail_nbk", nbk)
-        try:
+        with L.tuning(tail_nbk=nbk):
             outs[nbk] = ops.tail_sweep(xcl, up, head, skip=scl)
-        finally:
-            L.set_tuning("tail_nbk", 0)
         assert outs[nbk] is not None
     u11 = ops.conv3d(xcl, up, skip=scl)
-    L.set_tuning("c1_sweep", 2)              # the depth-sweep variant of the head: the accumulation chains the fused kernel uses
-    try:
+    with L.tuning(c1_sweep=2):      # the depth-sweep variant of the head: the accumulation chains the fused kernel uses
         two = ops.conv3d(u11, head, out_dtype=torch.float32).view(B, 2 * Di, 2 * Hi, 2 * Wi)
-    finally:
-        L.set_tuning("c1_sweep", 1)
     default = ops.conv3d(u11, head, out_dtype=torch.float32).view(B, 2 * Di, 2 * Hi, 2 * Wi)
     torch.cuda.synchronize()
     for nbk, o in outs.items():
@@ -580,11 +544,8 @@ def test_tail_sweep_equals_the_two_layers(env, shape, with_skip, dtype):
     dv = torch.stack([torch.linspace(2.0, 6.0, D2), torch.linspace(1.0, 9.0, D2)]).cuda().contiguous()
     sep = ops.softargmin(two.contiguous(), dv, want_conf=True, conf_mode=0)
     for nbk in (0, 2, 3):
-        L.set_tuning("tail_nbk", nbk)
-        try:
+        with L.tuning(tail_nbk=nbk):
             fz = ops.tail_sweep(xcl, up, head, skip=scl, regress=dv)
-        finally:
-            L.set_tuning("tail_nbk", 0)
         assert isinstance(fz, dict) and torch.equal(fz["logits"], two)
         check_close(f"tail sweep regression depth {shape} nbk={nbk}", fz["depth"].cpu(), sep["depth"].cpu(), max_abs=2e-6 * 9.0)
         check_close(f"tail sweep regression confidence {shape} nbk={nbk}", fz["conf"].cpu(), sep["conf"].cpu(), max_abs=2e-5)
@@ -616,11 +577,8 @@ def test_conv3d_epilogue_propagates_nan_like_torch_relu(env, cin, cout, kind, sh
     wshape = (cin, cout, 3, 3, 3) if transposed else (cout, cin, 3, 3, 3)
     w = bf16_round(torch.randn(wshape, generator=g) / np.sqrt(27 * cin))
     layer = ops.Conv3dLayer.build(w, kind=kind, transposed=transposed, device="cuda", relu=relu, dtype=torch.float16)
-    L.set_tuning("conv_s2_sweep", 2)
-    try:
+    with L.tuning(conv_s2_sweep=2):
         y = ops.conv3d(ops.to_channels_last(x.cuda(), torch.float16), layer, out_dtype=torch.float32)
-    finally:
-        L.set_tuning("conv_s2_sweep", 1)
     ref = _ref_conv(x, w, kind, transposed, L)
     if relu:
         ref = F.relu(ref)
@@ -698,16 +656,9 @@ def test_tall_64_channel_tiles_equal_the_4x4_tiles(env, cout, shape, dtype):
     bn = (torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1, torch.randn(cout, generator=g) * 0.1, torch.rand(cout, generator=g) + 0.5)
     layer = ops.Conv3dLayer.build(w, kind=L.CONV_S1, device="cuda", dtype=dtype, bn=bn, relu=True)
     res = {}
-    L.set_tuning("conv_small_tiles", 0)
-    L.set_tuning("conv_wide", 0)               # (both arms on the brick kernel)
-    try:
-        for tall in (0, 2):
-            L.set_tuning("conv_tall64", tall)
+    for tall in (0, 2):
+        with L.tuning(conv_small_tiles=0, conv_wide=0, conv_tall64=tall):      # (both arms on the brick kernel)
             res[tall] = (ops.conv3d(x, layer, skip=sk), ops.conv3d(x, layer, out_dtype=torch.float32))
-    finally:
-        L.set_tuning("conv_tall64", 1)
-        L.set_tuning("conv_small_tiles", 1)
-        L.set_tuning("conv_wide", 1)
     assert torch.equal(res[0][0], res[2][0]) and torch.equal(res[0][1], res[2][1])
     scale = bn[0] / torch.sqrt(bn[3] + 1e-5)
     ref = F.relu(F.conv3d(x.float().cpu().permute(0, 4, 1, 2, 3), w, padding=1) * scale.view(1, -1, 1, 1, 1) + (bn[1] - bn[2] * scale).view(1, -1, 1, 1, 1))
@@ -734,14 +685,11 @@ def test_fused_residual_block_equals_the_two_launches(env, shape, slots, dtype):
         relu=relu, relu_post=relu_post)
     l1, l2 = mk(True, False), mk(False, True)
     want = ops.conv3d(ops.conv3d(x, l1), l2, skip=x)
-    L.set_tuning("block8_slots", slots)
-    try:
+    with L.tuning(block8_slots=slots):
         got = ops.conv3d_block8(x, l1, l2, residual=True)
         out = torch.full((B, D, H, W, 12), -5.0, dtype=dtype, device="cuda")
         ops.conv3d_block8(xw, l1, l2, residual=True, in_coff=8, out=out, out_coff=4)
         plain = ops.conv3d_block8(x, l1, l2, residual=False)
-    finally:
-        L.set_tuning("block8_slots", 0)
     assert got is not None and torch.equal(got, want)
     assert torch.equal(out[..., 4:], want) and bool((out[..., :4] == -5.0).all())
     assert torch.equal(plain, ops.conv3d(ops.conv3d(x, l1), l2))
@@ -769,14 +717,9 @@ def test_wide_kernel_equals_the_brick_kernel_and_aten(env, cin, cout, shape, tra
     bn = (torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1, torch.randn(cout, generator=g) * 0.1, torch.rand(cout, generator=g) + 0.5)
     layer = ops.Conv3dLayer.build(w, kind=L.CONV_S1, transposed=transposed, device="cuda", dtype=dtype, bn=bn, relu=True)
     res = {}
-    L.set_tuning("conv_small_tiles", 0)       # the brick kernel's row-split variant (the k-split small tiles sum in another order)
-    try:
-        for wide in (0, 2):                   # brick | the wide kernel at any size
-            L.set_tuning("conv_wide", wide)
+    for wide in (0, 2):                       # brick | the wide kernel at any size
+        with L.tuning(conv_small_tiles=0, conv_wide=wide):     # the brick kernel's row-split variant (the k-split small tiles sum in another order)
             res[wide] = (ops.conv3d(x, layer, skip=sk), ops.conv3d(x, layer, out_dtype=torch.float32), ops.conv3d(x, layer))
-    finally:
-        L.set_tuning("conv_wide", 1)
-        L.set_tuning("conv_small_tiles", 1)
     for arm in (2,):
         for a_, b_ in zip(res[0], res[arm]):
             assert torch.isfinite(b_.float()).all()

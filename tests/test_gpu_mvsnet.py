@@ -210,12 +210,11 @@ def test_fused_tail_option_equals_default_path(env):
     run = lambda: net(dev["imgs"], dev["K"], dev["R"], dev["t"], dev["depth_min"], dev["depth_max"])
     want = run()
     M.FUSED_TAIL = True
-    L.set_tuning("c1_sweep", 2)
     try:
-        got = run()
+        with L.tuning(c1_sweep=2):
+            got = run()
     finally:
         M.FUSED_TAIL = False
-        L.set_tuning("c1_sweep", 1)
     check_close("fused tail depth", got["depth"].cpu(), want["depth"].cpu(), max_abs=2e-5)
     check_close("fused tail confidence", got["photometric_confidence"].cpu(), want["photometric_confidence"].cpu(), max_abs=5e-5)
 

@@ -115,11 +115,8 @@ def test_warp_cost_kernels_are_bit_stable_beside_conv0(env, soak, name, tiled, c
         dv = (dv.view(1, -1, 1, 1) + 0.01 * torch.rand(1, 1, 128, 160, device="cuda")).contiguous()
     code = {"variance": L.COST_VARIANCE, "softmin": L.COST_SOFTMIN, "variance_cvp": L.COST_VARIANCE_CVP}[cost]
     assert L.get_tuning("warp_tiled") == 1
-    L.set_tuning("warp_tiled", tiled)
-    try:
+    with L.tuning(warp_tiled=tiled):
         bad, _, _ = soak.run(f"warp_cost {name}", lambda: ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=code, temp=0.7, out_dtype=torch.float16))
-    finally:
-        L.set_tuning("warp_tiled", -1)
     assert bad == 0
 
 
@@ -138,12 +135,9 @@ def test_groupcorr_homog_warp_is_bit_stable_beside_conv0(env, soak, kernel):
     fcl = [ops.to_channels_last(feats[i].cuda(), torch.float16) for i in range(V)]
     planes = (cams[0][:, 1, 3, 0].view(1, 1) + di[:, :1] * 2.0 * torch.arange(D, dtype=torch.float32).view(1, D)).contiguous().cuda()
     assert L.get_tuning("warp_gc_lds") == 1
-    L.set_tuning("warp_gc_lds", 1 if kernel == "lds" else 0)
-    try:
+    with L.tuning(warp_gc_lds=1 if kernel == "lds" else 0):
         bad, _, _ = soak.run(f"warp_cost groupcorr HOMOG ({kernel})", lambda: ops.warp_cost(fcl[0], fcl[1:], blocks, planes, geom=L.GEOM_HOMOG,
                                                                                           cost=L.COST_GROUPCORR, out_dtype=torch.float16))
-    finally:
-        L.set_tuning("warp_gc_lds", 1)
     assert bad == 0
 
 
@@ -182,13 +176,8 @@ def test_conv3d_kernels_are_bit_stable_beside_conv0(env, soak, name, cin, cout, 
     if with_skip:
         so = tuple(2 * v for v in dhw) if tr else dhw
         skip = (torch.randn(1, *so, cout, generator=g) * 0.5).to(torch.float16).cuda()
-    for k, v in tune.items():
-        L.set_tuning(k, v)
-    try:
+    with L.tuning(**tune):
         bad, _, _ = soak.run(f"conv3d {name}", lambda: ops.conv3d(x, layer, skip=skip))
-    finally:
-        for k in tune:
-            L.set_tuning(k, 1 if k == "c1_sweep" else 0)
     assert bad == 0
 
 

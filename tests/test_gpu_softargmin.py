@@ -93,12 +93,9 @@ def test_short_depth_axes_thread_per_pixel_kernel(env, D, per_pixel):
     for mode in (0, 1):
         res = {}
         for small in (1, 0):
-            L.set_tuning("softargmin_small", small)
-            try:
+            with L.tuning(softargmin_small=small):
                 res[small] = ops.softargmin(logits, depth, want_index=True, want_conf=True, conf_mode=mode, window=2.0, want_entropy=True,
                                             index_offset=3)
-            finally:
-                L.set_tuning("softargmin_small", 1)
         o = res[1]
         check_close(f"depth D={D}", o["depth"].cpu(), (p * dd).sum(1).float(), max_abs=3e-5 * float(dd.max()))
         check_close(f"index D={D}", o["index"].cpu(), (e_idx + 3).float(), max_abs=2e-5 * max(D, 4))

@@ -1157,12 +1157,9 @@ def test_warp_backward_tiled_vs_direct_kernel(case):
     g = (torch.randn(1, D, h, w, 32, generator=gen) * 0.1).to(dt).cuda()
     res = {}
     for direct in (0, 1):
-        L.set_tuning("warp_bwd_direct", direct)
-        try:
+        with L.tuning(warp_bwd_direct=direct):
             res[direct] = ops.warp_cost_bwd(ref, srcs, cams, depth, g, geom=L.GEOM_PROJ, cost=L.COST_VARIANCE)
             torch.cuda.synchronize()
-        finally:
-            L.set_tuning("warp_bwd_direct", 0)
     check_close(f"{case}: d ref", res[0][0].cpu(), res[1][0].cpu(), rel_l2=1e-5)
     for v in range(V - 1):
         assert float(res[1][1][v].abs().max()) > 0

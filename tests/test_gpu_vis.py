@@ -318,15 +318,12 @@ def test_fused_pair_head_equals_head_plus_softargmin(env, shape, force, dtype):
     tiles, nblocks = B * ((H + 3) // 4) * ((W + 31) // 32), (D + 5) // 6
     ndc = min(1 if tiles >= 768 else 768 // tiles, nblocks)
     qualifies = force or (nblocks + ndc - 1) // ndc >= 3
-    L.set_tuning("c1_sweep", 2 if force else 1)
-    try:
+    with L.tuning(c1_sweep=2 if force else 1):
         score = head(x)                                                                  # (the same head kernel: same bits)
         want = ops.softargmin(score, None, want_index=True, want_entropy=True)
         got = head.head_index_entropy(x, idx, ent, want_scores=True)
         idx2, ent2 = torch.empty_like(idx), torch.empty_like(ent)
         got2 = head.head_index_entropy(x, idx2, ent2)                                    # no score volume: same maps
-    finally:
-        L.set_tuning("c1_sweep", 1)
     if not qualifies:
         assert got is None and got2 is None
         return

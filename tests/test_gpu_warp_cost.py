@@ -88,14 +88,9 @@ def test_cost_volume_16bit_storage(env, lpv, dtype):
     ref = O.variance_cost(fr[0], warped)
     cams = ops.proj_cams([proj[:, i].cuda() for i in range(1, V)], proj[:, 0].cuda())
     # 0 = default mapping; 4/2/1 = direct kernel with that many lanes per voxel; -1 = LDS-staged tiled kernel
-    L.set_tuning("warp_lpv", max(lpv, 0))
-    L.set_tuning("warp_tiled", 1 if lpv < 0 else 0)
-    try:
+    with L.tuning(warp_lpv=max(lpv, 0), warp_tiled=1 if lpv < 0 else 0):
         cost = ops.warp_cost(_cl(feats[0], dtype), [_cl(feats[i], dtype) for i in range(1, V)],
                              cams, dv.cuda(), cost=L.COST_VARIANCE, out_dtype=dtype)
-    finally:
-        L.set_tuning("warp_lpv", 0)
-        L.set_tuning("warp_tiled", -1)
     ulp = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
     s = check_close(f"variance cost {dtype} storage lpv={lpv}", cost.float().permute(0, 4, 1, 2, 3).cpu(), ref, rel_l2=ulp)
     assert s["max_abs"] <= ulp * s["ref_max"] + 3e-4
@@ -181,11 +176,8 @@ def test_tiled_kernel_equals_direct_kernel(env, baseline_scale, shape, V, D, cos
     code = {"variance": L.COST_VARIANCE, "softmin": L.COST_SOFTMIN, "variance_cvp": L.COST_VARIANCE_CVP}[cost_name]
     outs = []
     for tiled in (1, 0):
-        L.set_tuning("warp_tiled", tiled)
-        try:
+        with L.tuning(warp_tiled=tiled):
             outs.append(ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=code, temp=0.7, out_dtype=torch.float16).float().cpu())
-        finally:
-            L.set_tuning("warp_tiled", -1)
     s = check_close(f"tiled vs direct {cost_name} baseline x{baseline_scale} {shape}", outs[0], outs[1],
                     max_abs=2 ** -10 * float(outs[1].abs().max()), rel_l2=2e-5)
     assert float(outs[1].abs().max()) > 0
@@ -215,13 +207,11 @@ def test_adaptive_split_levels_store_the_same_bits_on_the_wide_baseline_rig(env,
     run = lambda: ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=L.COST_VARIANCE, out_dtype=dtype)
     fn = L.lib().pscv_debug_wl_mode_hist
     fn.argtypes, fn.restype = [ctypes.c_void_p], None
-    try:
-        L.set_tuning("warp_tiled", 0)
+    with L.tuning(warp_tiled=0):
         want = run().clone()
-        L.set_tuning("warp_tiled", 1)
-        direct_share = {}
-        for tile in (0, 3, 1):
-            L.set_tuning("warp_tile", tile)
+    direct_share = {}
+    for tile in (0, 3, 1):
+        with L.tuning(warp_tiled=1, warp_tile=tile):
             hist = torch.zeros(16, dtype=torch.int32, device="cuda")
             fn(hist.data_ptr())
             try:
@@ -229,12 +219,9 @@ def test_adaptive_split_levels_store_the_same_bits_on_the_wide_baseline_rig(env,
                 torch.cuda.synchronize()
             finally:
                 fn(None)
-            assert torch.equal(got, want), f"warp_tile = {tile}: stored bits differ from the direct-gather kernel"
-            hm = hist.view(4, 4).cpu()                       # [view][DIRECT, GEN, FAST, ZERO]
-            direct_share[tile] = float(hm[:, 0].sum()) / float(hm.sum())
-    finally:
-        L.set_tuning("warp_tiled", -1)
-        L.set_tuning("warp_tile", 0)
+        assert torch.equal(got, want), f"warp_tile = {tile}: stored bits differ from the direct-gather kernel"
+        hm = hist.view(4, 4).cpu()                       # [view][DIRECT, GEN, FAST, ZERO]
+        direct_share[tile] = float(hm[:, 0].sum()) / float(hm.sum())
     print(f"[parity] DTU-like rig D={D} {dtype}: share of (plane range, view) pairs on global taps: no split {direct_share[1]:.3f}, "
           f"halves {direct_share[3]:.3f}, halves + quarters {direct_share[0]:.3f}", flush=True)
     assert direct_share[0] < direct_share[3] < direct_share[1]
@@ -270,13 +257,8 @@ def test_lane_owner_kernel_equals_direct_kernel(env, baseline_scale, shape, V, D
     outs = {}
     # ("warp_tile" = 2: the adaptive split of a chunk whose boxes do not fit, round 5; off by default in this kernel)
     for name, tiled, tile in (("lane-owner", 4, 0), ("lane-owner, general path", 4, 7), ("lane-owner, split", 4, 2), ("direct", 0, 0)):
-        L.set_tuning("warp_tiled", tiled)
-        L.set_tuning("warp_tile", tile)
-        try:
+        with L.tuning(warp_tiled=tiled, warp_tile=tile):
             outs[name] = ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=code, out_dtype=out_dtype)
-        finally:
-            L.set_tuning("warp_tiled", -1)
-            L.set_tuning("warp_tile", 0)
     torch.cuda.synchronize()
     want = outs["direct"]
     assert float(want.float().abs().max()) > 0
@@ -326,13 +308,8 @@ def test_quad_kernel_equals_generic_kernel(env, baseline_scale, shape, D, per_pi
     ref_in = None if code == L.COST_WARP_ONLY else fcl[0]
     outs = []
     for q2 in (1, 0):
-        L.set_tuning("warp_q2", q2)
-        L.set_tuning("warp_tiled", 0)      # (the LDS-staged kernel is the default where it applies: compare the two direct kernels)
-        try:
+        with L.tuning(warp_q2=q2, warp_tiled=0):      # (the LDS-staged kernel is the default where it applies: compare the two direct kernels)
             outs.append(ops.warp_cost(ref_in, fcl[1:], cams, dv.cuda(), geom=geom, cost=code, temp=0.7, out_dtype=dtype).float().cpu())
-        finally:
-            L.set_tuning("warp_q2", 1)
-            L.set_tuning("warp_tiled", -1)
     ulp = 2 ** -7 if dtype == torch.bfloat16 else 2 ** -10
     assert float(outs[1].abs().max()) > 0
     check_close(f"quad vs generic {cost_name} {dtype} baseline x{baseline_scale} {shape} D={D}", outs[0], outs[1],
@@ -368,13 +345,8 @@ def test_lds_staged_groupcorr_equals_quad_kernel(env, baseline_scale, shape, V, 
     outs = {}
     assert L.get_tuning("warp_gc_lds") == 1          # (default: per-batch planes on the staged kernel, per-pixel planes on the quad kernel)
     for name, gc, tile in (("staged", 2, 0), ("staged kernel, nothing staged", 2, 7), ("quad", 0, 0)):
-        L.set_tuning("warp_gc_lds", gc)
-        L.set_tuning("warp_tile", tile)
-        try:
+        with L.tuning(warp_gc_lds=gc, warp_tile=tile):
             outs[name] = ops.warp_cost(fcl[0], fcl[1:], cams, dv.cuda(), geom=L.GEOM_HOMOG, cost=L.COST_GROUPCORR, out_dtype=dtype).float().cpu()
-        finally:
-            L.set_tuning("warp_gc_lds", 1)
-            L.set_tuning("warp_tile", 0)
     want = outs["quad"]
     assert tuple(want.shape) == (V - 1, B, D, h, w, 8) and float(want.abs().max()) > 0
     ulp = 2 ** -7 if dtype == torch.bfloat16 else 2 ** -10
@@ -413,11 +385,8 @@ def test_lds_staged_kernels_on_random_rigs(env, seed):
     dv = dvals[:, 0].contiguous().cuda()
     outs = {}
     for name, tiled in (("quad-owner", 1), ("lane-owner", 4), ("direct", 0)):
-        L.set_tuning("warp_tiled", tiled)
-        try:
+        with L.tuning(warp_tiled=tiled):
             outs[name] = ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=L.COST_VARIANCE, out_dtype=dtype)
-        finally:
-            L.set_tuning("warp_tiled", -1)
     for name in ("quad-owner", "lane-owner"):
         ne = int((outs[name] != outs["direct"]).sum())
         assert ne == 0, f"{tag}: variance, {name} vs direct: {ne} of {outs['direct'].numel()} values differ"
@@ -431,11 +400,8 @@ def test_lds_staged_kernels_on_random_rigs(env, seed):
         planes = (planes.view(B, D, 1, 1) * (1.0 + 0.03 * torch.rand(B, 1, h, w, generator=gen))).contiguous()
     gouts = {}
     for name, gc in (("staged", 2), ("quad", 0)):
-        L.set_tuning("warp_gc_lds", gc)
-        try:
+        with L.tuning(warp_gc_lds=gc):
             gouts[name] = ops.warp_cost(fcl[0], fcl[1:], hc, planes.cuda(), geom=L.GEOM_HOMOG, cost=L.COST_GROUPCORR, out_dtype=dtype).float().cpu()
-        finally:
-            L.set_tuning("warp_gc_lds", 1)
     ulp = 2 ** -7 if dtype == torch.bfloat16 else 2 ** -10
     scale_v = max(float(gouts["quad"].abs().max()), 1e-6)
     check_close(f"{tag}: groupcorr staged vs quad", gouts["staged"], gouts["quad"], max_abs=ulp * scale_v, rel_l2=ulp / 16 if scale_v > 1e-3 else None)
@@ -457,11 +423,8 @@ def test_staged_kernel_fp16_stores_saturate(env):
     dv = dvals[:, 0].contiguous().cuda()
     outs = []
     for tiled in (1, 0):
-        L.set_tuning("warp_tiled", tiled)
-        try:
+        with L.tuning(warp_tiled=tiled):
             outs.append(ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=L.COST_VARIANCE, out_dtype=torch.float16))
-        finally:
-            L.set_tuning("warp_tiled", -1)
     assert torch.isfinite(outs[0]).all() and float(outs[0].max()) == 65504.0
     assert (outs[0] == 65504.0).float().mean() > 1e-3            # the case really overflows
     assert torch.equal(outs[0], outs[1])
@@ -505,12 +468,9 @@ def test_tuning_knobs_thread_override_and_process_wide(env):
     finally:
         L.set_tuning_thread("warp_lpv", 0, enable=False)
     assert torch.equal(run(), want)
-    L.set_tuning("warp_lpv", 3)
-    try:
+    with L.tuning(warp_lpv=3):
         res = in_other_thread()
         assert isinstance(res.get("err"), L.PscvError)
-    finally:
-        L.set_tuning("warp_lpv", 0)
     assert torch.equal(run(), want)
 
 
@@ -531,11 +491,8 @@ def test_staged_kernel_inf_inputs_stay_inf(env):
     dv = dvals[:, 0].contiguous().cuda()
     outs = []
     for tiled in (1, 0):
-        L.set_tuning("warp_tiled", tiled)
-        try:
+        with L.tuning(warp_tiled=tiled):
             outs.append(ops.warp_cost(fcl[0], fcl[1:], cams, dv, cost=L.COST_VARIANCE, out_dtype=torch.float16))
-        finally:
-            L.set_tuning("warp_tiled", -1)
     staged, direct = outs
     bad = ~torch.isfinite(staged)
     assert bad.any() and bad[0, :, 10, 10, 3].all() and int(bad.sum()) == D       # inf - inf = NaN at that voxel column only
@@ -574,9 +531,8 @@ def test_row_slab_launch_equals_the_rows_of_the_whole_image_launch(env, case):
         if case == "quad_per_pixel":
             dv = (dv.view(B, D, 1, 1) * (1.0 + 0.01 * torch.rand(B, 1, h, w, device="cuda"))).contiguous()
         kw = dict(cost=L.COST_VARIANCE_CVP if case == "generic_16ch" else L.COST_VARIANCE)
-    L.set_tuning("warp_tiled", 0 if case == "quad_variance" else 4 if case == "lane_owner_variance" else 1)
-    L.set_tuning("warp_gc_lds", 2 if case.startswith("homog_groupcorr_lds") else 0)      # (the LDS-staged group-correlation kernel, per-batch and per-pixel planes)
-    try:
+    with L.tuning(warp_tiled=0 if case == "quad_variance" else 4 if case == "lane_owner_variance" else 1,
+                  warp_gc_lds=2 if case.startswith("homog_groupcorr_lds") else 0):      # (the LDS-staged group-correlation kernel, per-batch and per-pixel planes)
         full = ops.warp_cost(fcl[0], fcl[1:], cams, dv, out_dtype=torch.float16, **kw)
         for y0, hs_ in ((0, 20), (13, 25), (30, 22)):
             ref_slab = fcl[0][:, y0:y0 + hs_].contiguous()
@@ -585,6 +541,3 @@ def test_row_slab_launch_equals_the_rows_of_the_whole_image_launch(env, case):
             want = full[..., y0:y0 + hs_, :, :]
             assert slab.shape == want.shape
             assert torch.equal(slab, want), f"{case}: slab at row {y0} differs from the whole-image launch on {int((slab != want).sum())} values"
-    finally:
-        L.set_tuning("warp_tiled", -1)
-        L.set_tuning("warp_gc_lds", 1)

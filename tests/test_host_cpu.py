@@ -499,6 +499,66 @@ def test_tuning_knobs_are_process_wide_with_a_per_thread_override():
         L.set_tuning("no_such_knob", 1)
     with pytest.raises(L.PscvError):
         L.set_tuning_thread("no_such_knob", 1)
+    for setter in (L.set_tuning, L.set_tuning_thread):       # one validation for both: the removed diagnostic build is refused
+        with pytest.raises(L.PscvError, match="warp_tiled = 3"):
+            setter("warp_tiled", 3)
+        assert L.get_tuning("warp_tiled") == 1
+
+
+def _knob_table():
+    """[(key, C++ symbol, default)] of PSCV_KNOB_TABLE in csrc/pscv_common.h."""
+    src = open(os.path.join(REPO, "wild_deep_mvs_amd", "csrc", "pscv_common.h")).read()
+    body = src[src.index("#define PSCV_KNOB_TABLE(X)"):src.index("#define PSCV_KNOB_DECLARE")]
+    return [(k, sym, int(d)) for k, sym, d in re.findall(r'X\("(\w+)",\s*(\w+),\s*(-?\d+)\)', body)]
+
+
+def test_knob_table_is_documented_and_holds_the_defaults():
+    """Every key of the C++ knob table has one entry in the key list of include/pscv.h and the other way round, and a fresh process
+    reads the table's default for each."""
+    import subprocess
+    import sys
+    table = _knob_table()
+    keys = [k for k, _, _ in table]
+    assert len(keys) >= 27 and len(set(keys)) == len(keys) and len({sym for _, sym, _ in table}) == len(keys)
+    hdr = open(os.path.join(REPO, "include", "pscv.h")).read()
+    doc = hdr[hdr.index("/* Tuning knobs for measurement runs"):hdr.index("int pscv_set_tuning(")]
+    documented = re.findall(r'^ \*   "(\w+)"', doc, flags=re.M)
+    assert sorted(documented) == sorted(keys), sorted(set(documented) ^ set(keys))
+    code = ("import json, sys; sys.path.insert(0, sys.argv[1]); from wild_deep_mvs_amd import _lib as L; "
+            "print(json.dumps({k: L.get_tuning(k) for k in sys.argv[2:]}))")
+    out = subprocess.run([sys.executable, "-c", code, REPO] + keys, capture_output=True, text=True, check=True).stdout
+    assert json.loads(out.strip().splitlines()[-1]) == {k: d for k, _, d in table}
+
+
+def test_scoped_tuning_restores_nests_and_refuses_an_overridden_knob():
+    gen = L.TUNING_GEN
+    with L.tuning(c1_sweep=0, sweep_dc=12):
+        assert (L.get_tuning("c1_sweep"), L.get_tuning("sweep_dc")) == (0, 12) and L.TUNING_GEN > gen
+        gen = L.TUNING_GEN
+        with L.tuning(c1_sweep=2):
+            assert (L.get_tuning("c1_sweep"), L.get_tuning("sweep_dc")) == (2, 12)
+        assert (L.get_tuning("c1_sweep"), L.get_tuning("sweep_dc")) == (0, 12) and L.TUNING_GEN > gen      # back to the outer block's value
+    assert (L.get_tuning("c1_sweep"), L.get_tuning("sweep_dc")) == (1, 0)
+    with pytest.raises(ZeroDivisionError):
+        with L.tuning(c1_sweep=0):
+            1 / 0
+    assert L.get_tuning("c1_sweep") == 1
+    with pytest.raises(L.PscvError):                     # a value the knob refuses: what was set before it is put back
+        with L.tuning(sweep_dc=12, warp_tiled=3):
+            pass
+    assert (L.get_tuning("sweep_dc"), L.get_tuning("warp_tiled")) == (0, 1)
+    L.set_tuning_thread("c1_sweep", 2)                   # get_tuning now reports the override, not the process-wide value
+    try:
+        with pytest.raises(L.PscvError, match="overrides"):
+            with L.tuning(c1_sweep=0):
+                pass
+        with L.tuning(sweep_dc=12):                      # (other knobs are not affected)
+            assert L.get_tuning("sweep_dc") == 12
+    finally:
+        L.set_tuning_thread("c1_sweep", 0, enable=False)
+    with L.tuning(c1_sweep=0):
+        assert L.get_tuning("c1_sweep") == 0
+    assert L.get_tuning("c1_sweep") == 1
 
 
 def test_replay_keys_follow_options_weights_and_groups():

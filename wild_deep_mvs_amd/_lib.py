@@ -6,6 +6,7 @@ and must be present: there is no PyTorch / CPU fallback for the hot path.  ``lib
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -298,11 +299,35 @@ def get_tuning(key: str) -> int:
     return int(v.value)
 
 
+_thread_overrides = threading.local()     # .keys: the knobs the calling thread overrides (set_tuning_thread)
+
+
 def set_tuning_thread(key: str, value: int, enable: bool = True) -> None:
     """Override (or, enable=False, stop overriding) a knob for the calling host thread only."""
     global TUNING_GEN
     TUNING_GEN += 1
     check(lib().pscv_set_tuning_thread(key.encode(), int(value), 1 if enable else 0), "pscv_set_tuning_thread")
+    keys = _thread_overrides.__dict__.setdefault("keys", set())
+    keys.add(key) if enable else keys.discard(key)
+
+
+@contextlib.contextmanager
+def tuning(**knobs: int):
+    """`with tuning(warp_tiled=0, conv_wide=2): ...` sets process-wide knobs and puts back what they held before, also when the
+    body raises.  Blocks nest.  get_tuning reports the calling thread's override where one is set, which is not the value to put
+    back: entering with such a knob raises."""
+    mine = getattr(_thread_overrides, "keys", ())
+    for key in knobs:
+        if key in mine:
+            raise PscvError(f"tuning({key}=...): this thread overrides '{key}' (set_tuning_thread); the process-wide value cannot be read")
+    saved = {key: get_tuning(key) for key in knobs}
+    try:
+        for key, value in knobs.items():
+            set_tuning(key, value)
+        yield
+    finally:
+        for key, value in saved.items():
+            set_tuning(key, value)
 
 
 def check(rc: int, what: str):

@@ -28,22 +28,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 c2_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 c2_f16x8;
-typedef __attribute__((ext_vector_type(4))) float c2_f32x4;
-
-template <typename H> struct C2Mfma;
-template <> struct C2Mfma<bf16_t> {
-    __device__ static __forceinline__ c2_f32x4 run(const uint4& a, const uint4& b, const c2_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(c2_bf16x8, a), __builtin_bit_cast(c2_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct C2Mfma<f16_t> {
-    __device__ static __forceinline__ c2_f32x4 run(const uint4& a, const uint4& b, const c2_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(c2_f16x8, a), __builtin_bit_cast(c2_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 struct Conv2dArgs {
     const uint16_t* in;      // [B,Hi,Wi,c_in]
     const uint4* wpk;        // [steps][NT][64 lanes] x 8 halves
@@ -79,9 +63,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
     constexpr int PAD = c2_pad(KS);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3, q_ = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + slot;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int tw_i = fast_divmod(wg, a.ntw, a.mg_tw);
     const int th_i = fast_divmod(wg, a.nth, a.mg_th);
     const int b = wg;
@@ -162,7 +144,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
         }
     __syncthreads();
 
-    c2_f32x4 acc[MB][NT];
+    f32x4 acc[MB][NT];
     int anchor[MB];
 #pragma unroll
     for (int i = 0; i < MB; ++i) {
@@ -170,7 +152,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
         const int row = mt >> 1, ct = mt & 1;
         anchor[i] = ((row * STRIDE) * BWL + ct * 16 + n) * VS;
 #pragma unroll
-        for (int m = 0; m < NT; ++m) acc[i][m] = c2_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < NT; ++m) acc[i][m] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int s = 0; s < NSTEPS; ++s) {
@@ -185,7 +167,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
         for (int i = 0; i < MB; ++i) {
             const uint4 xf = *reinterpret_cast<const uint4*>(smem + anchor[i] + koff);
 #pragma unroll
-            for (int m = 0; m < NT; ++m) acc[i][m] = C2Mfma<H>::run(wf[s % PF][m], xf, acc[i][m]);
+            for (int m = 0; m < NT; ++m) acc[i][m] = Mfma<H>::run(wf[s % PF][m], xf, acc[i][m]);
         }
         if (s + PF < NSTEPS) {
 #pragma unroll
@@ -398,11 +380,11 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_wlds_kernel(const Conv2
         if (tn < n_tiles) fetch(tn, val);                        // in flight during the contraction below
         PSCV_STAMP(2)
 
-        c2_f32x4 acc[2][NT];
+        f32x4 acc[2][NT];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int m = 0; m < NT; ++m) acc[i][m] = c2_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int m = 0; m < NT; ++m) acc[i][m] = f32x4{0.f, 0.f, 0.f, 0.f};
         // k-loop, software-pipelined by hand: the operands of step s + 1 are requested BEFORE the MFMAs of step s (two register
         // sets).  Left to the compiler each group of four MFMAs waited for `ds_read`s issued right in front of it, and with two
         // waves per SIMD the LDS latency was exposed at every step (29 % of the MFMA peak).
@@ -422,7 +404,7 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_wlds_kernel(const Conv2
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int m = 0; m < NT; ++m) acc[i][m] = C2Mfma<H>::run(wf[s & 1][m], xf[s & 1][i], acc[i][m]);
+                for (int m = 0; m < NT; ++m) acc[i][m] = Mfma<H>::run(wf[s & 1][m], xf[s & 1][i], acc[i][m]);
             __builtin_amdgcn_sched_barrier(0);
         }
         PSCV_STAMP(3)
@@ -516,8 +498,6 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_wlds_kernel(const Conv2
 }  // namespace pscv
 PSCV_PROF_EXPORT(c2w)
 namespace pscv {
-Knob g_conv2d_wlds = {1, KNOB_SPARE1};    // pscv_set_tuning("conv2d_wlds", 0): 64-channel k3 s1 layers back on conv2d_kernel; 2: at any size
-
 template <typename H, int NT, int CIN>
 static int c2w_launch(Conv2dArgs& a, hipStream_t st) {
     constexpr int LDS = C2WGeom<CIN>::STEPS * NT * 1024 + C2WGeom<CIN>::BRICK + 8 * 32 * (NT * 32 + 16);

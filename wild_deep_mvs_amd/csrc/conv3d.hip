@@ -21,27 +21,7 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// one v_mfma_f32_16x16x32_{bf16,f16}: D[16 x 16] += A[16 x 32] * B[32 x 16], fp32 accumulate
-template <typename H> struct Mfma;
-template <> struct Mfma<bf16_t> {
-    __device__ static __forceinline__ f32x4 run(const uint4& a, const uint4& b, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<f16_t> {
-    __device__ static __forceinline__ f32x4 run(const uint4& a, const uint4& b, const f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
-
 PSCV_PROF_BUFFER(conv)
-Knob g_conv_small_tiles = {1, KNOB_CONV_SMALL_TILES};   // pscv_set_tuning("conv_small_tiles", 0) forces the large-tile variant
-Knob g_conv_small_nt = {0, KNOB_CONV_SMALL_NT};         // pscv_set_tuning("conv_small_nt", 1|2|4): 16-channel output tiles per workgroup of the small-volume / stride-2 variants (0 = default choice)
-Knob g_conv_tall64 = {1, KNOB_SPARE2};                  // pscv_set_tuning("conv_tall64", 0): 64-channel stride-1 layers back on 4x4x16 tiles; 2: 4x8x16 at any size
 
 struct ConvArgs {
     const uint16_t* in;
@@ -150,11 +130,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
     PSCV_PROF_BEGIN
 
     // ---- which tile (XCD-aware bijective remap: each XCD gets a contiguous run of tiles) ----
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int tw_i = fast_divmod(wg, a.ntw, a.mg_tw);
     const int th_i = fast_divmod(wg, a.nth, a.mg_th);
     const int td_i = fast_divmod(wg, a.ntd, a.mg_td);

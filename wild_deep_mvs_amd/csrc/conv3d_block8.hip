@@ -20,21 +20,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(4))) float b8_f32x4;
-typedef __attribute__((ext_vector_type(8))) __bf16 b8_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 b8_f16x8;
-template <typename H> struct B8Mfma;
-template <> struct B8Mfma<bf16_t> {
-    __device__ static __forceinline__ b8_f32x4 run(const uint4& a, const uint4& b, const b8_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8_bf16x8, a), __builtin_bit_cast(b8_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct B8Mfma<f16_t> {
-    __device__ static __forceinline__ b8_f32x4 run(const uint4& a, const uint4& b, const b8_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(b8_f16x8, a), __builtin_bit_cast(b8_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 struct Block8Args {
     const uint16_t* in;
     const uint16_t* wpk1;    // PSCV_CONV_S1P8 packing of layer 1: [9 taps][64 lanes][8]
@@ -65,9 +50,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
     unsigned char* const xs = smem;                                   // x ring
     unsigned char* const ts = smem + B8_NSLOT * B8_XSLOT;             // t ring
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q + 1) : r_ * (q + 1) + (xcd - r_) * q) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -158,11 +141,11 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
         const int j = k - 2;
         const unsigned char* sp1 = xs + ((2 * k + g) & (B8_NSLOT - 1)) * B8_XSLOT + (rb1 * B8_XW + n) * 16;
         const unsigned char* sp2 = ts + ((2 * j + g) & (B8_NSLOT - 1)) * B8_TSLOT + (rb2 * B8_TCOLS + n) * 16;
-        b8_f32x4 a1[NR1], a2[2];
+        f32x4 a1[NR1], a2[2];
 #pragma unroll
-        for (int i = 0; i < NR1; ++i) a1[i] = b8_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NR1; ++i) a1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 0; i < 2; ++i) a2[i] = b8_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < 2; ++i) a2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (l1) {
 #pragma unroll
             for (int q = 0; q < NR1 + 2; ++q)                        // input row rb1 + q
@@ -172,7 +155,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
 #pragma unroll
                     for (int kh = 0; kh < 3; ++kh) {
                         const int i = q - kh;
-                        if (i >= 0 && i < NR1) a1[i] = B8Mfma<H>::run(wf1[kh * 3 + kw], xf, a1[i]);
+                        if (i >= 0 && i < NR1) a1[i] = Mfma<H>::run(wf1[kh * 3 + kw], xf, a1[i]);
                     }
                 }
         }
@@ -185,7 +168,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
 #pragma unroll
                     for (int kh = 0; kh < 3; ++kh) {
                         const int i = q - kh;
-                        if (i >= 0 && i < 2) a2[i] = B8Mfma<H>::run(wf2[kh * 3 + kw], xf, a2[i]);
+                        if (i >= 0 && i < 2) a2[i] = Mfma<H>::run(wf2[kh * 3 + kw], xf, a2[i]);
                     }
                 }
         }
@@ -248,8 +231,6 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
 }
 
 }  // namespace pscv
-
-pscv::Knob g_block8_slots = {0, pscv::KNOB_SPARE3};   // pscv_set_tuning("block8_slots", n): workgroup slots the depth chunks are sized for
 
 extern "C" int pscv_conv3d_block8(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed1, const float* scale1,
                                   const float* bias1, const float* floor1, int epi1, const uint16_t* packed2, const float* scale2,

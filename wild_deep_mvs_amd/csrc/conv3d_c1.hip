@@ -22,22 +22,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 c1_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 c1_f16x8;
-typedef __attribute__((ext_vector_type(4))) float c1_f32x4;
-
-template <typename H> struct C1Mfma;
-template <> struct C1Mfma<bf16_t> {
-    __device__ static __forceinline__ c1_f32x4 run(const uint4& a, const uint4& b, const c1_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(c1_bf16x8, a), __builtin_bit_cast(c1_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct C1Mfma<f16_t> {
-    __device__ static __forceinline__ c1_f32x4 run(const uint4& a, const uint4& b, const c1_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(c1_f16x8, a), __builtin_bit_cast(c1_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 struct C1Args {
     const uint16_t* in;
     const uint4* wpk;        // [NSTEPS][64 lanes] x 8 halves (A fragments)
@@ -78,9 +62,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_kernel(const C1Args a) {
     constexpr int MAXP = C1_NB_MAX * C1_P + 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [(6 nb + 2)][C1_PS][VB]
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q_ = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_kernel(const C1Args a) {
         const int d0 = dbeg + blk * C1_P;
         if (d0 >= a.D) break;
         const unsigned char* sp = smem + blk * (C1_P * C1_PS * VB) + lane_off;
-        c1_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < NSTEPS; ++s) {
             // step s = (q, tap): lane group g reads plane 4 (g >> 1) + 2 q + (g & 1) (C_in 8) or 4 (g >> 1) + q
@@ -183,8 +165,8 @@ __global__ __launch_bounds__(256) void conv3d_c1_kernel(const C1Args a) {
             const int off = (((CIN == 8) ? 2 * q : q) * C1_PS + (t / 3) * C1_BW + (t % 3)) * VB;
             const uint4 x0 = *reinterpret_cast<const uint4*>(sp + off);
             const uint4 x1 = *reinterpret_cast<const uint4*>(sp + off + 16 * VB);
-            acc0 = C1Mfma<H>::run(wf[s], x0, acc0);
-            acc1 = C1Mfma<H>::run(wf[s], x1, acc1);
+            acc0 = Mfma<H>::run(wf[s], x0, acc0);
+            acc1 = Mfma<H>::run(wf[s], x1, acc1);
         }
         PSCV_STAMP(3)
         // ---- epilogue: lane (n, g) holds rows 4g..4g+3 = output planes d0 + 4g + r of pixel n ----
@@ -259,9 +241,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
     constexpr int VB = 16, NSTEPS = 18, PV = C1_BH * C1_BW, PSB = C1_PS * VB;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [16 slots][C1_PS][16 B]
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q_ = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -340,7 +320,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
         const unsigned char* spB = smem + ((C1_P * k + pA + 2) & (C1S_NSLOT - 1)) * PSB + inplane;
         // four accumulation chains of 9 dependent MFMAs (two column tiles x the two plane sets) instead of two of 18: the block is a
         // latency chain (one workgroup per CU still needs ~3.5 K cycles per block), so the chain length counts
-        c1_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc0b = {0.f, 0.f, 0.f, 0.f}, acc1b = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc0b = {0.f, 0.f, 0.f, 0.f}, acc1b = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int off = ((t / 3) * C1_BW + (t % 3)) * VB;
@@ -348,10 +328,10 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
             const uint4 x1 = *reinterpret_cast<const uint4*>(spA + off + 16 * VB);
             const uint4 x2 = *reinterpret_cast<const uint4*>(spB + off);
             const uint4 x3 = *reinterpret_cast<const uint4*>(spB + off + 16 * VB);
-            acc0 = C1Mfma<H>::run(wf[t], x0, acc0);
-            acc1 = C1Mfma<H>::run(wf[t], x1, acc1);
-            acc0b = C1Mfma<H>::run(wf[9 + t], x2, acc0b);
-            acc1b = C1Mfma<H>::run(wf[9 + t], x3, acc1b);
+            acc0 = Mfma<H>::run(wf[t], x0, acc0);
+            acc1 = Mfma<H>::run(wf[t], x1, acc1);
+            acc0b = Mfma<H>::run(wf[9 + t], x2, acc0b);
+            acc1b = Mfma<H>::run(wf[9 + t], x3, acc1b);
         }
         acc0 += acc0b;
         acc1 += acc1b;
@@ -560,8 +540,6 @@ static int c1_launch(const C1Args& a, long nblk, hipStream_t st) {
 
 }  // namespace pscv
 
-pscv::Knob g_c1_nb = {0, pscv::KNOB_C1_NB};
-pscv::Knob g_c1_sweep = {1, pscv::KNOB_C1_SWEEP};   // pscv_set_tuning("c1_sweep", 0): always the brick variant; 2: the depth sweep at any depth
 PSCV_PROF_EXPORT(c1)
 
 // depth / part / merged outputs non-null: the fused tail (pscv_prob_softargmin); returns 1 when the layer does not get the depth-sweep

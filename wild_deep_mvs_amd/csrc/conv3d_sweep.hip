@@ -21,28 +21,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 sw_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 sw_f16x8;
-typedef __attribute__((ext_vector_type(4))) float sw_f32x4;
-
-template <typename H> struct SwMfma;
-template <> struct SwMfma<bf16_t> {
-    __device__ static __forceinline__ sw_f32x4 run(const uint4& a, const uint4& b, const sw_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(sw_bf16x8, a), __builtin_bit_cast(sw_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct SwMfma<f16_t> {
-    __device__ static __forceinline__ sw_f32x4 run(const uint4& a, const uint4& b, const sw_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(sw_f16x8, a), __builtin_bit_cast(sw_f16x8, b), c, 0, 0, 0);
-    }
-};
-
-Knob g_sweep_dc = {0, KNOB_SWEEP_DC};     // pscv_set_tuning("sweep_dc", n): depth planes per workgroup sweep (0 = heuristic)
-Knob g_sweepc_pd = {0, KNOB_SWEEPC_PD};    // pscv_set_tuning("sweepc_pd", 1..3): prefetch distance (iterations) of the narrow-input sweep (0 = 1)
-Knob g_sweepc_slots = {0, KNOB_SWEEPC_SLOTS}; // pscv_set_tuning("sweepc_slots", n): resident-workgroup target of the narrow-input sweep (0 = 768)
-Knob g_sweep_th16 = {0, KNOB_SWEEP_TH16};   // pscv_set_tuning("sweep_th16", 1) selects the 16-row / 512-thread tile variant (measured
-                        // 116 us vs 107 us for 8-row tiles at the headline size: one workgroup per CU hides less latency)
-
 struct SweepArgs {
     const uint16_t* in;
     const uint16_t* wpk;     // [4 p_rel][9 taps][64 lanes][8]
@@ -89,9 +67,7 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
     constexpr int R = 2;   // rows (M-tiles) per wave
 
     // ---- work decode (XCD-aware: each XCD gets a contiguous run of (tile, depth-chunk) ids) ----
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q + 1) : r_ * (q + 1) + (xcd - r_) * q) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -191,9 +167,9 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
         __builtin_amdgcn_sched_barrier(0);      // both planes are requested HERE (the scheduler otherwise sinks the second below the MFMAs)
         PSCV_STAMP(1)
 
-        sw_f32x4 acc[R];
+        f32x4 acc[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = sw_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < R; ++r) acc[r] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             constexpr int SL = (RING + 4 * SW_NSLOT) % SW_NSLOT;
@@ -205,7 +181,7 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const uint4 xf = *reinterpret_cast<const uint4*>(sp + boff[r + kh][kw]);
-                        acc[r] = SwMfma<H>::run(wf[p][kh * 3 + kw], xf, acc[r]);
+                        acc[r] = Mfma<H>::run(wf[p][kh * 3 + kw], xf, acc[r]);
                     }
         }
 
@@ -272,22 +248,7 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
 // {4-11, 16-19, 28-31} (+32); each group gets 16 x-ADJACENT pixels of one row, and with chunk ^= (voxel >> 2) & 3 sixteen
 // consecutive 64-byte voxels fall on the sixteen 16-byte slots of the 256-byte bank row for every tap offset.
 // Weights: the PSCV_CONV_S1P8 packing, gathered (rows 0-7 of p_rel = kd hold kernel slice kd).
-typedef __attribute__((ext_vector_type(16))) float sw_f32x16;
-template <typename H> struct SwMfma32;
-template <> struct SwMfma32<bf16_t> {
-    __device__ static __forceinline__ sw_f32x16 run(const uint4& a, const uint4& b, const sw_f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(sw_bf16x8, a), __builtin_bit_cast(sw_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct SwMfma32<f16_t> {
-    __device__ static __forceinline__ sw_f32x16 run(const uint4& a, const uint4& b, const sw_f32x16& c) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(sw_f16x8, a), __builtin_bit_cast(sw_f16x8, b), c, 0, 0, 0);
-    }
-};
 
-extern Knob g_fuse_c0;
-Knob g_sweep_kdm_pd = {0, KNOB_SWEEP_KDM_PD};    // prefetch distance (planes in flight per workgroup) of the kd-in-rows kernel: 1 (default) or 2
-Knob g_sweep_kdm = {0, KNOB_SWEEP_KDM};      // pscv_set_tuning("sweep_kdm", 1): kd-in-rows kernel for the 32 -> 8 layer; 2: with four workgroups per CU as the chunking target
 constexpr int KM_NSLOT = 3;
 constexpr int KM_PV = 192;                    // 10 x 18 = 180 voxels per plane, padded to a multiple of 16 (swizzle is slot-invariant)
 constexpr int KM_PB = KM_PV * SW_VB;
@@ -308,9 +269,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NLD = KM_NLD;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q + 1) : r_ * (q + 1) + (xcd - r_) * q) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -439,7 +398,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
     }
     __syncthreads();
 
-    sw_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
     uint2 skv = make_uint2(0u, 0u);
@@ -475,7 +434,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
                 for (int t = 0; t < AH; ++t) xb[t] = *reinterpret_cast<const uint4*>(sp + (boff[(t >> 1) / 3][(t >> 1) % 3] ^ ((t & 1) << 5)));
 #pragma unroll
                 for (int t = 0; t < 18; ++t) {
-                    acc = SwMfma32<H>::run(wf[t >> 1][t & 1], xb[t % AH], acc);
+                    acc = Mfma32<H>::run(wf[t >> 1][t & 1], xb[t % AH], acc);
                     if (t + AH < 18) {
                         const int u = t + AH;
                         xb[t % AH] = *reinterpret_cast<const uint4*>(sp + (boff[(u >> 1) / 3][(u >> 1) % 3] ^ ((u & 1) << 5)));
@@ -533,9 +492,7 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
     constexpr int VB = G::VB, CCH = G::CCH, PB = G::PB, CHUNKS = G::CHUNKS, NLD = G::NLD, NM = G::NM;
     constexpr int R = 2;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q + 1) : r_ * (q + 1) + (xcd - r_) * q) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -673,11 +630,11 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
                 fetch(dd + 3 + 2 * PD, pfa[s]);
                 fetch(dd + 4 + 2 * PD, pfb[s]);
 
-                sw_f32x4 acc[NOP][R];
+                f32x4 acc[NOP][R];
 #pragma unroll
                 for (int op = 0; op < NOP; ++op)
 #pragma unroll
-                    for (int r = 0; r < R; ++r) acc[op][r] = sw_f32x4{0.f, 0.f, 0.f, 0.f};
+                    for (int r = 0; r < R; ++r) acc[op][r] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int op = 0; op < NOP; ++op)
 #pragma unroll
@@ -693,7 +650,7 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
 #pragma unroll
                                 for (int r = 0; r < R; ++r) {
                                     const uint4 xf = *reinterpret_cast<const uint4*>(sp + boff[r + kh][kw]);
-                                    acc[op][r] = SwMfma<H>::run(wf[set * 9 + kh * 3 + kw], xf, acc[op][r]);
+                                    acc[op][r] = Mfma<H>::run(wf[set * 9 + kh * 3 + kw], xf, acc[op][r]);
                                 }
                             // 72 MFMAs per iteration: fence the scheduler per tap row, or it hoists the independent LDS reads of all
                             // four (plane, set) blocks and spills ~150 registers

@@ -20,25 +20,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 s2_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 s2_f16x8;
-typedef __attribute__((ext_vector_type(4))) float s2_f32x4;
-
-template <typename H> struct S2Mfma;
-template <> struct S2Mfma<bf16_t> {
-    __device__ static __forceinline__ s2_f32x4 run(const uint4& a, const uint4& b, const s2_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s2_bf16x8, a), __builtin_bit_cast(s2_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct S2Mfma<f16_t> {
-    __device__ static __forceinline__ s2_f32x4 run(const uint4& a, const uint4& b, const s2_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(s2_f16x8, a), __builtin_bit_cast(s2_f16x8, b), c, 0, 0, 0);
-    }
-};
-
-Knob g_conv_s2_sweep = {1, KNOB_CONV_S2_SWEEP};   // pscv_set_tuning("conv_s2_sweep", 0): always the brick kernel; 2: the sweep at any size
-Knob g_s2s_slots = {0, KNOB_S2S_SLOTS};       // pscv_set_tuning("s2s_slots", n): resident-workgroup target that sizes the depth chunks (0 = 768)
-
 struct S2sArgs {
     const uint16_t* in;
     const uint4* wpk;        // [7 steps][nt_total][64 lanes] x 8 halves: the dense S2 packing
@@ -69,9 +50,7 @@ PSCV_PROF_BUFFER(s2s)
 template <typename H, int NT, bool PLAIN>
 __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q_ = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -196,11 +175,11 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
             sl = sl >= S2S_NSLOT ? sl - S2S_NSLOT : sl;
             sb[k] = sl * S2S_PB;
         }
-        s2_f32x4 acc[S2S_R][NT];
+        f32x4 acc[S2S_R][NT];
 #pragma unroll
         for (int r = 0; r < S2S_R; ++r)
 #pragma unroll
-            for (int m = 0; m < NT; ++m) acc[r][m] = s2_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int m = 0; m < NT; ++m) acc[r][m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < S2S_STEPS; ++s) {
             const int base = kd_s[s] == 0 ? sb[0] : (kd_s[s] == 1 ? sb[1] : sb[2]);
@@ -208,7 +187,7 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
             for (int r = 0; r < S2S_R; ++r) {
                 const uint4 xf = *reinterpret_cast<const uint4*>(smem + base + boff[s][r]);
 #pragma unroll
-                for (int m = 0; m < NT; ++m) acc[r][m] = S2Mfma<H>::run(wf[s][m], xf, acc[r][m]);
+                for (int m = 0; m < NT; ++m) acc[r][m] = Mfma<H>::run(wf[s][m], xf, acc[r][m]);
             }
         }
         PSCV_STAMP(2)

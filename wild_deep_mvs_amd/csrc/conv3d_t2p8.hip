@@ -14,22 +14,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 tp_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 tp_f16x8;
-typedef __attribute__((ext_vector_type(4))) float tp_f32x4;
-
-template <typename H> struct TpMfma;
-template <> struct TpMfma<bf16_t> {
-    __device__ static __forceinline__ tp_f32x4 run(const uint4& a, const uint4& b, const tp_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tp_bf16x8, a), __builtin_bit_cast(tp_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct TpMfma<f16_t> {
-    __device__ static __forceinline__ tp_f32x4 run(const uint4& a, const uint4& b, const tp_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(tp_f16x8, a), __builtin_bit_cast(tp_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 struct Tp8Args {
     const uint16_t* in;
     const uint16_t* wpk;     // [9 steps][64 lanes][8]; step order: (pd,ph) = (0,0) | (0,1): th 0,1 | (1,0): td 0,1 | (1,1): td,th
@@ -55,9 +39,7 @@ __global__ __launch_bounds__(256) void conv3d_t2p8_kernel(const Tp8Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[TP_BD * TP_BH * TP_BW * TP_VS];
     constexpr int NVOX = TP_BD * TP_BH * TP_BW;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3, q = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q + 1) : r_ * (q + 1) + (xcd - r_) * q) + slot;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int tw_i = fast_divmod(wg, a.ntw, a.mg_tw);
     const int th_i = fast_divmod(wg, a.nth, a.mg_th);
     const int td_i = fast_divmod(wg, a.ntd, a.mg_td);
@@ -159,14 +141,14 @@ __global__ __launch_bounds__(256) void conv3d_t2p8_kernel(const Tp8Args a) {
             float yf[2][4];
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph) {
-                tp_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int sd = 0; sd <= pd; ++sd)
 #pragma unroll
                     for (int sh = 0; sh <= ph; ++sh) {
                         const int od = (pd && sd == 0) ? 1 : 0, oh = (ph && sh == 0) ? 1 : 0;   // sub 0 = kernel index 0 at input offset +1
                         const uint4 xf = *reinterpret_cast<const uint4*>(smem + (((td + od) * TP_BH + th + oh) * TP_BW) * TP_VS + lane_off);
-                        acc = TpMfma<H>::run(wf[step], xf, acc);
+                        acc = Mfma<H>::run(wf[step], xf, acc);
                         ++step;
                     }
                 const uint2 sv = skv[i][pd * 2 + ph];

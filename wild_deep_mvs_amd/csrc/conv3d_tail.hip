@@ -28,22 +28,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 tl_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 tl_f16x8;
-typedef __attribute__((ext_vector_type(4))) float tl_f32x4;
-
-template <typename H> struct TlMfma;
-template <> struct TlMfma<bf16_t> {
-    __device__ static __forceinline__ tl_f32x4 run(const uint4& a, const uint4& b, const tl_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tl_bf16x8, a), __builtin_bit_cast(tl_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct TlMfma<f16_t> {
-    __device__ static __forceinline__ tl_f32x4 run(const uint4& a, const uint4& b, const tl_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(tl_f16x8, a), __builtin_bit_cast(tl_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 struct TailArgs {
     const uint16_t* in;       // [B, Di, Hi, Wi, in_cs], channels [in_co, in_co + 16)
     const uint4* w_up;        // T2P8 packing of the [16, 8, 3, 3, 3] transposed weight: [9 steps][64 lanes]
@@ -82,8 +66,6 @@ constexpr int TL_LDS = TL_NSLOT * TL_PB + TL_ISLOT * TL_IPB + TL_DEPTHS * 4;
 constexpr int TL_P = 6;                              // output planes per consume block
 static_assert(TL_LDS <= 80 * 1024, "two workgroups per CU");
 
-Knob g_tail_nbk = {0, KNOB_TAIL_NBK};                  // pscv_set_tuning("tail_nbk", n): 6-plane blocks per depth chunk (0 = default heuristic)
-
 // UP_POST: the transposed layer has a ReLU after the skip add; HD_CLAMP: the head has any ReLU.  MVSNet's tail has neither: the
 // <H, false, false> instantiation carries no dead clamp instructions (a NaN-propagating clamp is a compare + select per value).
 template <typename H, bool UP_POST, bool HD_CLAMP, bool FUSE>
@@ -92,9 +74,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
     unsigned char* const ring = smem;                           // u11 planes
     unsigned char* const iring = smem + TL_NSLOT * TL_PB;       // input planes
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot_ = bid >> 3, q_ = nwg >> 3, r_ = nwg & 7;
-    int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + slot_;
+    int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int dci = fast_divmod(wg, a.ndc, a.mg_dc);
     const int twi = fast_divmod(wg, a.ntw, a.mg_tw);
     const int thi = fast_divmod(wg, a.nth, a.mg_th);
@@ -193,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
     // i + 1).  Output row of (r, ph): 2 (ih0 + r) + ph = brick row 2 r + ph - 1 -- a COMPILE-TIME constant per unrolled unit (r and
     // the wave's classes are template constants of its code path), so rows outside the brick cost nothing.
     auto cls_plane = [&](int i, int cls) { return (cls >> 1) ? 2 * i + 1 : 2 * i + 2; };
-    auto epilogue = [&](const tl_f32x4& acc, int op, int rb, const uint2& sv) {     // rb in [0, TL_BR)
+    auto epilogue = [&](const f32x4& acc, int op, int rb, const uint2& sv) {     // rb in [0, TL_BR)
         const int orow = h0 - 1 + rb;
         float y[4];
 #pragma unroll
@@ -227,23 +207,23 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
         const unsigned char* pi = iring + islot_i * TL_IPB + pl_off;       // input plane i
         const unsigned char* pj = iring + islot_i1 * TL_IPB + pl_off;      // input plane i + 1
         constexpr int ro0 = R * TL_IC * TL_VS, ro1 = (R + 1) * TL_IC * TL_VS;
-        tl_f32x4 acca, accb;
-        const tl_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acca, accb;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         if (TA) {
             const uint4 xj0 = *reinterpret_cast<const uint4*>(pj + ro0), xj1 = *reinterpret_cast<const uint4*>(pj + ro1);
             const uint4 xi0 = *reinterpret_cast<const uint4*>(pi + ro0), xi1 = *reinterpret_cast<const uint4*>(pi + ro1);
-            acca = TlMfma<H>::run(wu[0], xj0, z);
-            accb = TlMfma<H>::run(wu[1], xj1, z);
-            accb = TlMfma<H>::run(wu[2], xj0, accb);
-            accb = TlMfma<H>::run(wu[3], xi1, accb);
-            accb = TlMfma<H>::run(wu[4], xi0, accb);
+            acca = Mfma<H>::run(wu[0], xj0, z);
+            accb = Mfma<H>::run(wu[1], xj1, z);
+            accb = Mfma<H>::run(wu[2], xj0, accb);
+            accb = Mfma<H>::run(wu[3], xi1, accb);
+            accb = Mfma<H>::run(wu[4], xi0, accb);
         } else {
             const uint4 xj0 = *reinterpret_cast<const uint4*>(pj + ro0), xj1 = *reinterpret_cast<const uint4*>(pj + ro1);
             const uint4 xi0 = *reinterpret_cast<const uint4*>(pi + ro0);
-            acca = TlMfma<H>::run(wu[0], xj1, z);
-            acca = TlMfma<H>::run(wu[1], xj0, acca);
-            accb = TlMfma<H>::run(wu[2], xj0, z);
-            accb = TlMfma<H>::run(wu[3], xi0, accb);
+            acca = Mfma<H>::run(wu[0], xj1, z);
+            acca = Mfma<H>::run(wu[1], xj0, acca);
+            accb = Mfma<H>::run(wu[2], xj0, z);
+            accb = Mfma<H>::run(wu[3], xi0, accb);
         }
         if (rba >= 0 && rba < TL_BR) epilogue(acca, cls_plane(i, CA), rba, sk[0]);
         if (rbb >= 0 && rbb < TL_BR) epilogue(accb, cls_plane(i, CB), rbb, sk[1]);
@@ -349,7 +329,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
             const int tr = 2 * wave + rr;
             const unsigned char* spA = ring + ((TL_P * k + pA) & (TL_NSLOT - 1)) * TL_PB + (tr * TL_BC + n + 1) * 16;
             const unsigned char* spB = ring + ((TL_P * k + pA + 2) & (TL_NSLOT - 1)) * TL_PB + (tr * TL_BC + n + 1) * 16;
-            tl_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc0b = {0.f, 0.f, 0.f, 0.f}, acc1b = {0.f, 0.f, 0.f, 0.f};
+            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc0b = {0.f, 0.f, 0.f, 0.f}, acc1b = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int off = ((t / 3) * TL_BC + (t % 3)) * 16;
@@ -357,10 +337,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
                 const uint4 x1 = *reinterpret_cast<const uint4*>(spA + off + 16 * 16);
                 const uint4 x2 = *reinterpret_cast<const uint4*>(spB + off);
                 const uint4 x3 = *reinterpret_cast<const uint4*>(spB + off + 16 * 16);
-                acc0 = TlMfma<H>::run(wh[t], x0, acc0);
-                acc1 = TlMfma<H>::run(wh[t], x1, acc1);
-                acc0b = TlMfma<H>::run(wh[9 + t], x2, acc0b);
-                acc1b = TlMfma<H>::run(wh[9 + t], x3, acc1b);
+                acc0 = Mfma<H>::run(wh[t], x0, acc0);
+                acc1 = Mfma<H>::run(wh[t], x1, acc1);
+                acc0b = Mfma<H>::run(wh[9 + t], x2, acc0b);
+                acc1b = Mfma<H>::run(wh[9 + t], x3, acc1b);
             }
             acc0 += acc0b;
             acc1 += acc1b;

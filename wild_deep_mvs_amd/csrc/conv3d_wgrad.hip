@@ -20,24 +20,7 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 wg_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 wg_f16x8;
-typedef __attribute__((ext_vector_type(4))) float wg_f32x4;
-
-template <typename H> struct WMfma;
-template <> struct WMfma<bf16_t> {
-    __device__ static __forceinline__ wg_f32x4 run(const uint4& a, const uint4& b, const wg_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wg_bf16x8, a), __builtin_bit_cast(wg_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct WMfma<f16_t> {
-    __device__ static __forceinline__ wg_f32x4 run(const uint4& a, const uint4& b, const wg_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wg_f16x8, a), __builtin_bit_cast(wg_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 #ifdef PSCV_ABLATE
-extern Knob g_fuse_c0;      // warp_cost.hip
 #endif
 struct WgradArgs {
     const uint16_t* p;
@@ -91,23 +74,23 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
     const int at = blockIdx.y / nbg, bg = blockIdx.y % nbg;
     const int a0 = at * 16 * NA, b0 = bg * 16 * NB;
 
-    wg_f32x4 acc[7][NB];
+    f32x4 acc[7][NB];
 #pragma unroll
     for (int ti = 0; ti < 7; ++ti)
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[ti][nb] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < NB; ++nb) acc[ti][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     // stride 1: a wave owns whole (tz, ty, b-tile) units -- unit u = wave + 4 i -> pair u / NB, b-tile u % NB -- and runs their three
     // x-taps off ONE pair of aligned reads (two ds_read_b128 + four byte-align ops per three MFMAs)
     constexpr int NPAIR = G::P2D ? 3 : 9, NU = NPAIR * NB, NUW = (NU + 3) / 4;
     // (single-plane mode with 64 a-channels: NA = 4 a-tiles share ONE staging of Q -- as (a-tile, b-group) workgroups every Q tile was
     //  transposed four times)
-    wg_f32x4 accu[NA][G::ONE ? NUW : 1][3];
+    f32x4 accu[NA][G::ONE ? NUW : 1][3];
 #pragma unroll
     for (int m = 0; m < NA; ++m)
 #pragma unroll
         for (int i = 0; i < (G::ONE ? NUW : 1); ++i)
 #pragma unroll
-            for (int tx = 0; tx < 3; ++tx) accu[m][i][tx] = wg_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int tx = 0; tx < 3; ++tx) accu[m][i][tx] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         int t = tile;
@@ -253,9 +236,9 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
 #pragma unroll
                         for (int m = 0; m < NA; ++m) {
                             const uint4 afm = m == 0 ? af : *reinterpret_cast<const uint4*>(p_lds + (m * 16 + n) * G::PAS + ((zl * TY + yl) * 16 + x8 * 8) * 2);
-                            accu[m][i][0] = WMfma<H>::run(afm, c0, accu[m][i][0]);
-                            accu[m][i][1] = WMfma<H>::run(afm, b1, accu[m][i][1]);
-                            accu[m][i][2] = WMfma<H>::run(afm, b2, accu[m][i][2]);
+                            accu[m][i][0] = Mfma<H>::run(afm, c0, accu[m][i][0]);
+                            accu[m][i][1] = Mfma<H>::run(afm, b1, accu[m][i][1]);
+                            accu[m][i][2] = Mfma<H>::run(afm, b2, accu[m][i][2]);
                         }
                     }
                 }
@@ -269,7 +252,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
                         const uint4 bf = *reinterpret_cast<const uint4*>(qrow + (nb * 16 + n) * G::QBS);
-                        acc[ti][nb] = WMfma<H>::run(af, bf, acc[ti][nb]);
+                        acc[ti][nb] = Mfma<H>::run(af, bf, acc[ti][nb]);
                     }
                 }
             }

@@ -26,22 +26,6 @@
 
 namespace pscv {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 wd_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 wd_f16x8;
-typedef __attribute__((ext_vector_type(4))) float wd_f32x4;
-
-template <typename H> struct WdMfma;
-template <> struct WdMfma<bf16_t> {
-    __device__ static __forceinline__ wd_f32x4 run(const uint4& a, const uint4& b, const wd_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(wd_bf16x8, a), __builtin_bit_cast(wd_bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct WdMfma<f16_t> {
-    __device__ static __forceinline__ wd_f32x4 run(const uint4& a, const uint4& b, const wd_f32x4& c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(wd_f16x8, a), __builtin_bit_cast(wd_f16x8, b), c, 0, 0, 0);
-    }
-};
-
 struct WideArgs {
     const uint16_t* in;
     const uint4* wpk;        // kind S1 packing: [k-step][output tile][64 lanes] x 8 halves
@@ -61,7 +45,6 @@ struct WideArgs {
 constexpr int WD_TD = 4, WD_TH = 4, WD_BD = 6, WD_BH = 6, WD_BW = 18, WD_NVOX = WD_BD * WD_BH * WD_BW;
 
 PSCV_PROF_BUFFER(wide)
-Knob g_conv_wide = {1, KNOB_CONV_WIDE};       // pscv_set_tuning("conv_wide", 0): these layers back on the brick kernel (A/B runs, bit comparison)
 
 // ---- the kernel ------------------------------------------------------------------------------------------------------------------
 // One workgroup per CU walks its share of the tiles.  With one tile per workgroup (this file's first form, round 5) the phase stamps
@@ -111,9 +94,8 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
     const int G = gridDim.x, bid = blockIdx.x;
     int t_cur, t_end, t_step;
     if ((G & 7) == 0) {
-        const int xcd = bid & 7, q = ntiles >> 3, r_ = ntiles & 7;
-        const int base = xcd < r_ ? xcd * (q + 1) : r_ * (q + 1) + (xcd - r_) * q;
-        t_step = G >> 3; t_cur = base + (bid >> 3); t_end = base + q + (xcd < r_ ? 1 : 0);
+        const int first = xcd_run(bid & 7, ntiles, t_end);
+        t_step = G >> 3; t_cur = first + (bid >> 3);
     } else { t_step = G; t_cur = bid; t_end = ntiles; }
     if (t_cur >= t_end) return;
 
@@ -233,11 +215,11 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
 
     for (;;) {
         const bool have_next = t_next < t_end;                  // (workgroup-uniform)
-        wd_f32x4 acc[2][NT];
+        f32x4 acc[2][NT];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int m = 0; m < NT; ++m) acc[i][m] = wd_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int m = 0; m < NT; ++m) acc[i][m] = f32x4{0.f, 0.f, 0.f, 0.f};
         const int ow = T.t0w + n;
         const bool col_ok = ow < a.W;
         uint2 skv[2][NT];
@@ -270,7 +252,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int m = 0; m < NT; ++m) acc[i][m] = WdMfma<H>::run(af[st & 1][m], xf[st & 1][i], acc[i][m]);
+                    for (int m = 0; m < NT; ++m) acc[i][m] = Mfma<H>::run(af[st & 1][m], xf[st & 1][i], acc[i][m]);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }

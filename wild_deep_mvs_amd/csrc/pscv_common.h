@@ -27,11 +27,40 @@ struct Knob {
     operator int() const;
     void set(int v) { __atomic_store_n(&process, v, __ATOMIC_RELAXED); }
 };
-enum { KNOB_WARP_LPV, KNOB_WARP_PPD, KNOB_WARP_TILED, KNOB_WARP_Q2, KNOB_CONV_SMALL_TILES, KNOB_SWEEP_TH16, KNOB_SWEEP_DC,
-       KNOB_SWEEPC_SLOTS, KNOB_SWEEPC_PD, KNOB_C1_NB, KNOB_C1_SWEEP, KNOB_WARP_BWD_DIRECT, KNOB_CONV_S2_SWEEP, KNOB_S2S_SLOTS,
-       KNOB_WARP_TILE, KNOB_FUSE_C0, KNOB_SPARE1, KNOB_SPARE2, KNOB_SPARE3, KNOB_SPARE4, KNOB_SWEEP_KDM, KNOB_SWEEP_KDM_PD, KNOB_WARP_LDS_PAD, KNOB_WARP_GC_LDS, KNOB_TAIL_NBK, KNOB_CONV_WIDE, KNOB_CONV_SMALL_NT, KNOB_COUNT };
-bool knob_thread_value(int id, int* v);             // this thread's override of slot id, if one is set
-void knob_thread_set(int id, int v, bool enable);
+// THE knob table: X(key of pscv_set_tuning, C++ symbol, default).  A new knob is one row here and one entry in the key list of
+// include/pscv.h (which says what the values mean; tests/test_host_cpu.py holds the two lists against each other).  The id enum,
+// the definitions, the name lookup and the setters are made from this list in pscv_host.cpp; the declarations right below.
+#define PSCV_KNOB_TABLE(X)                      \
+    X("warp_q2", g_warp_q2, 1)                  \
+    X("warp_lpv", g_warp_lpv_override, 0)       \
+    X("warp_ppd", g_warp_ppd_override, 0)       \
+    X("warp_tiled", g_warp_tiled, 1)            \
+    X("warp_tile", g_warp_tile, 0)              \
+    X("warp_gc_lds", g_warp_gc_lds, 1)          \
+    X("warp_lds_pad", g_warp_lds_pad, 0)        \
+    X("warp_bwd_direct", g_warp_bwd_direct, 0)  \
+    X("sweep_dc", g_sweep_dc, 0)                \
+    X("sweepc_slots", g_sweepc_slots, 0)        \
+    X("sweepc_pd", g_sweepc_pd, 0)              \
+    X("sweep_th16", g_sweep_th16, 0)            \
+    X("sweep_kdm", g_sweep_kdm, 0)              \
+    X("sweep_kdm_pd", g_sweep_kdm_pd, 0)        \
+    X("c1_sweep", g_c1_sweep, 1)                \
+    X("c1_nb", g_c1_nb, 0)                      \
+    X("conv_s2_sweep", g_conv_s2_sweep, 1)      \
+    X("s2s_slots", g_s2s_slots, 0)              \
+    X("block8_slots", g_block8_slots, 0)        \
+    X("conv2d_wlds", g_conv2d_wlds, 1)          \
+    X("conv_wide", g_conv_wide, 1)              \
+    X("conv_tall64", g_conv_tall64, 1)          \
+    X("conv_small_tiles", g_conv_small_tiles, 1) \
+    X("conv_small_nt", g_conv_small_nt, 0)      \
+    X("tail_nbk", g_tail_nbk, 0)                \
+    X("softargmin_small", g_softargmin_small, 1) \
+    X("fuse_c0", g_fuse_c0, 0)
+#define PSCV_KNOB_DECLARE(key, sym, def) extern Knob sym;
+PSCV_KNOB_TABLE(PSCV_KNOB_DECLARE)
+#undef PSCV_KNOB_DECLARE
 
 #define PSCV_CHECK_ARG(cond, ...)          \
     do {                                   \
@@ -90,6 +119,23 @@ __device__ __forceinline__ int fast_divmod(int& x, int d, unsigned mg) {
     if (r < 0) { --q; r += d; }
     x = (int)q;
     return r;
+}
+
+// ---- workgroup -> work item, XCD-aware --------------------------------------------------------------------------------
+// The hardware deals workgroups round-robin over the 8 XCDs (workgroup `bid` runs on XCD bid % 8) and each XCD has its own L2.
+// Handing out work items in blockIdx order would put neighbouring tiles -- which share halo rows, source texels and weights --
+// on eight different L2s; instead XCD k takes a CONTIGUOUS run of the n items (the first n % 8 XCDs one item more), so
+// consecutive tiles meet in one L2.  xcd_run: XCD `xcd`'s run [first, end); xcd_remap: the bijection for a grid of one workgroup
+// per item (an XCD's `bid >> 3`-th workgroup takes the run's `bid >> 3`-th item).
+__device__ __forceinline__ int xcd_run(int xcd, int n, int& end) {
+    const int q = n >> 3, r = n & 7;
+    const int first = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+    end = first + q + (xcd < r ? 1 : 0);
+    return first;
+}
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    int end;
+    return xcd_run(bid & 7, nwg, end) + (bid >> 3);
 }
 
 // ---- bf16 <-> fp32 (round to nearest even, same as torch's .to(bfloat16)) ----
@@ -182,6 +228,36 @@ __device__ __forceinline__ float clamp_lo(float x, float lo) { return relu_floor
 struct bf16_t { uint16_t bits; };
 struct f16_t { uint16_t bits; };
 static_assert(sizeof(bf16_t) == 2 && sizeof(f16_t) == 2, "16-bit storage");
+
+// ---- MFMA: operands are 8 x 16-bit per lane in a uint4, fp32 accumulate ----
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+// one v_mfma_f32_16x16x32_{bf16,f16}: D[16 x 16] += A[16 x 32] * B[32 x 16]
+template <typename H> struct Mfma;
+template <> struct Mfma<bf16_t> {
+    __device__ static __forceinline__ f32x4 run(const uint4& a, const uint4& b, const f32x4& c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
+template <> struct Mfma<f16_t> {
+    __device__ static __forceinline__ f32x4 run(const uint4& a, const uint4& b, const f32x4& c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+};
+// one v_mfma_f32_32x32x16_{bf16,f16}: D[32 x 32] += A[32 x 16] * B[16 x 32]
+template <typename H> struct Mfma32;
+template <> struct Mfma32<bf16_t> {
+    __device__ static __forceinline__ f32x16 run(const uint4& a, const uint4& b, const f32x16& c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
+template <> struct Mfma32<f16_t> {
+    __device__ static __forceinline__ f32x16 run(const uint4& a, const uint4& b, const f32x16& c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+};
 
 // 8 consecutive channels of one texel / voxel
 struct f32x8 { float v[8]; };

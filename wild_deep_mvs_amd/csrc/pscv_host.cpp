@@ -1,4 +1,4 @@
-// Host-only parts of the pscv C ABI: error channel, version, conv3d weight packing.
+// Host-only parts of the pscv C ABI: error channel, version, tuning knobs, conv3d weight packing.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -79,24 +79,71 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-static thread_local int g_knob_tl[KNOB_COUNT];
-static thread_local unsigned g_knob_tl_mask = 0;
+// ---- tuning knobs: everything that pscv_common.h's PSCV_KNOB_TABLE does not declare itself ----
+#define PSCV_KNOB_ID(key, sym, def) KNOB_##sym,
+enum { PSCV_KNOB_TABLE(PSCV_KNOB_ID) KNOB_COUNT };
+#undef PSCV_KNOB_ID
+#define PSCV_KNOB_DEFINE(key, sym, def) Knob sym = {def, KNOB_##sym};
+PSCV_KNOB_TABLE(PSCV_KNOB_DEFINE)
+#undef PSCV_KNOB_DEFINE
 
-bool knob_thread_value(int id, int* v) {
-    if (!(g_knob_tl_mask >> id & 1u)) return false;
-    *v = g_knob_tl[id];
-    return true;
-}
-void knob_thread_set(int id, int v, bool enable) {
-    g_knob_tl[id] = v;
-    g_knob_tl_mask = enable ? (g_knob_tl_mask | 1u << id) : (g_knob_tl_mask & ~(1u << id));
-}
+static thread_local int g_knob_tl[KNOB_COUNT];      // this thread's overrides (pscv_set_tuning_thread) ...
+static thread_local unsigned g_knob_tl_mask = 0;    // ... and which of them are set
+static_assert(KNOB_COUNT <= 32, "one mask bit per knob");
+
 Knob::operator int() const {
-    int v;
-    return knob_thread_value(id, &v) ? v : __atomic_load_n(&process, __ATOMIC_RELAXED);
+    return (g_knob_tl_mask >> id & 1u) ? g_knob_tl[id] : __atomic_load_n(&process, __ATOMIC_RELAXED);
+}
+
+struct KnobRow { const char* name; Knob* k; int def; };
+static const KnobRow* find_knob(const char* fn, const char* key) {      // nullptr, with the error set under the caller's name, if none
+#define PSCV_KNOB_ROW(key, sym, def) {key, &sym, def},
+    static const KnobRow table[] = {PSCV_KNOB_TABLE(PSCV_KNOB_ROW)};
+#undef PSCV_KNOB_ROW
+    if (!key) { set_error("%s: null key", fn); return nullptr; }
+    for (const KnobRow& r : table)
+        if (!strcmp(key, r.name)) return &r;
+    set_error("%s: unknown key '%s'", fn, key);
+    return nullptr;
+}
+// What both setters store for `value`; false (error set) where the knob does not take it.
+static bool knob_value(const char* fn, const KnobRow& r, int* value) {
+    if (r.k != &g_warp_tiled) return true;
+    if (*value < 0) *value = r.def;      // -1: back to the default
+    // (3 selected the SLP-packed diagnostic build of the LDS-staged kernel, since removed: refuse it rather than silently measure the
+    //  default kernel under its name)
+    if (*value == 3) { set_error("%s: warp_tiled = 3 (packed diagnostic build) no longer exists", fn); return false; }
+    return true;
 }
 
 }  // namespace pscv
+
+extern "C" int pscv_set_tuning(const char* key, int value) {
+    using namespace pscv;
+    const KnobRow* r = find_knob("pscv_set_tuning", key);
+    if (!r || !knob_value("pscv_set_tuning", *r, &value)) return -1;
+    r->k->set(value);
+    return 0;
+}
+
+extern "C" int pscv_set_tuning_thread(const char* key, int value, int enable) {
+    using namespace pscv;
+    const KnobRow* r = find_knob("pscv_set_tuning_thread", key);
+    if (!r || (enable && !knob_value("pscv_set_tuning_thread", *r, &value))) return -1;     // (dropping an override takes no value)
+    const int id = r->k->id;
+    g_knob_tl[id] = value;
+    g_knob_tl_mask = enable ? (g_knob_tl_mask | 1u << id) : (g_knob_tl_mask & ~(1u << id));
+    return 0;
+}
+
+extern "C" int pscv_get_tuning(const char* key, int* value) {
+    using namespace pscv;
+    PSCV_CHECK_ARG(key && value, "pscv_get_tuning: null argument");
+    const KnobRow* r = find_knob("pscv_get_tuning", key);
+    if (!r) return -1;
+    *value = (int)*r->k;
+    return 0;
+}
 
 extern "C" const char* pscv_last_error(void) { return pscv::g_err; }
 extern "C" int pscv_abi_version(void) { return PSCV_ABI_VERSION; }

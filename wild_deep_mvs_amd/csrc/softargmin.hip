@@ -238,8 +238,6 @@ extern "C" int pscv_softargmin_window(const float* logits, const float* stats, f
     return 0;
 }
 
-pscv::Knob g_softargmin_small = {1, pscv::KNOB_SPARE4};   // pscv_set_tuning("softargmin_small", 0): short depth axes back on the slice kernel
-
 extern "C" int pscv_softargmin(const void* logits, int logit_dtype, const float* depth, long depth_bstride,
                                int depth_per_pixel, float* out_depth, float* out_index, float* out_conf,
                                float* out_entropy, float* out_prob, float* out_partials, int conf_mode, float window,

@@ -39,11 +39,7 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(const WarpBwdArgs A) {
     constexpr int PIXB = C * (int)sizeof(TIn);
     constexpr bool VAR = (COST == PSCV_COST_VARIANCE || COST == PSCV_COST_VARIANCE_CVP);
 
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int pb = wg / a.n_dchunks;
     const int dc = wg - pb * a.n_dchunks;
     const int b = pb / a.npb_batch;
@@ -288,11 +284,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
     __shared__ int mm2[4];                // box of one row group when the tile's box exceeds the patch (sub-passes)
     __shared__ float red_lds[4];
 
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int pb = wg / a.n_dchunks;
     const int dc = wg - pb * a.n_dchunks;
     const int b = pb / a.npb_batch;
@@ -664,8 +656,6 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
     }
 }
 
-Knob g_warp_bwd_direct = {0, KNOB_WARP_BWD_DIRECT};   // pscv_set_tuning("warp_bwd_direct", 1): the one-global-atomic-per-tap kernel (measurement / tests)
-
 template <typename TIn, typename TG, int C>
 static int bwd_tile_launch(WarpBwdArgs& A, int geom, int cost, hipStream_t st) {
     WarpArgs& a = A.w;
@@ -673,7 +663,7 @@ static int bwd_tile_launch(WarpBwdArgs& A, int geom, int cost, hipStream_t st) {
     A.nty = (a.h + BT_TH - 1) / BT_TH;
     a.npb_batch = A.ntx * A.nty;
 #ifdef PSCV_ABLATE
-    { extern Knob g_fuse_c0; a.variant = g_fuse_c0; }
+    a.variant = g_fuse_c0;
 #endif
     a.ppd = BT_PLN;
     a.n_dchunks = (a.D + BT_PLN - 1) / BT_PLN;

@@ -32,13 +32,8 @@ __global__ __launch_bounds__(256, 4) void warp_cost_kernel(const WarpArgs a) {
     constexpr int RQ = (GEOM == PSCV_GEOM_HOMOG) ? 2 : 1;   // float4s of depth-independent ray terms per (view, pixel)
     static_assert(CPL % 8 == 0, "a lane owns whole 8-channel groups");
 
-    // XCD-aware bijective remap: hardware places block `bid` on XCD bid % 8; give XCD k a contiguous
-    // run of work ids (pixel-block major, depth-chunk minor) = a band of reference pixels.
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    // XCD k gets a contiguous run of work ids (pixel-block major, depth-chunk minor) = a band of reference pixels
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int pb = __builtin_amdgcn_readfirstlane(wg / a.n_dchunks);
     const int dc = __builtin_amdgcn_readfirstlane(wg - pb * a.n_dchunks);
 
@@ -240,26 +235,6 @@ __global__ __launch_bounds__(256, 4) void warp_cost_kernel(const WarpArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-static Knob g_warp_lpv_override = {0, KNOB_WARP_LPV};  // 0 = default heuristic; set through pscv_set_tuning("warp_lpv", n)
-static Knob g_warp_ppd_override = {0, KNOB_WARP_PPD};
-static Knob g_warp_gc_lds = {1, KNOB_WARP_GC_LDS};   // 1 (default): group-correlation volumes over per-batch planes on the LDS-staged kernel (warp_gc_lv.hip); 2: per-pixel planes too; 0: quad kernel
-static Knob g_warp_tiled = {1, KNOB_WARP_TILED};     // 1 (default; 2 = the same): the LDS-staged kernel (warp_cost_tiled.hip) where it applies: fp32
-                                 // patches, scalar fp32 blend, same bits as the direct kernels; 0: direct kernels; 4: lane-owns-voxel kernel
-extern Knob g_conv_small_tiles;   // conv3d.hip
-extern Knob g_sweep_th16;         // conv3d_sweep.hip
-extern Knob g_sweep_dc;
-extern Knob g_sweep_kdm;
-extern Knob g_sweep_kdm_pd;
-extern Knob g_sweepc_slots;
-extern Knob g_sweepc_pd;
-}
-extern pscv::Knob g_c1_nb;
-extern pscv::Knob g_c1_sweep;
-namespace pscv {
-extern Knob g_warp_bwd_direct;    // warp_bwd.hip
-extern Knob g_conv_s2_sweep;      // conv3d_sweep_s2.hip
-extern Knob g_s2s_slots;
-static Knob g_warp_q2 = {1, KNOB_WARP_Q2};        // 1: 32-channel 16-bit sweeps use the quad-mapped kernel (warp_cost_q2.hip)
 int warp_cost_q2_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st);
 int warp_cost_tiled_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st);
 // the lane-owns-voxel kernel ("warp_tiled" = 4; warp_cost_lv.hip): variance costs
@@ -346,63 +321,6 @@ static int launch_channels(WarpArgs& a, int C, int geom, int cost, hipStream_t s
 }
 
 }  // namespace pscv
-
-namespace pscv {
-Knob g_warp_tile = {0, KNOB_WARP_TILE};       // warp_cost_tiled.hip variants (measurement)
-Knob g_fuse_c0 = {0, KNOB_FUSE_C0};           // reserved: fused warp -> conv0 experiment
-Knob g_warp_lds_pad = {0, KNOB_WARP_LDS_PAD};       // KiB of LDS the LDS-staged warp kernel requests on top of its need (fewer workgroups per CU)
-extern Knob g_conv2d_wlds;                    // conv2d.hip
-extern Knob g_conv_tall64;                    // conv3d.hip
-extern Knob g_conv_small_nt;                  // conv3d.hip
-extern Knob g_tail_nbk;                       // conv3d_tail.hip
-extern Knob g_conv_wide;                      // conv3d_wide.hip
-}
-extern pscv::Knob g_block8_slots;             // conv3d_block8.hip
-extern pscv::Knob g_softargmin_small;         // softargmin.hip
-namespace pscv {
-static Knob* find_knob(const char* key) {
-    static const struct { const char* name; Knob* k; } table[] = {
-        {"warp_lpv", &g_warp_lpv_override}, {"warp_ppd", &g_warp_ppd_override}, {"conv_small_tiles", &g_conv_small_tiles},
-        {"warp_tiled", &g_warp_tiled}, {"warp_gc_lds", &g_warp_gc_lds}, {"warp_q2", &g_warp_q2}, {"c1_nb", &g_c1_nb}, {"c1_sweep", &g_c1_sweep},
-        {"sweep_th16", &g_sweep_th16}, {"sweep_dc", &g_sweep_dc}, {"sweep_kdm", &g_sweep_kdm}, {"sweep_kdm_pd", &g_sweep_kdm_pd}, {"sweepc_slots", &g_sweepc_slots}, {"sweepc_pd", &g_sweepc_pd},
-        {"warp_bwd_direct", &g_warp_bwd_direct}, {"conv_s2_sweep", &g_conv_s2_sweep}, {"s2s_slots", &g_s2s_slots},
-        {"warp_tile", &g_warp_tile}, {"fuse_c0", &g_fuse_c0}, {"warp_lds_pad", &g_warp_lds_pad}, {"conv2d_wlds", &g_conv2d_wlds}, {"conv_tall64", &g_conv_tall64}, {"block8_slots", &::g_block8_slots}, {"softargmin_small", &::g_softargmin_small}, {"tail_nbk", &g_tail_nbk}, {"conv_wide", &g_conv_wide}, {"conv_small_nt", &g_conv_small_nt}};
-    for (const auto& e : table)
-        if (!strcmp(key, e.name)) return e.k;
-    return nullptr;
-}
-static int knob_value(const char* key, int value) { return (!strcmp(key, "warp_tiled") && value < 0) ? 1 : value; }   // -1: default
-}  // namespace pscv
-
-extern "C" int pscv_set_tuning(const char* key, int value) {
-    using namespace pscv;
-    PSCV_CHECK_ARG(key, "pscv_set_tuning: null key");
-    Knob* k = find_knob(key);
-    if (!k) { set_error("pscv_set_tuning: unknown key '%s'", key); return -1; }
-    // ("warp_tiled" = 3 selected the SLP-packed diagnostic build of the LDS-staged kernel, removed in round 5: refuse it rather than
-    //  silently measure the default kernel under its name)
-    if (!strcmp(key, "warp_tiled") && value == 3) { set_error("pscv_set_tuning: warp_tiled = 3 (packed diagnostic build) no longer exists"); return -1; }
-    k->set(knob_value(key, value));
-    return 0;
-}
-
-extern "C" int pscv_set_tuning_thread(const char* key, int value, int enable) {
-    using namespace pscv;
-    PSCV_CHECK_ARG(key, "pscv_set_tuning_thread: null key");
-    Knob* k = find_knob(key);
-    if (!k) { set_error("pscv_set_tuning_thread: unknown key '%s'", key); return -1; }
-    knob_thread_set(k->id, knob_value(key, value), enable != 0);
-    return 0;
-}
-
-extern "C" int pscv_get_tuning(const char* key, int* value) {
-    using namespace pscv;
-    PSCV_CHECK_ARG(key && value, "pscv_get_tuning: null argument");
-    Knob* k = find_knob(key);
-    if (!k) { set_error("pscv_get_tuning: unknown key '%s'", key); return -1; }
-    *value = (int)*k;
-    return 0;
-}
 
 extern "C" int pscv_warp_cost(const void* ref, const void* const* srcs, int n_src, const float* cams,
                               const float* depth, long depth_bstride, int depth_per_pixel, int geom, int cost,

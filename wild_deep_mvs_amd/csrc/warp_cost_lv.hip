@@ -526,7 +526,6 @@ static int lv_dispatch(const WarpArgs& a, int cost, hipStream_t st) {
 }
 
 extern int* g_wl_mode_hist;   // warp_cost_tiled.hip (pscv_debug_wl_mode_hist)
-extern Knob g_warp_tile;       // warp_cost.hip
 
 // Returns 0 if launched, 1 if this configuration is not covered (the caller tries the quad-owner kernel next), negative on error.
 int warp_cost_lv_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {

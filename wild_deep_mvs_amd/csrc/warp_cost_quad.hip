@@ -84,10 +84,8 @@ __global__ __launch_bounds__(256, 4) void warp_cost_q2_kernel(const WarpArgs a) 
     constexpr int OB = (int)sizeof(TOut);
     constexpr bool VAR = COST == PSCV_COST_VARIANCE || COST == PSCV_COST_VARIANCE_CVP;
 
-    // XCD-aware bijective remap (see warp_cost.hip): XCD k owns a contiguous band of reference pixels
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3, q_ = nwg >> 3, r_ = nwg & 7;
-    const int wg = (xcd < r_ ? xcd * (q_ + 1) : r_ * (q_ + 1) + (xcd - r_) * q_) + slot;
+    // XCD k owns a contiguous band of reference pixels
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
     const int pb = __builtin_amdgcn_readfirstlane(wg / a.n_dchunks);
     const int dc = __builtin_amdgcn_readfirstlane(wg - pb * a.n_dchunks);
     const int b = __builtin_amdgcn_readfirstlane(pb / a.npb_batch);

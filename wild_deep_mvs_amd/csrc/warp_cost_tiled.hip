@@ -528,7 +528,6 @@ static int wl_launch(const WarpArgs& a, int nblk, hipStream_t st) {
     auto kern = warp_cost_lds_kernel<TIn, TOut, PSCV_GEOM_PROJ, COST>;
     // "warp_lds_pad" (KiB, measurement knob): ask for more LDS than the kernel needs = fewer workgroups per CU with the same code --
     // the occupancy experiment of scripts/dev/wl_residency.py and the stream-mode co-residency runs (room for another stream's conv0)
-    extern Knob g_warp_lds_pad;
     const int lds = min(WL_LDS + 1024 * max(0, (int)g_warp_lds_pad), 160 * 1024);
     {
         hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
@@ -549,7 +548,6 @@ static int wl_dispatch(const WarpArgs& a, int cost, int nblk, hipStream_t st) {
 
 // Returns 0 if launched, 1 if this configuration is not covered by the LDS-staged kernel (the caller uses the quad /
 // generic direct kernels), negative on error.
-extern Knob g_warp_tile;   // warp_cost.hip
 int* g_wl_mode_hist = nullptr;   // set by pscv_debug_wl_mode_hist (development aid, not thread-safe; shared with warp_cost_lv.hip)
 
 int warp_cost_tiled_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {

@@ -300,7 +300,6 @@ static int gc_launch(const WarpArgs& a, hipStream_t st) {
 }
 
 extern int* g_wl_mode_hist;   // warp_cost_tiled.hip (pscv_debug_wl_mode_hist)
-extern Knob g_warp_tile;       // warp_cost.hip
 
 // Returns 0 if launched (one launch per group of four source views), 1 if this configuration is not covered (the caller uses the quad
 // kernel), negative on error.
