@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PSCV_ABI_VERSION 13
+#define PSCV_ABI_VERSION 14
 
 /* storage dtypes */
 #define PSCV_F32 0
@@ -466,6 +466,17 @@ int pscv_patch_match_filter(const float* state, const float* ref, int h, int w, 
  *   counter     device int64 running point count, as pscv_fuse_depth_pass (counter > capacity after the last pass = overflow)
  *   workspace   device scratch of pscv_colmap_fuse_workspace(h, w) bytes for the pass's view
  * No host synchronisation: five launches on `stream` (phase A, phase B, count, scan, scatter); the result is bit-reproducible.
+ *
+ * pscv_colmap_fuse_pass_normals (ABI 14; the COLMAP baseline, where the reference runs `colmap stereo_fusion
+ * --StereoFusion.max_normal_error 10` over PatchMatch's own normal maps, utils/colmap_utils.py:377-381, 396): the same pass with
+ * the normal test on ("with normal maps").
+ *   normal      host array of n_views device pointers, fp32 [h_v, w_v, 3]: unit normals in the camera frame of their view, 0
+ *               where the depth is filtered (what pscv_patch_match_filter writes); every pointer non-null
+ *   max_normal_error   degrees, in (0, 180]; min_cos = cos(max_normal_error pi / 180) in fp64
+ * The world normal of a pixel is w = R^T n, fp64 sums rounded to fp32.  A pixel joins a seed only if it also passes
+ * w_seed . w_pixel >= min_cos (fp64, against the seed, neither side normalised, NaN fails); a pixel that fails only this test is
+ * neither claimed nor marked.  The emitted normal is the normalised per-component median of w over the cluster, seed included.
+ * pscv_colmap_fuse_pass itself is unchanged (constant normals, no normal test).
  */
 long pscv_colmap_fuse_workspace(int h, int w);
 int pscv_colmap_fuse_pass(int view, int tag, const float* const* depth, const unsigned int* const* color,
@@ -474,6 +485,13 @@ int pscv_colmap_fuse_pass(int view, int tag, const float* const* depth, const un
                           float max_reproj_error, int min_num_pixels, int max_traversal_depth, float* out_xyz, float* out_normal,
                           unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity, long long* counter, void* workspace,
                           long workspace_bytes, void* stream);
+int pscv_colmap_fuse_pass_normals(int view, int tag, const float* const* depth, const unsigned int* const* color,
+                                  unsigned char* const* fused, unsigned long long* const* claim, const int* hw, int n_views,
+                                  const float* cams, const long* overlap, long processed, float max_depth_error,
+                                  float max_reproj_error, int min_num_pixels, int max_traversal_depth, const float* const* normal,
+                                  float max_normal_error, float* out_xyz, float* out_normal, unsigned char* out_rgb, int* out_view,
+                                  int* out_pixel, long capacity, long long* counter, void* workspace, long workspace_bytes,
+                                  void* stream);
 
 /*
  * Point-cloud metrics (ABI 11; the step after fusion).  Replaces the scipy cKDTree calls of evaluation/metrics.py: reduce_pts,

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("PSCV_LIB") or os.path.join(_HERE, "libpscv.so")     #
 CSRC = os.path.join(_HERE, "csrc")
 
 # mirror of include/pscv.h
-ABI_VERSION = 13
+ABI_VERSION = 14
 F32, BF16, F16 = 0, 1, 2
 GEOM_PROJ, GEOM_HOMOG = 0, 1
 COST_VARIANCE, COST_VARIANCE_CVP, COST_SOFTMIN, COST_GROUPCORR, COST_WARP_ONLY, COST_VARIANCE_PARTIAL = 0, 1, 2, 3, 4, 5
@@ -42,7 +42,8 @@ EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_
            "pscv_tail_sweep", "pscv_tail_sweep_workspace", "pscv_fuse_depth_workspace", "pscv_fuse_depth_pass",
            "pscv_point_grid_workspace", "pscv_point_grid_build", "pscv_point_nn_dist", "pscv_dtu_cell_occupancy", "pscv_radius_mis_round",
            "pscv_radius_mis_workspace", "pscv_radius_mis_compact", "pscv_colmap_fuse_workspace", "pscv_colmap_fuse_pass",
-           "pscv_patch_match_init", "pscv_patch_match_cost", "pscv_patch_match_half_step", "pscv_patch_match_filter")
+           "pscv_patch_match_init", "pscv_patch_match_cost", "pscv_patch_match_half_step", "pscv_patch_match_filter",
+           "pscv_colmap_fuse_pass_normals")
 
 
 class PscvMissingError(RuntimeError):
@@ -156,6 +157,9 @@ def _declare(lib):
     lib.pscv_colmap_fuse_pass.restype = i
     lib.pscv_colmap_fuse_pass.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp,
                                           C.POINTER(l), l, f, f, i, i, vp, vp, vp, vp, vp, l, vp, vp, l, vp]
+    lib.pscv_colmap_fuse_pass_normals.restype = i
+    lib.pscv_colmap_fuse_pass_normals.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp,
+                                                  C.POINTER(l), l, f, f, i, i, C.POINTER(vp), f, vp, vp, vp, vp, vp, l, vp, vp, l, vp]
     d = C.c_double
     lib.pscv_point_grid_workspace.restype = l
     lib.pscv_point_grid_workspace.argtypes = [l]

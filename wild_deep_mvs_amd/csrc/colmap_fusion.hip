@@ -20,6 +20,13 @@
 // Geometry is fp64 from the fp32 inputs with no contractions (the Makefile builds this file with -ffp-contract=off), so the
 // numpy restatement in tests/_colmap_fusion_ref.py reproduces every value bit for bit.
 //
+// With normal maps (NORMALS = true, pscv_colmap_fuse_pass_normals; section 2g "with normal maps"): every view brings an fp32
+// [h_v, w_v, 3] normal map in its camera frame.  The world normal of a pixel is w = R_m^T n rounded to fp32; phase A also asks
+// w_seed . w_pixel >= min_cos of every candidate that passed the depth and reprojection tests (against the SEED, not the parent
+// node, so it is a property of the (seed, pixel) pair and sits in the window scan); phase B, after the xyz and colour selections,
+// stages the cluster's world normals over nx_/ny_/nz_ (a second walk of the reach bits) and runs the same selection on them.
+// NORMALS = false is the network path as before: a constant normal per view, no normal test, its own kernel arguments.
+//
 // Replaces (fdarmon/wild_deep_mvs): utils/colmap_utils.py:391-400, the external `colmap stereo_fusion` run.
 #include "geo_common.h"
 
@@ -43,6 +50,13 @@ struct CfArgs {
     int n, i, lg_p, min_pixels, max_td;
     double max_depth_error, r2;
 };
+struct CfArgsN : CfArgs {                               // NORMALS = true
+    const float* normal[PSCV_FUSE_MAX_VIEWS];           // [h_v, w_v, 3] unit normals in the camera frame of view v (0 = filtered)
+    double min_cos;                                     // cos(max_normal_error)
+};
+static_assert(sizeof(CfArgsN) <= 4096, "the kernel-argument segment holds 4 KB");
+template <bool NORMALS> struct CfArgsOf { using type = CfArgs; };
+template <> struct CfArgsOf<true> { using type = CfArgsN; };
 
 // R^T (d K^-1 (x, y, 1) - t)
 __device__ __forceinline__ void cf_unproject(const float* c, double x, double y, double d, double& X, double& Y, double& Z) {
@@ -91,9 +105,17 @@ __device__ __forceinline__ uint32_t cf_fkey(float f) {           // IEEE total o
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float cf_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// world normal R^T n of the camera-frame normal at n[0..2], each component rounded to fp32
+__device__ __forceinline__ void cf_world_normal(const float* c, const float* n, float& wx, float& wy, float& wz) {
+    const float* R = c + CAM_R;
+    const double nx = (double)n[0], ny = (double)n[1], nz = (double)n[2];
+    wx = (float)((double)R[0] * nx + (double)R[3] * ny + (double)R[6] * nz);
+    wy = (float)((double)R[1] * nx + (double)R[4] * ny + (double)R[7] * nz);
+    wz = (float)((double)R[2] * nx + (double)R[5] * ny + (double)R[8] * nz);
+}
 
-template <int W, bool PHASE_B>
-__global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
+template <int W, bool PHASE_B, bool NORMALS>
+__global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const typename CfArgsOf<NORMALS>::type a) {
     constexpr int S = 2 * W + 1, NB = S * S;
     __shared__ float cam[PSCV_FUSE_MAX_VIEWS * PSCV_GEO_CAM_FLOATS];
     __shared__ unsigned long long adj[PSCV_FUSE_MAX_VIEWS];
@@ -118,6 +140,11 @@ __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
     }
     double Xs = 0.0, Ys = 0.0, Zs = 0.0;
     if (seed) cf_unproject(cam + i * PSCV_GEO_CAM_FLOATS, (double)scol, (double)srow, (double)ds, Xs, Ys, Zs);
+    // the seed's world normal: phase A tests every candidate against it, phase B stages it as the seed node's
+    float wsx = 0.0f, wsy = 0.0f, wsz = 0.0f;
+    if constexpr (NORMALS) {
+        if (seed) cf_world_normal(cam + i * PSCV_GEO_CAM_FLOATS, a.normal[i] + 3 * s, wsx, wsy, wsz);
+    }
     const unsigned long long key = a.key | (unsigned long long)s;   // (pass tag, seed index): the lowest seed wins a pixel
     const bool act = seed && m < a.n && m != i && !((a.processed >> m) & 1ull);
     const float* cm = cam + (m < a.n ? m : 0) * PSCV_GEO_CAM_FLOATS;
@@ -149,6 +176,11 @@ __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
                 if (!(fabs((z - dd) / dd) <= a.max_depth_error)) continue;
                 const double du = u - (double)col, dv = v - (double)row;
                 if (!(du * du + dv * dv <= a.r2)) continue;
+                if constexpr (NORMALS) {           // against the seed's normal; NaN fails
+                    float wx, wy, wz;
+                    cf_world_normal(cm, a.normal[m] + 3 * q, wx, wy, wz);
+                    if (!((double)wsx * (double)wx + (double)wsy * (double)wy + (double)wsz * (double)wz >= a.min_cos)) continue;
+                }
                 cand |= 1u << b;
             }
         }
@@ -221,6 +253,7 @@ __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
     const int total = (int)cf_group_sum((unsigned long long)cnt, P);
     const bool emit = seed && total >= a.min_pixels;
     // the lane's normal: R_m^T (1, 1, 1) / sqrt(3) rounded to fp32 (the constant normal maps of the reference's network path)
+    // (with normal maps the lane's nodes bring their own: staged over nx_/ny_/nz_ after the xyz selection below)
     constexpr double INV_SQRT3 = 0.57735026918962573;
     const float* Rm = cm + CAM_R;
     const float nrm[3] = {(float)((double)Rm[0] * INV_SQRT3 + (double)Rm[3] * INV_SQRT3 + (double)Rm[6] * INV_SQRT3),
@@ -253,7 +286,7 @@ __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
             // the same over the lane's normal, held cnt times
             int kn_[3] = {k0 + e, k0 + e, k0 + e};
             uint32_t pn[3] = {0, 0, 0};
-            for (int bit = 31; bit >= 0; --bit) {
+            for (int bit = NORMALS ? -1 : 31; bit >= 0; --bit) {
                 unsigned long long c = 0;
                 for (int d = 0; d < 3; ++d)
                     c += ((((cf_fkey(nrm[d]) ^ pn[d]) >> bit) == 0u) ? (unsigned long long)cnt : 0ull) << (16 * d);
@@ -283,6 +316,42 @@ __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const CfArgs a) {
             if (__ballot(emit && even) == 0ull) {   // no group needs the upper middle value
                 for (int d = 0; d < 3; ++d) { kx[1][d] = pre[d]; kn[1][d] = pn[d]; kc[1][d] = pc[d]; }
                 break;
+            }
+        }
+        if constexpr (NORMALS) {
+            // the nodes' world normals take the place of their positions (slot-major as before, the seed in slot 0 of lane i and
+            // the reach bits in the same order; a lane reads and writes its own column only), then the selection of x, y, z again
+            int j = 0;
+            if (seed && m == i) { nx_[0][lane] = wsx; ny_[0][lane] = wsy; nz_[0][lane] = wsz; j = 1; }
+            for (uint32_t r = reach; r; r &= r - 1u) {
+                const int bit = __builtin_ctz(r);
+                const int col = c0x - W + bit % S, row = c0y - W + bit / S;
+                float wx, wy, wz;
+                cf_world_normal(cm, a.normal[m] + 3 * ((long)row * wm + col), wx, wy, wz);
+                nx_[j][lane] = wx; ny_[j][lane] = wy; nz_[j][lane] = wz;
+                ++j;
+            }
+            for (int e = 0; e < 2; ++e) {
+                int kk[3] = {k0 + e, k0 + e, k0 + e};
+                uint32_t pre[3] = {0, 0, 0};
+                for (int bit = 31; bit >= 0; --bit) {
+                    unsigned long long c = 0;
+                    for (int jj = 0; jj < cnt; ++jj) {
+                        c += (((cf_fkey(nx_[jj][lane]) ^ pre[0]) >> bit) == 0u) ? 1ull : 0ull;
+                        c += (((cf_fkey(ny_[jj][lane]) ^ pre[1]) >> bit) == 0u) ? (1ull << 16) : 0ull;
+                        c += (((cf_fkey(nz_[jj][lane]) ^ pre[2]) >> bit) == 0u) ? (1ull << 32) : 0ull;
+                    }
+                    c = cf_group_sum(c, P);
+                    for (int d = 0; d < 3; ++d) {
+                        const int cd = (int)((c >> (16 * d)) & 0xffffull);
+                        if (kk[d] >= cd) { kk[d] -= cd; pre[d] |= 1u << bit; }
+                    }
+                }
+                for (int d = 0; d < 3; ++d) kn[e][d] = pre[d];
+                if (__ballot(emit && even) == 0ull) {
+                    for (int d = 0; d < 3; ++d) kn[1][d] = pre[d];
+                    break;
+                }
             }
         }
         for (int d = 0; d < 3; ++d) {
@@ -354,39 +423,52 @@ extern "C" long pscv_colmap_fuse_workspace(int h, int w) {
     return pscv::align256(npix) + pscv::align256(nseg * 4) + pscv::align256(nseg * 8) + pscv::align256(npix * 32);
 }
 
-extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* depth, const unsigned int* const* color,
-                                     unsigned char* const* fused, unsigned long long* const* claim, const int* hw, int n_views,
-                                     const float* cams, const long* overlap, long processed_mask,
-                                     float max_depth_error, float max_reproj_error, int min_num_pixels, int max_traversal_depth,
-                                     float* out_xyz, float* out_normal, unsigned char* out_rgb, int* out_view, int* out_pixel,
-                                     long capacity, long long* counter, void* workspace, long workspace_bytes, void* stream) {
+namespace {
+// one pass: `what` names the entry point in messages; NORMALS adds the normal maps and cos(max_normal_error)
+template <bool NORMALS>
+int cf_pass(const char* what, int view, int tag, const float* const* depth, const unsigned int* const* color,
+            unsigned char* const* fused, unsigned long long* const* claim, const int* hw, int n_views, const float* cams,
+            const long* overlap, long processed_mask, float max_depth_error, float max_reproj_error, int min_num_pixels,
+            int max_traversal_depth, const float* const* normal, float max_normal_error, float* out_xyz, float* out_normal,
+            unsigned char* out_rgb, int* out_view, int* out_pixel, long capacity, long long* counter, void* workspace,
+            long workspace_bytes, void* stream) {
     using namespace pscv;
     PSCV_CHECK_ARG(depth && color && fused && claim && hw && cams && overlap && counter && workspace,
-                   "pscv_colmap_fuse_pass: null pointer argument");
-    PSCV_CHECK_ARG(n_views >= 2 && n_views <= PSCV_FUSE_MAX_VIEWS, "pscv_colmap_fuse_pass: n_views=%d outside [2,%d]", n_views,
+                   "%s: null pointer argument", what);
+    PSCV_CHECK_ARG(n_views >= 2 && n_views <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [2,%d]", what, n_views,
                    PSCV_FUSE_MAX_VIEWS);
-    PSCV_CHECK_ARG(view >= 0 && view < n_views, "pscv_colmap_fuse_pass: view %d outside [0,%d)", view, n_views);
+    PSCV_CHECK_ARG(view >= 0 && view < n_views, "%s: view %d outside [0,%d)", what, view, n_views);
     const unsigned long long processed = (unsigned long long)processed_mask;
-    PSCV_CHECK_ARG(!((processed >> view) & 1ull), "pscv_colmap_fuse_pass: view %d is already processed", view);
-    PSCV_CHECK_ARG(max_reproj_error > 0.0f && max_reproj_error <= 2.0f, "pscv_colmap_fuse_pass: max_reproj_error=%g outside (0,2]",
+    PSCV_CHECK_ARG(!((processed >> view) & 1ull), "%s: view %d is already processed", what, view);
+    PSCV_CHECK_ARG(max_reproj_error > 0.0f && max_reproj_error <= 2.0f, "%s: max_reproj_error=%g outside (0,2]", what,
                    (double)max_reproj_error);
-    PSCV_CHECK_ARG(max_depth_error > 0.0f && max_depth_error < 1.0f, "pscv_colmap_fuse_pass: max_depth_error=%g outside (0,1)",
+    PSCV_CHECK_ARG(max_depth_error > 0.0f && max_depth_error < 1.0f, "%s: max_depth_error=%g outside (0,1)", what,
                    (double)max_depth_error);
-    PSCV_CHECK_ARG(max_traversal_depth >= 1, "pscv_colmap_fuse_pass: max_traversal_depth=%d < 1", max_traversal_depth);
-    PSCV_CHECK_ARG(tag >= 0, "pscv_colmap_fuse_pass: tag %d < 0", tag);
-    PSCV_CHECK_ARG(capacity >= 0 && (capacity == 0 || (out_xyz && out_rgb)), "pscv_colmap_fuse_pass: bad output buffer (capacity %ld)",
+    PSCV_CHECK_ARG(max_traversal_depth >= 1, "%s: max_traversal_depth=%d < 1", what, max_traversal_depth);
+    PSCV_CHECK_ARG(tag >= 0, "%s: tag %d < 0", what, tag);
+    PSCV_CHECK_ARG(capacity >= 0 && (capacity == 0 || (out_xyz && out_rgb)), "%s: bad output buffer (capacity %ld)", what,
                    capacity);
-    CfArgs a;
-    if (fill_views(a, a.fused, "pscv_colmap_fuse_pass", n_views, depth, color, fused, hw)) return -1;
+    typename CfArgsOf<NORMALS>::type a;
+    if (fill_views(a, a.fused, what, n_views, depth, color, fused, hw)) return -1;
     for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
         const bool on = v < n_views;
         a.claim[v] = on ? claim[v] : nullptr;
         a.overlap[v] = on ? ((unsigned long long)overlap[v] & ~(1ull << v)) & (n_views == 64 ? ~0ull : ((1ull << n_views) - 1ull)) : 0ull;
-        PSCV_CHECK_ARG(!on || claim[v], "pscv_colmap_fuse_pass: view %d has a null pointer", v);
+        PSCV_CHECK_ARG(!on || claim[v], "%s: view %d has a null pointer", what, v);
+    }
+    if constexpr (NORMALS) {
+        PSCV_CHECK_ARG(normal, "%s: null pointer argument", what);
+        PSCV_CHECK_ARG(max_normal_error > 0.0f && max_normal_error <= 180.0f, "%s: max_normal_error=%g outside (0,180] degrees", what,
+                       (double)max_normal_error);
+        for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
+            a.normal[v] = v < n_views ? normal[v] : nullptr;
+            PSCV_CHECK_ARG(v >= n_views || normal[v], "%s: view %d has a null normal map", what, v);
+        }
+        a.min_cos = cos((double)max_normal_error * 3.14159265358979323846 / 180.0);
     }
     const long npix = (long)a.h[view] * a.w[view], nseg = cf_nseg(npix);
     PSCV_CHECK_ARG(workspace_bytes >= pscv_colmap_fuse_workspace(a.h[view], a.w[view]),
-                   "pscv_colmap_fuse_pass: workspace of %ld bytes < %ld", workspace_bytes,
+                   "%s: workspace of %ld bytes < %ld", what, workspace_bytes,
                    pscv_colmap_fuse_workspace(a.h[view], a.w[view]));
     char* ws = static_cast<char*>(workspace);
     a.flag = reinterpret_cast<uint8_t*>(ws);
@@ -405,22 +487,47 @@ extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* dept
     const bool w2 = max_reproj_error > 1.0f;
     const long groups = (long)CF_WAVE >> a.lg_p;
     const long nblk = (npix + groups - 1) / groups;
-    PSCV_CHECK_ARG(nblk < (1L << 31), "pscv_colmap_fuse_pass: %ld blocks", nblk);
+    PSCV_CHECK_ARG(nblk < (1L << 31), "%s: %ld blocks", what, nblk);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (w2) hipLaunchKernelGGL((colmap_fuse_kernel<2, false>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    else hipLaunchKernelGGL((colmap_fuse_kernel<1, false>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (phase A)");
-    if (w2) hipLaunchKernelGGL((colmap_fuse_kernel<2, true>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    else hipLaunchKernelGGL((colmap_fuse_kernel<1, true>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (phase B)");
+    if (w2) hipLaunchKernelGGL((colmap_fuse_kernel<2, false, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
+    else hipLaunchKernelGGL((colmap_fuse_kernel<1, false, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
+    PSCV_CHECK_LAUNCH(what);
+    if (w2) hipLaunchKernelGGL((colmap_fuse_kernel<2, true, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
+    else hipLaunchKernelGGL((colmap_fuse_kernel<1, true, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
+    PSCV_CHECK_LAUNCH(what);
     const unsigned aux = (unsigned)((npix + CF_AUX_THREADS - 1) / CF_AUX_THREADS);
     hipLaunchKernelGGL(colmap_count_kernel, dim3(aux), dim3(CF_AUX_THREADS), 0, st, a.flag, npix, seg_count);
-    PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (count)");
+    PSCV_CHECK_LAUNCH(what);
     hipLaunchKernelGGL((scan_kernel<CF_SCAN_THREADS, long long, true>), dim3(1), dim3(CF_SCAN_THREADS), 0, st, seg_count, seg_off, counter,
                        (int)nseg);
-    PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (scan)");
+    PSCV_CHECK_LAUNCH(what);
     hipLaunchKernelGGL(colmap_scatter_kernel, dim3(aux), dim3(CF_AUX_THREADS), 0, st, a.flag, seg_off, a.stage, npix, view,
                        (long long)capacity, out_xyz, out_normal, out_rgb, out_view, out_pixel);
-    PSCV_CHECK_LAUNCH("pscv_colmap_fuse_pass (scatter)");
+    PSCV_CHECK_LAUNCH(what);
     return 0;
+}
+}  // namespace
+
+extern "C" int pscv_colmap_fuse_pass(int view, int tag, const float* const* depth, const unsigned int* const* color,
+                                     unsigned char* const* fused, unsigned long long* const* claim, const int* hw, int n_views,
+                                     const float* cams, const long* overlap, long processed_mask,
+                                     float max_depth_error, float max_reproj_error, int min_num_pixels, int max_traversal_depth,
+                                     float* out_xyz, float* out_normal, unsigned char* out_rgb, int* out_view, int* out_pixel,
+                                     long capacity, long long* counter, void* workspace, long workspace_bytes, void* stream) {
+    return cf_pass<false>("pscv_colmap_fuse_pass", view, tag, depth, color, fused, claim, hw, n_views, cams, overlap, processed_mask,
+                          max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, nullptr, 0.0f, out_xyz, out_normal,
+                          out_rgb, out_view, out_pixel, capacity, counter, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pscv_colmap_fuse_pass_normals(int view, int tag, const float* const* depth, const unsigned int* const* color,
+                                             unsigned char* const* fused, unsigned long long* const* claim, const int* hw,
+                                             int n_views, const float* cams, const long* overlap, long processed_mask,
+                                             float max_depth_error, float max_reproj_error, int min_num_pixels,
+                                             int max_traversal_depth, const float* const* normal, float max_normal_error,
+                                             float* out_xyz, float* out_normal, unsigned char* out_rgb, int* out_view, int* out_pixel,
+                                             long capacity, long long* counter, void* workspace, long workspace_bytes, void* stream) {
+    return cf_pass<true>("pscv_colmap_fuse_pass_normals", view, tag, depth, color, fused, claim, hw, n_views, cams, overlap,
+                         processed_mask, max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, normal,
+                         max_normal_error, out_xyz, out_normal, out_rgb, out_view, out_pixel, capacity, counter, workspace,
+                         workspace_bytes, stream);
 }

@@ -3,11 +3,16 @@
 The reference writes COLMAP workspace files and runs the external ``colmap image_undistorter`` and ``colmap stereo_fusion``
 binaries (``utils/colmap_utils.py:324-400``), which are not part of the AMD stack.  Here the fusion is ``pscv_colmap_fuse_pass``,
 two HIP phases per view (INTEGRATION.md section 2g states the rule and its named deviations from COLMAP; it restates
-StereoFusion as the reference configures it -- normal test off, ``max_depth_error``, ``max_reproj_error`` and ``min_num_pixels``
-from the command line, COLMAP's defaults for the rest -- and has not been compared with the binary).
+StereoFusion as the reference configures it -- ``max_depth_error``, ``max_reproj_error`` and ``min_num_pixels`` from the command
+line, COLMAP's defaults for the rest -- and has not been compared with the binary).
 
 ``colmap_fusion(dataloader, args)`` keeps the reference's interface and writes the file its metrics step reads,
 ``<data_path>/Points/<model>_<nviews>/<model>_<nviews><scene>.ply``, in COLMAP's fused PLY layout.
+
+Network path (``args.colmap`` false): constant normals, the normal test off (``max_normal_error 180`` in the reference).
+COLMAP baseline (``args.colmap``): the geometric normal maps that ``depthmap_colmap`` wrote under
+``IntRes/colmap_dense/<scene>/stereo/normal_maps`` go into ``pscv_colmap_fuse_pass_normals`` with ``MAX_NORMAL_ERROR`` = 10
+degrees; until that folder exists the call raises ``NotImplementedError`` and touches no file.
 """
 from __future__ import annotations
 
@@ -18,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from ..utils.colmap_array import read_array
 from ..utils.colmap_model import overlap_from_counts, shared_point_counts
 from ..utils.point_cloud import write_colmap_point_cloud
 from .filtering import depth_folder_name
@@ -26,6 +32,7 @@ from .fusibile import get_mask
 CHECK_NUM_IMAGES = 50          # COLMAP's StereoFusionOptions defaults
 MAX_TRAVERSAL_DEPTH = 100
 MAX_NUM_PIXELS = 10000
+MAX_NORMAL_ERROR = 10.0        # degrees, under args.colmap: "--StereoFusion.max_normal_error 10" (utils/colmap_utils.py:396)
 
 
 def nearest_colors(img: torch.Tensor, h: int, w: int) -> np.ndarray:
@@ -70,10 +77,24 @@ def scene_overlap(args, names):
     return [[u for u in range(n) if u != v][:CHECK_NUM_IMAGES] for v in range(n)], "all other views (no sparse model)"
 
 
+def view_normals(normal_dir, filename, shape):
+    """The geometric normal map of one view (camera frame, fp32 [h,w,3]) at the depth map's size ``shape``; not resampled."""
+    path = Path(normal_dir) / f"{filename}.jpg.geometric.bin"
+    if not path.exists():
+        raise FileNotFoundError(f"colmap_fusion: view {filename} has a depth map but no normal map {path}")
+    normal = read_array(path)
+    if normal.ndim != 3 or normal.shape[2] != 3 or normal.shape[:2] != tuple(shape):
+        raise ValueError(f"colmap_fusion: normal map {path} is {normal.shape}, the depth map of view {filename} is {tuple(shape)} "
+                         "(after args.upsample); normal maps are not resampled")
+    return np.ascontiguousarray(normal, dtype=np.float32)
+
+
 def colmap_fusion(dataloader, args):
-    if getattr(args, "colmap", False):
-        raise NotImplementedError("colmap_fusion with args.colmap needs COLMAP's own depth and normal maps (its patch match), "
-                                  "which this port does not produce")
+    use_normals = bool(getattr(args, "colmap", False))
+    normal_dir = Path(args.data_path) / "IntRes" / "colmap_dense" / str(args.scene) / "stereo" / "normal_maps"
+    if use_normals and not normal_dir.is_dir():
+        raise NotImplementedError(f"colmap_fusion with args.colmap fuses the depth and normal maps of depthmap_colmap, which has "
+                                  f"to run first: {normal_dir} does not exist")
     folder_name = depth_folder_name(args)
     ply_dir = Path(args.data_path) / "Points" / folder_name
     outfile = ply_dir / f"{folder_name}{args.scene}.ply"
@@ -81,7 +102,13 @@ def colmap_fusion(dataloader, args):
         print("Point cloud Fusion already done")
         return
     depth_folder = Path(args.data_path) / "IntRes" / "depthmaps" / folder_name / str(args.scene)
-    views, names = [], []
+    if use_normals:
+        # the reference reads IntRes/depthmaps/None_<nviews>/<scene> here, a folder none of its steps writes; depthmap_colmap
+        # writes IntRes/direct_depthmaps/colmap/<scene> (INTEGRATION.md section 2g names the deviation)
+        if not depth_folder.is_dir():
+            depth_folder = Path(args.data_path) / "IntRes" / "direct_depthmaps" / "colmap" / str(args.scene)
+        print(f"COLMAP fusion reads the depth maps of {depth_folder}")
+    views, names, normals = [], [], []
     for b in dataloader:
         filename = b["filename"][0]
         depth_file = depth_folder / f"{filename}_out.npz"
@@ -90,15 +117,18 @@ def colmap_fusion(dataloader, args):
             continue
         views.append(view_inputs(args, b, depth_file))
         names.append(filename)
+        if use_normals:
+            normals.append(view_normals(normal_dir, filename, views[-1][0].shape))
     overlap, source = scene_overlap(args, names)
     print(f"COLMAP fusion of {len(views)} views, overlap from {source}")
     depths, colors, K, R, t = zip(*views)
+    extra = dict(normals=[torch.from_numpy(n).cuda() for n in normals], max_normal_error=MAX_NORMAL_ERROR) if use_normals else {}
     with torch.no_grad():
         cams = ops.geo_filter_cams(torch.stack(K), torch.stack(R), torch.stack(t)).cuda()
         xyz, normal, rgb, _ = ops.colmap_fuse([torch.from_numpy(d).cuda() for d in depths], [torch.from_numpy(c).cuda() for c in colors],
                                               cams, overlap, max_depth_error=args.fusion_depth_threshold,
                                               max_reproj_error=args.fusion_max_reproj_error, min_num_pixels=args.fusion_num_consistent,
-                                              max_traversal_depth=MAX_TRAVERSAL_DEPTH, max_num_pixels=MAX_NUM_PIXELS)
+                                              max_traversal_depth=MAX_TRAVERSAL_DEPTH, max_num_pixels=MAX_NUM_PIXELS, **extra)
     ply_dir.mkdir(parents=True, exist_ok=True)
     write_colmap_point_cloud(outfile, xyz, normal, rgb)
     print(f"Fused {xyz.shape[0]} points from {len(views)} views -> {outfile}")

@@ -660,13 +660,39 @@ def _colmap_check(n, max_depth_error, max_reproj_error, min_num_pixels, max_trav
                          "COLMAP's cap could cut a cluster, which the parallel rule does not model")
 
 
-class _ColmapRun:
-    """Device state shared by the passes of one fusion: packed inputs, fused masks, claim maps, workspace, output, counter."""
+def _colmap_normals(normals, max_normal_error, depths, what):
+    """The normal maps of ``colmap_fuse`` checked against the depth maps -> (the list or None, max_normal_error or None)."""
+    if (normals is None) != (max_normal_error is None):
+        raise ValueError(f"{what}: normals and max_normal_error go together (both, or neither for the constant normals of the "
+                         "network path)")
+    if normals is None:
+        return None, None
+    e = float(np.float32(max_normal_error))
+    if not 0.0 < e <= 180.0:                         # (false for NaN)
+        raise ValueError(f"{what}: max_normal_error must lie in (0, 180] degrees, got {max_normal_error}")
+    normals = list(normals)
+    if len(normals) != len(depths):
+        raise ValueError(f"{what}: one normal map per view expected, got {len(normals)} for {len(depths)} depth maps")
+    for v, (nm, d) in enumerate(zip(normals, depths)):
+        if not torch.is_tensor(nm) or nm.dtype != torch.float32 or tuple(nm.shape) != tuple(d.shape) + (3,):
+            raise ValueError(f"{what}: normal map {v} must be fp32 {tuple(d.shape) + (3,)} (the depth map's size), got "
+                             f"{getattr(nm, 'dtype', type(nm))} {tuple(getattr(nm, 'shape', ()))}")
+        _dev(nm)
+        if nm.device != d.device:
+            raise ValueError(f"{what}: normal map {v} is on {nm.device}, its depth map on {d.device}")
+    return normals, e
 
-    def __init__(self, depths, colors, cams, overlap, fused, capacity, params):
+
+class _ColmapRun:
+    """Device state shared by the passes of one fusion: packed inputs, fused masks, claim maps, workspace, output, counter; with
+    ``normals`` (N x fp32 [h_v,w_v,3]) and ``max_normal_error`` (degrees) the passes run pscv_colmap_fuse_pass_normals."""
+
+    def __init__(self, depths, colors, cams, overlap, fused, capacity, params, *, normals=None, max_normal_error=None):
         self.depths, self.packed, self.cams, ptrs, _ = _fuse_inputs(depths, colors, cams)
         n = len(self.depths)
         _colmap_check(n, *params)
+        self.normals, self.max_normal_error = _colmap_normals(normals, max_normal_error, self.depths, "pscv.colmap_fuse")
+        self.nptr = None if self.normals is None else _used_ptrs(self.normals)
         self.params = params
         self.overlap = colmap_overlap_lists(overlap, n)
         self.bits = (C.c_long * n)(*[C.c_long(sum(1 << m for m in row)).value for row in self.overlap])
@@ -690,6 +716,17 @@ class _ColmapRun:
         n = len(self.depths)
         e, r, mnp, mtd, _ = self.params
         h, w = self.depths[view].shape
+        if self.normals is not None:
+            rc = _launch("colmap_fuse_pass_normals", lambda: L.lib().pscv_colmap_fuse_pass_normals(
+                int(view), int(tag), self.dptr, self.cptr, self.fptr, self.clptr, self.hw, n, _p(self.cams), self.bits,
+                C.c_long(int(processed)).value, float(e), float(r), int(mnp), int(mtd), self.nptr, float(self.max_normal_error),
+                _p(self.xyz), _p(self.normal), _p(self.rgb), _p(self.view), _p(self.pixel), self.cap, _p(self.counter), _p(self.ws),
+                int(self.ws.numel()), _stream()),
+                # as below, plus 12 B of normal per window pixel that passed depth and reprojection (phase A, at most all) and per
+                # cluster node (phase B)
+                cost=lambda: (float(h * w * (n - 1) * (2 * 25 * 5 + 2 * 25 * 12)), 0.0))
+            L.check(rc, "pscv_colmap_fuse_pass_normals")
+            return
         rc = _launch("colmap_fuse_pass", lambda: L.lib().pscv_colmap_fuse_pass(
             int(view), int(tag), self.dptr, self.cptr, self.fptr, self.clptr, self.hw, n, _p(self.cams), self.bits, C.c_long(int(processed)).value,
             float(e), float(r), int(mnp), int(mtd), _p(self.xyz), _p(self.normal), _p(self.rgb), _p(self.view), _p(self.pixel),
@@ -706,11 +743,12 @@ class _ColmapRun:
 def colmap_fuse_pass(view: int, depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, overlap,
                      fused: Sequence[torch.Tensor], *, processed: Sequence[int] = (), max_depth_error: float = 0.01,
                      max_reproj_error: float = 1.0, min_num_pixels: int = 3, max_traversal_depth: int = 100,
-                     max_num_pixels: int = 10000, capacity: Optional[int] = None):
+                     max_num_pixels: int = 10000, capacity: Optional[int] = None,
+                     normals: Optional[Sequence[torch.Tensor]] = None, max_normal_error: Optional[float] = None):
     """The pass of view ``view`` of ``colmap_fuse`` alone, with explicit state: ``fused`` N x uint8 [h_v,w_v] masks (updated in
     place) and ``processed`` the views whose passes are done -> (xyz fp32 [M,3], normal fp32 [M,3], rgb uint8 [M,3], pixel int32
     [M] = y w + x of each seed), row-major seed order.  ``capacity`` (default h w of the view) sizes the output buffer; a pass that
-    needs more raises ``PscvError``."""
+    needs more raises ``PscvError``.  ``normals`` / ``max_normal_error`` as in ``colmap_fuse``."""
     n = len(depths)
     if not 0 <= int(view) < n:
         raise ValueError(f"pscv.colmap_fuse_pass: view {view} outside [0,{n})")
@@ -721,7 +759,8 @@ def colmap_fuse_pass(view: int, depths: Sequence[torch.Tensor], colors: Sequence
         proc |= 1 << int(v)
     cap = int(depths[view].numel()) if capacity is None else int(capacity)
     run = _ColmapRun(depths, colors, cams, overlap, list(fused), cap,
-                     (max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels))
+                     (max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels),
+                     normals=normals, max_normal_error=max_normal_error)
     run.run_pass(int(view), 0, proc)
     xyz, normal, rgb, _, pixel = run.result("pscv.colmap_fuse_pass")
     return xyz, normal, rgb, pixel
@@ -729,7 +768,8 @@ def colmap_fuse_pass(view: int, depths: Sequence[torch.Tensor], colors: Sequence
 
 def colmap_fuse(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, overlap, *, max_depth_error: float,
                 max_reproj_error: float, min_num_pixels: int, max_traversal_depth: int = 100, max_num_pixels: int = 10000,
-                capacity: Optional[int] = None, want_pixel: bool = False):
+                capacity: Optional[int] = None, want_pixel: bool = False,
+                normals: Optional[Sequence[torch.Tensor]] = None, max_normal_error: Optional[float] = None):
     """COLMAP-style stereo fusion of N depth maps into one point cloud (the YFCC fusion of the
     reference's pipeline): depths N x fp32 [h_v,w_v] (masked pixels 0), colors N x uint8 [h_v,w_v,3], cams [N,30]
     (``geo_filter_cams``; intrinsics at each map's size), all on the GPU, 2 <= N <= 64; overlap N lists of view indices (COLMAP's
@@ -737,9 +777,16 @@ def colmap_fuse(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], 
     [M]) on the GPU, pass-major (FindNextImage order, computed on the host) then row-major seed order, bit-reproducible.  One
     pscv_colmap_fuse_pass per view on the current stream; the host reads the point count once at the end.  ``capacity`` (default:
     the total pixel count, which no run can exceed) sizes the output; a run that needs more raises ``PscvError``.  ``want_pixel``
-    appends the seed pixel index (y w_v + x) of each point."""
+    appends the seed pixel index (y w_v + x) of each point.
+
+    Without ``normals`` every view has the constant normal of the reference's network path and the normal test is off.  With
+    ``normals`` (N x fp32 [h_v,w_v,3] on the GPU, contiguous: unit normals in the camera frame of their view, 0 where the depth is
+    filtered, what ``patch_match_filter`` returns) and ``max_normal_error`` (degrees, in (0, 180]) a pixel joins a seed only when
+    their world normals are within that angle, and the fused normal is the normalised per-component median over the cluster
+    (section 2g, "with normal maps"; pscv_colmap_fuse_pass_normals).  One without the other is a ``ValueError``."""
     run = _ColmapRun(depths, colors, cams, overlap, None, capacity,
-                     (max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels))
+                     (max_depth_error, max_reproj_error, min_num_pixels, max_traversal_depth, max_num_pixels),
+                     normals=normals, max_normal_error=max_normal_error)
     processed = 0
     for tag, v in enumerate(find_next_image_order(run.overlap)):
         run.run_pass(v, tag, processed)

@@ -568,6 +568,71 @@ def make_patch_match_scene(V: int, H: int, W: int, *, seed: int = 0, spacing: fl
             "vis": torch.from_numpy(vis.reshape(V, H, W))}
 
 
+def make_normal_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, overlap: str = "all", k_overlap: int = 3,
+                             jitter_deg: float = 2.5, rot_view: int = 1, rot_deg: float = 25.0, rot_frac: float = 0.5,
+                             outlier_view: int = 0, mask_frac: float = 0.02, spacing: float = 0.4) -> Dict[str, object]:
+    """Inputs of the COLMAP-style fusion with normal maps, with ground truth: ``make_patch_match_scene``'s tilted plane and
+    occluding sphere seen by V cameras, all H x W.  The depth maps are the true depths; the normal maps (camera frame, unit) are
+    the true normals with a Gaussian tangent jitter (``jitter_deg`` per tangent axis, seeded) everywhere.  In view ``rot_view`` a
+    central block (``rot_frac`` of the height and of the width) has its normals turned by ``rot_deg`` about a tangent axis while
+    its depths stay true, so the normal test alone can refuse those pixels.  View ``outlier_view`` has a block of gross depth
+    outliers (x 1.25); every view has ``mask_frac`` filtered pixels and one filtered rectangle (depth 0, normal 0).  ``overlap``
+    as in ``make_yfcc_fusion_scene``: "all" (nearest camera centre first), "knn" or "chain".
+
+    Returns ``depths`` V x float32 [H,W], ``normals`` V x float32 [H,W,3], ``colors`` V x uint8 [H,W,3] (the image x 255
+    truncated), ``K``, ``R`` [V,3,3], ``t`` [V,3,1], ``overlap`` (V lists), and the ground truth ``depth_gt`` [V,H,W] and
+    ``normal_world`` [V,H,W,3] (the true world normal at every pixel, facing its camera), ``rotated`` [V,H,W] bool."""
+    pm = make_patch_match_scene(V, H, W, seed=seed, spacing=spacing)
+    rng = np.random.default_rng([seed, 0x6E6F726D])
+    R = pm["R"].numpy().astype(np.float64)
+    n_true = pm["normal"].numpy().astype(np.float64)                       # [V,H,W,3] camera frame
+    depth_gt = pm["depth"].numpy().astype(np.float64)
+    normal_world = np.einsum("vji,vhwj->vhwi", R, n_true)                    # R^T n
+    sig = math.radians(jitter_deg)
+    depths, normals, colors, rotated = [], [], [], []
+    for v in range(V):
+        n = n_true[v]
+        g = rng.standard_normal((H, W, 3))
+        nj = n + sig * (g - (g * n).sum(-1, keepdims=True) * n)
+        nj /= np.linalg.norm(nj, axis=-1, keepdims=True)
+        rot = np.zeros((H, W), dtype=bool)
+        if v == rot_view % V:
+            bh, bw = max(int(round(H * rot_frac)), 1), max(int(round(W * rot_frac)), 1)
+            r0, c0 = (H - bh) // 2, (W - bw) // 2
+            rot[r0:r0 + bh, c0:c0 + bw] = True
+            k = np.cross(nj, np.array([0.0, 1.0, 0.0]))
+            k /= np.linalg.norm(k, axis=-1, keepdims=True)                   # a tangent axis: the turn is rot_deg exactly
+            th = math.radians(rot_deg)
+            turned = nj * math.cos(th) + np.cross(k, nj) * math.sin(th)
+            nj = np.where(rot[..., None], turned, nj)
+        d = depth_gt[v].copy()
+        if v == outlier_view % V:
+            d[H // 8:H // 4, W // 8:W // 3] *= 1.25
+        gone = rng.random((H, W)) < mask_frac
+        r0, c0 = int(rng.integers(0, max(H - 4, 1))), int(rng.integers(0, max(W - 6, 1)))
+        gone[r0:r0 + 3, c0:c0 + 5] = True
+        d[gone] = 0.0
+        nj[gone] = 0.0
+        depths.append(torch.from_numpy(d.astype(np.float32)).contiguous())
+        normals.append(torch.from_numpy(nj.astype(np.float32)).contiguous())
+        colors.append(pm["imgs"][v].mul(255).byte().permute(1, 2, 0).contiguous())
+        rotated.append(rot)
+    lists = []
+    for v in range(V):
+        others = list(pm["src"][v])
+        if overlap == "all":
+            lists.append(others)
+        elif overlap == "knn":
+            lists.append(others[:k_overlap])
+        elif overlap == "chain":
+            lists.append([u for u in (v - 1, v + 1) if 0 <= u < V])
+        else:
+            raise ValueError(f"make_normal_fusion_scene: unknown overlap {overlap!r}")
+    return {"depths": depths, "normals": normals, "colors": colors, "K": pm["K"], "R": pm["R"], "t": pm["t"], "overlap": lists,
+            "depth_gt": torch.from_numpy(depth_gt.astype(np.float32)), "normal_world": torch.from_numpy(normal_world.astype(np.float32)),
+            "rotated": torch.from_numpy(np.stack(rotated))}
+
+
 def patch_match_batches(scene: Mapping[str, object], names: Sequence[str] = None, max_src: int = None):
     """Dataloader batches of a ``make_patch_match_scene`` scene, shaped like the YFCC loader's (batch size 1): per reference view
     v, ``imgs`` [1,1+S,3,H,W], ``K``, ``R`` [1,1+S,3,3], ``t`` [1,1+S,3,1], ``depth_min``, ``depth_max`` [1,1+S], ``filename`` [name]
