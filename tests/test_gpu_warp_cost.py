@@ -270,11 +270,15 @@ def test_lane_owner_kernel_equals_direct_kernel(env, baseline_scale, shape, V, D
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("cost_name", ["variance", "variance_cvp", "softmin", "warp_only", "groupcorr", "warp_only_homog"])
-@pytest.mark.parametrize("baseline_scale,shape,D,per_pixel", [(1.0, (64, 80), 24, False), (1.0, (37, 53), 23, True),
-                                                              (12.0, (40, 48), 7, False)])
-def test_quad_kernel_equals_generic_kernel(env, baseline_scale, shape, D, per_pixel, cost_name, dtype):
+@pytest.mark.parametrize("baseline_scale,shape,D,per_pixel,V", [
+    pytest.param(1.0, (64, 80), 24, False, 4, id="1.0-shape0-24-False"), pytest.param(1.0, (37, 53), 23, True, 4, id="1.0-shape1-23-True"),
+    pytest.param(12.0, (40, 48), 7, False, 4, id="12.0-shape2-7-False"),
+    # PSCV_MAX_SRC = 16 source views: the HOMOG ray terms of the generic kernel (16 views x 128 pixels x 32 B = 64 KiB) need the
+    # dynamic-LDS opt-in, the one launch of the forward warp that asks for it only above a size; the quad kernel needs 32 KiB
+    pytest.param(1.0, (24, 32), 6, False, 17, id="16src-shape3-6-False")])
+def test_quad_kernel_equals_generic_kernel(env, baseline_scale, shape, D, per_pixel, V, cost_name, dtype):
     """The quad-mapped kernel (warp_cost_quad.hip: one texel per lane quad, two depth planes per quad) and the generic
-    2-lanes-per-voxel kernel run the same arithmetic on the same taps: every cost mode of both geometries, an odd
+    2-lanes-per-voxel kernel run the same arithmetic on the same taps: every cost mode of both geometries, 3 and 16 source views, an odd
     plane count (the unpaired tail plane), image sizes that do not divide the 64-pixel blocks, per-pixel planes (CVP /
     Vis refinement stages), and a 12x wider baseline where most samples leave the image (border path, zero padding,
     points behind the camera).  Agreement to one stored ulp (the compiler contracts the final variance / softmin
@@ -283,7 +287,7 @@ def test_quad_kernel_equals_generic_kernel(env, baseline_scale, shape, D, per_pi
     from wild_deep_mvs_amd import synthetic
     from oracle.mvsnet import mvsnet_cameras
     h, w = shape
-    B, V, C = 2, 4, 32
+    B, C = 2, 32
     feats = synthetic.make_features(B, V, C, h, w, seed=5)
     cam = synthetic.make_cameras(B, V, 4 * h, 4 * w)
     cam["t"] = cam["t"] * baseline_scale

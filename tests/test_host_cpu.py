@@ -39,6 +39,59 @@ def test_error_channel_and_argument_checks():
         ops.softargmin(torch.zeros(1, 8, 4, 4))
 
 
+def test_binding_is_derived_from_the_header():
+    """_lib declares every prototype of include/pscv.h, and for exports that cover every parameter kind the derived ctypes
+    signature equals a frozen copy of the table that used to be written by hand (single pointers other than `const char*` are
+    c_void_p: the hand-written table spelled three kinds of them POINTER(int / long), the same machine word)."""
+    vp, i, l, f, d, s = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_char_p
+    frozen = {
+        "pscv_warp_cost_rows": (i, [vp, C.POINTER(vp), i, vp, vp, l, i, i, i, f, vp, i, i, i, i, i, i, i, i, i, i, vp]),   # pointer to pointer, long, float
+        "pscv_point_nn_dist": (i, [vp, l, vp, vp, l, d, d, d, d, d, i, i, d, vp, vp, vp, vp]),                   # double
+        "pscv_get_tuning": (i, [s, vp]),                                                                         # const char*, int* host out-parameter
+        "pscv_set_tuning_thread": (i, [s, i, i]),
+        "pscv_last_error": (s, []),                                                                              # const char* return, (void)
+        "pscv_fuse_depth_workspace": (l, [i, i]),                                                                # long return
+        "pscv_bn_finalize": (i, [vp, l, i, vp, vp, f, f, vp, vp, vp, vp, vp]),                                   # long long*
+    }
+    for name, (restype, argtypes) in frozen.items():
+        assert L.PROTOTYPES[name] == (restype, argtypes), name
+    lib = L.lib()
+    assert len(L.EXPORTS) == len(L.PROTOTYPES) >= 77
+    for name in L.EXPORTS:
+        fn = getattr(lib, name)
+        assert (fn.restype, list(fn.argtypes)) == L.PROTOTYPES[name], name
+    hdr = open(os.path.join(REPO, "include", "pscv.h")).read()
+    for name, value in re.findall(r"^#define PSCV_(\w+) (\d+)", hdr, flags=re.M):
+        assert getattr(L, name) == int(value), name
+    assert L.ABI_VERSION == 14 and (L.F32, L.BF16, L.F16) == (0, 1, 2) and L.MAX_SRC == 16 and L.COST_GROUPCORR == 3
+
+
+def test_header_parser_is_strict():
+    protos, consts = L.parse_header("#define PSCV_X 3\n/* int pscv_no(int a); */\nlong pscv_a(const float* p /*host*/, long n,\n double x);\nint pscv_b(void);\n")
+    assert protos == {"pscv_a": (C.c_long, [C.c_void_p, C.c_long, C.c_double]), "pscv_b": (C.c_int, [])} and consts == {"X": 3}
+    with pytest.raises(ValueError, match="not a prototype"):
+        L.parse_header("int pscv_a(int a;\nint pscv_b(void);\n")              # unbalanced parenthesis
+    with pytest.raises(ValueError, match="not a prototype"):
+        L.parse_header("float pscv_a(int a);\n")                               # a return type the ABI does not use
+    with pytest.raises(ValueError, match="unsigned int n"):
+        L.parse_header("int pscv_a(unsigned int n);\n")                        # no silent default to int
+    with pytest.raises(ValueError, match="size_t"):
+        L.parse_header("int pscv_a(const float* p, size_t n);\n")
+
+
+def test_storage_dtype_dispatch_rejects_fp32_before_any_launch():
+    """The 16-bit exports choose their instantiation through one dispatcher; fp32 (or any other code) is its error, named after the
+    export.  The pointers are never dereferenced on the host and nothing is launched."""
+    lib = L.lib()
+    for dtype in (L.F32, 7):
+        rc = lib.pscv_fuse_finish(64, 64, dtype, 64, 1, 2, 4, 4, None)
+        msg = lib.pscv_last_error().decode()
+        assert rc != 0 and "pscv_fuse_finish" in msg and f"dtype {dtype}" in msg and "bf16 or fp16" in msg, msg
+    rc = lib.pscv_leaky_relu_bwd(64, 64, L.F32, 16, 8, 0.1, 64, None)
+    msg = lib.pscv_last_error().decode()
+    assert rc != 0 and "pscv_leaky_relu_bwd" in msg and "dtype 0" in msg, msg
+
+
 # ---- conv3d weight packing vs a numpy emulation of the kernel ------------------------------------
 def _bf16(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(torch.bfloat16).to(torch.float32).numpy()

@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
+import re
 import subprocess
 import threading
 
@@ -16,34 +17,55 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSCV_LIB") or os.path.join(_HERE, "libpscv.so")     # (PSCV_LIB: A/B builds of scripts/dev)
 CSRC = os.path.join(_HERE, "csrc")
 
-# mirror of include/pscv.h
-ABI_VERSION = 14
-F32, BF16, F16 = 0, 1, 2
-GEOM_PROJ, GEOM_HOMOG = 0, 1
-COST_VARIANCE, COST_VARIANCE_CVP, COST_SOFTMIN, COST_GROUPCORR, COST_WARP_ONLY, COST_VARIANCE_PARTIAL = 0, 1, 2, 3, 4, 5
-CONV_S1, CONV_S2, CONV_T2, CONV_S1P8, CONV_S1C1, CONV_T2P8 = 0, 1, 2, 3, 4, 5
-EPI_RELU_PRE, EPI_RELU_POST = 1, 2
-MAX_SRC = 16
-CAM_FLOATS = 18
-GEO_MAX_SRC = 32
-GEO_CAM_FLOATS = 30
-FUSE_MAX_VIEWS = 64
-PM_MAX_SRC, PM_MAX_RADIUS, PM_MAX_TOPK = 31, 8, 8
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "pscv.h")
 
-EXPORTS = ("pscv_last_error", "pscv_abi_version", "pscv_set_tuning", "pscv_proj_cams", "pscv_homog_cams", "pscv_warp_cost",
-           "pscv_fuse_pairs", "pscv_fuse_finish", "pscv_geo_filter", "pscv_pack_conv2d_weights", "pscv_conv2d",
-           "pscv_pack_conv3d_weights", "pscv_conv3d", "pscv_softargmin", "pscv_train_workspace_floats", "pscv_bn_stats",
-           "pscv_bn_act", "pscv_bn_bwd_reduce", "pscv_bn_bwd_apply", "pscv_softargmin_bwd", "pscv_conv3d_wgrad_workspace",
-           "pscv_conv3d_wgrad", "pscv_warp_cost_bwd", "pscv_cvp_depth_hypos", "pscv_relu_bwd", "pscv_fuse_pairs_bwd", "pscv_pack_conv3d_weights_device", "pscv_conv2d_ex", "pscv_variance_finish", "pscv_softargmin_window",
-           "pscv_photo_warp", "pscv_photo_warp_bwd", "pscv_ssim", "pscv_ssim_bwd", "pscv_bn_finalize", "pscv_bn_bwd_coeffs", "pscv_cvp_cams", "pscv_homography_warp", "pscv_homography_warp_bwd", "pscv_prob_softargmin", "pscv_prob_softargmin_workspace",
-           "pscv_set_tuning_thread", "pscv_get_tuning", "pscv_conv3d_cat2", "pscv_uncert_net", "pscv_head_index_entropy", "pscv_image_prep", "pscv_conv3d_block8",
-           "pscv_bn_stats_grouped", "pscv_bn_finalize_grouped", "pscv_bn_act_grouped", "pscv_bn_bwd_reduce_grouped", "pscv_bn_bwd_coeffs_grouped",
-           "pscv_bn_bwd_apply_grouped", "pscv_pack_conv2d_weights_device", "pscv_leaky_relu_bwd", "pscv_leaky_relu_bwd_sum", "pscv_pack_conv2d_weights_device_ex", "pscv_warp_cost_rows",
-           "pscv_tail_sweep", "pscv_tail_sweep_workspace", "pscv_fuse_depth_workspace", "pscv_fuse_depth_pass",
-           "pscv_point_grid_workspace", "pscv_point_grid_build", "pscv_point_nn_dist", "pscv_dtu_cell_occupancy", "pscv_radius_mis_round",
-           "pscv_radius_mis_workspace", "pscv_radius_mis_compact", "pscv_colmap_fuse_workspace", "pscv_colmap_fuse_pass",
-           "pscv_patch_match_init", "pscv_patch_match_cost", "pscv_patch_match_half_step", "pscv_patch_match_filter",
-           "pscv_colmap_fuse_pass_normals")
+_RET = {"const char*": C.c_char_p, "int": C.c_int, "long": C.c_long}
+_SCALAR = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double}
+_PROTO = re.compile(r"(const char\*|int|long) (pscv_\w+)\(([^()]*)\)")
+
+
+def _param_type(param: str):
+    """`const char*` -> c_char_p, a pointer to pointers (a host array of device pointers) -> POINTER(c_void_p), any other pointer ->
+    c_void_p, int / long / float / double by name; anything else raises."""
+    if "*" in param:
+        if param.count("*") >= 2:
+            return C.POINTER(C.c_void_p)
+        return C.c_char_p if re.fullmatch(r"const char\s*\*\s*\w*", param) else C.c_void_p
+    ctype = re.sub(r"\s*\b\w+$", "", param)          # drop the parameter's name
+    if ctype not in _SCALAR:
+        raise ValueError(f"pscv.h: no ctypes type for parameter '{param}'")
+    return _SCALAR[ctype]
+
+
+def parse_header(text: str):
+    """(prototypes, constants) of the C ABI: {name: (restype, [argtypes])} for every `pscv_x(...);` declaration and {NAME: int} for
+    every `#define PSCV_NAME <int>`.  Whatever is left of the header after comments, preprocessor lines and the extern "C" braces is
+    a sequence of prototypes; a statement that is not one, or a parameter type the tables above do not know, raises ValueError."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^#define PSCV_(\w+) (-?\d+)\s*$", text, flags=re.M)}
+    text = re.sub(r'^\s*(#.*|extern "C" \{|\})$', "", text, flags=re.M)
+    protos = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = _PROTO.fullmatch(stmt)
+        if m is None:
+            raise ValueError(f"pscv.h: not a prototype: '{stmt[:80]}'")
+        params = [] if m[3].strip() in ("", "void") else [p.strip() for p in m[3].split(",")]
+        protos[m[2]] = (_RET[m[1]], [_param_type(p) for p in params])
+    return protos, consts
+
+
+with open(HEADER) as _fh:
+    PROTOTYPES, _CONSTS = parse_header(_fh.read())
+EXPORTS = tuple(PROTOTYPES)
+# The constants the package and its users read (a #define that is not a plain integer would be missing here: fail at import)
+CONSTANTS = ("ABI_VERSION", "F32", "BF16", "F16", "GEOM_PROJ", "GEOM_HOMOG", "COST_VARIANCE", "COST_VARIANCE_CVP", "COST_SOFTMIN",
+             "COST_GROUPCORR", "COST_WARP_ONLY", "COST_VARIANCE_PARTIAL", "CONV_S1", "CONV_S2", "CONV_T2", "CONV_S1P8", "CONV_S1C1",
+             "CONV_T2P8", "EPI_RELU_PRE", "EPI_RELU_POST", "MAX_SRC", "CAM_FLOATS", "GEO_MAX_SRC", "GEO_CAM_FLOATS", "FUSE_MAX_VIEWS",
+             "PM_MAX_SRC", "PM_MAX_RADIUS", "PM_MAX_TOPK")
+_missing = [n for n in CONSTANTS if n not in _CONSTS]
+if _missing:
+    raise ImportError(f"include/pscv.h does not define PSCV_{_missing[0]} as an integer")
+globals().update(_CONSTS)
 
 
 class PscvMissingError(RuntimeError):
@@ -66,7 +88,7 @@ def source_hash() -> str:
     import hashlib
     h = hashlib.sha256()
     files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".cpp")) or f == "Makefile")
-    for path in [os.path.join(CSRC, f) for f in files] + [os.path.join(os.path.dirname(_HERE), "include", "pscv.h")]:
+    for path in [os.path.join(CSRC, f) for f in files] + [HEADER]:
         h.update(os.path.basename(path).encode())
         with open(path, "rb") as fh:
             h.update(fh.read())
@@ -95,167 +117,9 @@ def build(verbose: bool = False, force: bool = False) -> str:
 
 
 def _declare(lib):
-    vp, i, l, f = C.c_void_p, C.c_int, C.c_long, C.c_float
-    lib.pscv_last_error.restype = C.c_char_p
-    lib.pscv_last_error.argtypes = []
-    lib.pscv_abi_version.restype = i
-    lib.pscv_abi_version.argtypes = []
-    lib.pscv_set_tuning.restype = i
-    lib.pscv_set_tuning.argtypes = [C.c_char_p, i]
-    lib.pscv_set_tuning_thread.restype = i
-    lib.pscv_set_tuning_thread.argtypes = [C.c_char_p, i, i]
-    lib.pscv_get_tuning.restype = i
-    lib.pscv_get_tuning.argtypes = [C.c_char_p, C.POINTER(i)]
-    lib.pscv_proj_cams.restype = i
-    lib.pscv_proj_cams.argtypes = [vp, i, i, i, vp, vp]
-    lib.pscv_homog_cams.restype = i
-    lib.pscv_homog_cams.argtypes = [vp, vp, i, i, f, vp, vp]
-    lib.pscv_fuse_pairs.restype = i
-    lib.pscv_fuse_pairs.argtypes = [C.POINTER(vp), C.POINTER(vp), i, i, vp, vp, i, i, i, i, i, vp]
-    lib.pscv_fuse_finish.restype = i
-    lib.pscv_fuse_finish.argtypes = [vp, vp, i, vp, i, i, i, i, vp]
-    lib.pscv_pack_conv2d_weights.restype = l
-    lib.pscv_pack_conv2d_weights.argtypes = [vp, i, i, i, i, i, vp]
-    lib.pscv_conv2d.restype = i
-    lib.pscv_conv2d.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, i, i, i, i, i, f, vp]
-    lib.pscv_bn_finalize.restype = i
-    lib.pscv_bn_finalize.argtypes = [vp, l, i, vp, vp, f, f, vp, vp, vp, vp, vp]
-    lib.pscv_bn_bwd_coeffs.restype = i
-    lib.pscv_bn_bwd_coeffs.argtypes = [vp, vp, vp, vp, l, i, vp, vp]
-    lib.pscv_photo_warp.restype = i
-    lib.pscv_photo_warp.argtypes = [vp] * 10 + [i, i, i, i, i, vp]
-    lib.pscv_photo_warp_bwd.restype = i
-    lib.pscv_photo_warp_bwd.argtypes = [vp] * 6 + [i, i, i, i, i, vp]
-    lib.pscv_ssim.restype = i
-    lib.pscv_ssim.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
-    lib.pscv_ssim_bwd.restype = i
-    lib.pscv_ssim_bwd.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
-    lib.pscv_softargmin_window.restype = i
-    lib.pscv_softargmin_window.argtypes = [vp, vp, vp, f, i, i, i, i, i, vp]
-    lib.pscv_variance_finish.restype = i
-    lib.pscv_variance_finish.argtypes = [vp, l, i, i, i, vp, vp]
-    lib.pscv_conv2d_ex.restype = i
-    lib.pscv_conv2d_ex.argtypes = [vp, i, vp, vp, vp, vp, i, i, vp, i, i, i, i, i, i, i, i, i, i, i, f, vp]
-    lib.pscv_geo_filter.restype = i
-    lib.pscv_geo_filter.argtypes = [vp, C.POINTER(vp), C.POINTER(i), i, vp, i, i, f, f, f, i, vp, vp, vp, vp, vp]
-    lib.pscv_fuse_depth_workspace.restype = l
-    lib.pscv_fuse_depth_workspace.argtypes = [i, i]
-    lib.pscv_fuse_depth_pass.restype = i
-    lib.pscv_fuse_depth_pass.argtypes = [i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp, f, i, f, f, vp, vp, vp,
-                                         vp, l, vp, vp, l, vp]
-    lib.pscv_colmap_fuse_workspace.restype = l
-    lib.pscv_colmap_fuse_workspace.argtypes = [i, i]
-    lib.pscv_patch_match_init.restype = i
-    lib.pscv_patch_match_init.argtypes = [vp, i, i, vp, f, f, i, i, vp]
-    lib.pscv_patch_match_cost.restype = i
-    lib.pscv_patch_match_cost.argtypes = [vp, vp, i, i, C.POINTER(vp), C.POINTER(i), i, vp, C.POINTER(vp), i, i, i, vp, vp, vp, vp]
-    lib.pscv_patch_match_half_step.restype = i
-    lib.pscv_patch_match_half_step.argtypes = [vp, vp, i, i, C.POINTER(vp), C.POINTER(i), i, vp, C.POINTER(vp), f, f, i, i, i, i, i,
-                                               i, i, f, f, vp, vp, vp]
-    lib.pscv_patch_match_filter.restype = i
-    lib.pscv_patch_match_filter.argtypes = [vp, vp, i, i, C.POINTER(vp), C.POINTER(i), i, vp, C.POINTER(vp), i, i, vp, vp, vp, vp]
-    lib.pscv_colmap_fuse_pass.restype = i
-    lib.pscv_colmap_fuse_pass.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp,
-                                          C.POINTER(l), l, f, f, i, i, vp, vp, vp, vp, vp, l, vp, vp, l, vp]
-    lib.pscv_colmap_fuse_pass_normals.restype = i
-    lib.pscv_colmap_fuse_pass_normals.argtypes = [i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), i, vp,
-                                                  C.POINTER(l), l, f, f, i, i, C.POINTER(vp), f, vp, vp, vp, vp, vp, l, vp, vp, l, vp]
-    d = C.c_double
-    lib.pscv_point_grid_workspace.restype = l
-    lib.pscv_point_grid_workspace.argtypes = [l]
-    lib.pscv_point_grid_build.restype = i
-    lib.pscv_point_grid_build.argtypes = [vp, l, d, d, d, d, vp, vp, l, vp]
-    lib.pscv_point_nn_dist.restype = i
-    lib.pscv_point_nn_dist.argtypes = [vp, l, vp, vp, l, d, d, d, d, d, i, i, d, vp, vp, vp, vp]
-    lib.pscv_dtu_cell_occupancy.restype = i
-    lib.pscv_dtu_cell_occupancy.argtypes = [vp, l, vp, d, vp, vp]
-    lib.pscv_radius_mis_round.restype = i
-    lib.pscv_radius_mis_round.argtypes = [vp, l, d, d, d, d, d, vp, vp, vp, vp]
-    lib.pscv_radius_mis_workspace.restype = l
-    lib.pscv_radius_mis_workspace.argtypes = [l]
-    lib.pscv_radius_mis_compact.restype = i
-    lib.pscv_radius_mis_compact.argtypes = [vp, l, vp, vp, vp, vp, vp, l, vp]
-    lib.pscv_warp_cost.restype = i
-    lib.pscv_warp_cost.argtypes = [vp, C.POINTER(vp), i, vp, vp, l, i, i, i, f, vp, i, i, i, i, i, i, i, i, i, vp]
-    lib.pscv_warp_cost_rows.restype = i
-    lib.pscv_warp_cost_rows.argtypes = [vp, C.POINTER(vp), i, vp, vp, l, i, i, i, f, vp, i, i, i, i, i, i, i, i, i, i, vp]
-    lib.pscv_pack_conv3d_weights.restype = l
-    lib.pscv_pack_conv3d_weights.argtypes = [vp, i, i, i, i, i, vp]
-    lib.pscv_pack_conv3d_weights_device.restype = i
-    lib.pscv_pack_conv3d_weights_device.argtypes = [vp, i, i, i, i, i, vp, vp]
-    lib.pscv_conv3d.restype = i
-    lib.pscv_conv3d.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, i, i, vp, i, i, i, i, i, i, i, i, i, i, i, vp]
-    lib.pscv_conv3d_cat2.restype = i
-    lib.pscv_conv3d_cat2.argtypes = [vp, i, i, vp, i, i, i, vp, vp, vp, vp, vp, i, i, vp, i, i, i, i, i, i, i, i, i, vp]
-    lib.pscv_uncert_net.restype = i
-    lib.pscv_uncert_net.argtypes = [vp, vp, vp, i, i, i, vp]
-    lib.pscv_head_index_entropy.restype = i
-    lib.pscv_head_index_entropy.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, i, vp, vp, C.c_long, vp, vp, i, i, i, i, vp]
-    lib.pscv_image_prep.restype = i
-    lib.pscv_image_prep.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp]
-    lib.pscv_conv3d_block8.restype = i
-    lib.pscv_conv3d_block8.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, i, i, vp, i, i, i, i, i, i, vp]
-    lib.pscv_softargmin.restype = i
-    lib.pscv_softargmin.argtypes = [vp, i, vp, l, i, vp, vp, vp, vp, vp, vp, i, f, i, i, i, i, i, vp]
-    lib.pscv_train_workspace_floats.restype = l
-    lib.pscv_train_workspace_floats.argtypes = []
-    lib.pscv_leaky_relu_bwd_sum.restype = i
-    lib.pscv_leaky_relu_bwd_sum.argtypes = [vp, vp, i, l, i, f, vp, vp, vp, vp]
-    lib.pscv_leaky_relu_bwd.restype = i
-    lib.pscv_leaky_relu_bwd.argtypes = [vp, vp, i, l, i, f, vp, vp]
-    lib.pscv_pack_conv2d_weights_device_ex.restype = i
-    lib.pscv_pack_conv2d_weights_device_ex.argtypes = [vp, i, i, i, i, i, i, vp, vp]
-    lib.pscv_pack_conv2d_weights_device.restype = i
-    lib.pscv_pack_conv2d_weights_device.argtypes = [vp, i, i, i, i, i, vp, vp]
-    lib.pscv_bn_stats_grouped.restype = i
-    lib.pscv_bn_stats_grouped.argtypes = [vp, i, l, i, i, vp, vp, vp]
-    lib.pscv_bn_finalize_grouped.restype = i
-    lib.pscv_bn_finalize_grouped.argtypes = [vp, l, i, i, vp, vp, f, f, vp, vp, vp, vp, vp]
-    lib.pscv_bn_act_grouped.restype = i
-    lib.pscv_bn_act_grouped.argtypes = [vp, i, l, i, i, vp, vp, i, i, vp, vp, vp]
-    lib.pscv_bn_bwd_reduce_grouped.restype = i
-    lib.pscv_bn_bwd_reduce_grouped.argtypes = [vp, vp, i, l, i, i, vp, vp, i, i, vp, vp, vp]
-    lib.pscv_bn_bwd_coeffs_grouped.restype = i
-    lib.pscv_bn_bwd_coeffs_grouped.argtypes = [vp, vp, vp, i, vp, l, i, i, vp, vp]
-    lib.pscv_bn_bwd_apply_grouped.restype = i
-    lib.pscv_bn_bwd_apply_grouped.argtypes = [vp, vp, i, l, i, i, vp, vp, i, i, vp, vp, vp, i, vp, vp]
-    lib.pscv_bn_stats.restype = i
-    lib.pscv_bn_stats.argtypes = [vp, i, l, i, vp, vp, vp]
-    lib.pscv_bn_act.restype = i
-    lib.pscv_bn_act.argtypes = [vp, i, l, i, vp, vp, i, vp, vp, vp]
-    lib.pscv_bn_bwd_reduce.restype = i
-    lib.pscv_bn_bwd_reduce.argtypes = [vp, vp, i, l, i, vp, vp, i, vp, vp, vp]
-    lib.pscv_bn_bwd_apply.restype = i
-    lib.pscv_bn_bwd_apply.argtypes = [vp, vp, i, l, i, vp, vp, i, vp, vp, vp, vp, vp]
-    lib.pscv_softargmin_bwd.restype = i
-    lib.pscv_softargmin_bwd.argtypes = [vp, vp, l, i, vp, vp, vp, vp, i, i, i, i, i, vp]
-    lib.pscv_relu_bwd.restype = i
-    lib.pscv_relu_bwd.argtypes = [vp, vp, i, l, i, vp, vp]
-    lib.pscv_fuse_pairs_bwd.restype = i
-    lib.pscv_fuse_pairs_bwd.argtypes = [C.POINTER(vp), C.POINTER(vp), i, i, vp, C.POINTER(vp), C.POINTER(vp), i, i, i, i, vp]
-    lib.pscv_conv3d_wgrad_workspace.restype = l
-    lib.pscv_conv3d_wgrad_workspace.argtypes = [i, i, i, i, i, i, i]
-    lib.pscv_conv3d_wgrad.restype = i
-    lib.pscv_conv3d_wgrad.argtypes = [vp, i, i, i, vp, i, i, i, i, i, i, i, i, i, vp, vp, i, vp]
-    lib.pscv_prob_softargmin_workspace.restype = C.c_long
-    lib.pscv_prob_softargmin_workspace.argtypes = [i, i, i, i]
-    lib.pscv_prob_softargmin.restype = i
-    lib.pscv_prob_softargmin.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, i, vp, C.c_long, vp, vp, C.c_long, vp, vp, i, i, i, i, vp]
-    lib.pscv_tail_sweep.restype = i
-    lib.pscv_tail_sweep.argtypes = [vp, i, i, i, vp, vp, vp, vp, i, vp, i, i, vp, vp, vp, vp, i, vp, vp, l, vp, l, vp, vp, i, i, i, i, vp]
-    lib.pscv_tail_sweep_workspace.restype = C.c_long
-    lib.pscv_tail_sweep_workspace.argtypes = [i, i, i, i]
-    lib.pscv_homography_warp.restype = i
-    lib.pscv_homography_warp.argtypes = [vp, vp, i, vp, i, i, i, i, i, i, vp]
-    lib.pscv_homography_warp_bwd.restype = i
-    lib.pscv_homography_warp_bwd.argtypes = [vp, vp, i, vp, i, i, i, i, i, i, vp]
-    lib.pscv_cvp_cams.restype = i
-    lib.pscv_cvp_cams.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
-    lib.pscv_cvp_depth_hypos.restype = i
-    lib.pscv_cvp_depth_hypos.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp]
-    lib.pscv_warp_cost_bwd.restype = i
-    lib.pscv_warp_cost_bwd.argtypes = [vp, C.POINTER(vp), i, vp, vp, l, i, i, i, f, vp, vp, C.POINTER(vp), vp, i, i, i, i, i,
-                                       i, i, i, i, vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
 
 
 def lib():

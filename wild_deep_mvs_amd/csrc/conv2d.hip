@@ -505,17 +505,11 @@ static int c2w_launch(Conv2dArgs& a, hipStream_t st) {
     a.nth = c2_ceil_div(a.Ho, C2W_TH); a.ntw = c2_ceil_div(a.Wo, C2_TW);
     const long tiles = (long)a.B * a.nth * a.ntw;
     if (tiles <= 0 || tiles > 0x7fffffffL) { set_error("pscv_conv2d: bad grid %ld", tiles); return -1; }
-    auto kern = conv2d_wlds_kernel<H, NT, CIN>;
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS);
-        if (e != hipSuccess) { set_error("pscv_conv2d: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e)); return -2; }
-    }
     const int n_cu = device_cu_count();            // of the current device (cached per device)
     if (n_cu <= 0) { set_error("pscv_conv2d: device query failed"); return -2; }
     const int per_cu = LDS <= 80 * 1024 ? 2 : 1;
     const long grid = tiles < (long)n_cu * per_cu ? tiles : (long)n_cu * per_cu;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C2W_THREADS), LDS, st, a, (int)tiles);
-    return 0;
+    return launch("pscv_conv2d", conv2d_wlds_kernel<H, NT, CIN>, dim3((unsigned)grid), dim3(C2W_THREADS), LDS, st, a, (int)tiles);
 }
 
 template <typename H, int CIN, int NT, int KS, int STRIDE>
@@ -529,15 +523,7 @@ static int c2_launch(Conv2dArgs& a, int n_split, hipStream_t st) {
     a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw);
     const long nblk = (long)a.B * a.nth * a.ntw;
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv2d: bad grid %ld", nblk); return -1; }
-    auto kern = conv2d_kernel<H, CIN, NT, KS, STRIDE>;
-    if (LDS > 60000) {
-        {
-            hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS);
-            if (e != hipSuccess) { set_error("pscv_conv2d: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e)); return -2; }
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
-    return 0;
+    return launch("pscv_conv2d", conv2d_kernel<H, CIN, NT, KS, STRIDE>, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
 }
 
 template <typename H>
@@ -673,10 +659,7 @@ extern "C" int pscv_conv2d_ex(const void* in, int dtype, const uint16_t* packed,
     PSCV_CHECK_ARG(neg_slope >= 0.0f && neg_slope <= 1.0f, "pscv_conv2d: neg_slope=%g outside [0,1]", (double)neg_slope);
     a.cout = c_out; a.neg_slope = neg_slope;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int rc = dtype == PSCV_BF16 ? c2_dispatch<bf16_t>(a, c_in, c_out, ks, stride, st) : c2_dispatch<f16_t>(a, c_in, c_out, ks, stride, st);
-    if (rc) return rc;
-    PSCV_CHECK_LAUNCH("pscv_conv2d");
-    return 0;
+    return with_half("pscv_conv2d", dtype, [&](auto t) { return c2_dispatch<typename decltype(t)::type>(a, c_in, c_out, ks, stride, st); });
 }
 
 extern "C" int pscv_conv2d(const void* in, int dtype, const uint16_t* packed, const float* scale, const float* bias, void* out,

@@ -552,13 +552,7 @@ static int launch_conv(ConvArgs& a, int n_split, hipStream_t st) {
     a.mg_td = fast_div_magic(a.ntd); a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw);
     const long nblk = (long)a.B * a.ntd * a.nth * a.ntw;
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d: bad grid %ld", nblk); return -1; }
-    auto kern = conv3d_kernel<H, CIN, NT, KIND, TD, TH>;
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS);
-        if (e != hipSuccess) { set_error("pscv_conv3d: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e)); return -2; }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
-    return 0;
+    return launch("pscv_conv3d", conv3d_kernel<H, CIN, NT, KIND, TD, TH>, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
 }
 
 // Tile choice.  Large volumes: 4x4x16 (S1), 2x2x16 (S2), 2x4x16 input voxels (T2) with all NT output tiles in one
@@ -750,9 +744,5 @@ extern "C" int pscv_conv3d(const void* in, int dtype, int in_cstride, int in_cof
     else { a.Do = 2 * Di; a.Ho = 2 * Hi; a.Wo = 2 * Wi; }
     a.cout = c_out; a.epi = epi_flags;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int rc = dtype == PSCV_BF16 ? launch_channels<bf16_t>(a, c_in, c_out, kind, st)
-                                      : launch_channels<f16_t>(a, c_in, c_out, kind, st);
-    if (rc) return rc;
-    PSCV_CHECK_LAUNCH("pscv_conv3d");
-    return 0;
+    return with_half("pscv_conv3d", dtype, [&](auto t) { return launch_channels<typename decltype(t)::type>(a, c_in, c_out, kind, st); });
 }

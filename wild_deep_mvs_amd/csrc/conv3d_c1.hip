@@ -528,14 +528,8 @@ __global__ __launch_bounds__(256) void index_entropy_merge_kernel(const float* _
 
 template <typename H, int CIN>
 static int c1_launch(const C1Args& a, long nblk, hipStream_t st) {
-    auto kern = conv3d_c1_kernel<H, CIN>;
     const size_t lds = (size_t)(a.nb * C1_P + 2) * C1_PS * CIN * 2;
-    if (lds > 60000) {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds);
-        if (e != hipSuccess) { set_error("pscv_conv3d(c1): hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e)); return -2; }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), lds, st, a);
-    return 0;
+    return launch("pscv_conv3d(c1)", conv3d_c1_kernel<H, CIN>, dim3((unsigned)nblk), dim3(256), lds, st, a);
 }
 
 }  // namespace pscv
@@ -590,36 +584,31 @@ static int c1_dispatch(const void* in, int dtype, int in_cstride, int in_coff, c
     }
     if (sweep) {
         const size_t lds = (size_t)C1S_NSLOT * C1_PS * 16;
-        if (part && ie) {
-            if (dtype == PSCV_BF16) hipLaunchKernelGGL((conv3d_c1_sweep_kernel<bf16_t, 2>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((conv3d_c1_sweep_kernel<f16_t, 2>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-            if (a.ndc > 1) {
-                const long npix = (long)B * Hh * W;
-                hipLaunchKernelGGL(index_entropy_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, part, a.ndc, B, (long)Hh * W,
-                                   o_index, o_entropy);
-            }
-            return 0;
-        }
-        if (part) {
-            if (dtype == PSCV_BF16) hipLaunchKernelGGL((conv3d_c1_sweep_kernel<bf16_t, 1>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((conv3d_c1_sweep_kernel<f16_t, 1>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-        } else {
-            if (dtype == PSCV_BF16) hipLaunchKernelGGL((conv3d_c1_sweep_kernel<bf16_t, 0>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-            else hipLaunchKernelGGL((conv3d_c1_sweep_kernel<f16_t, 0>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-        }
-        if (part) {
-            const long npix = (long)B * Hh * W;
+        const long npix = (long)B * Hh * W;
+        const int fuse = part ? (ie ? 2 : 1) : 0;     // FUSE of the kernel: 0 logits only, 1 + softmax partials, 2 + index / entropy partials
+        const int rc = with_half("pscv_conv3d(c1)", dtype, [&](auto t) {
+            using H = typename decltype(t)::type;
+            const dim3 grid((unsigned)nblk);
+            if (fuse == 2) return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 2>, grid, dim3(256), lds, st, a);
+            if (fuse == 1) return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 1>, grid, dim3(256), lds, st, a);
+            return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 0>, grid, dim3(256), lds, st, a);
+        });
+        if (rc) return rc;
+        if (fuse == 2 && a.ndc > 1)
+            hipLaunchKernelGGL(index_entropy_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, part, a.ndc, B, (long)Hh * W,
+                               o_index, o_entropy);
+        if (fuse == 1)
             hipLaunchKernelGGL(softargmin_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, part, reinterpret_cast<const float*>(out),
                                a.ndc, B, D, (long)Hh * W, o_depth, o_conf);
-        }
         return 0;
     }
-    if (dtype == PSCV_BF16 && c_in == 8) return c1_launch<bf16_t, 8>(a, nblk, st);
-    if (dtype == PSCV_BF16 && c_in == 16) return c1_launch<bf16_t, 16>(a, nblk, st);
-    if (dtype == PSCV_F16 && c_in == 8) return c1_launch<f16_t, 8>(a, nblk, st);
-    if (dtype == PSCV_F16 && c_in == 16) return c1_launch<f16_t, 16>(a, nblk, st);
-    set_error("pscv_conv3d(c1): c_in=%d dtype=%d not supported (c_in 8 or 16)", c_in, dtype);
-    return -1;
+    return with_half("pscv_conv3d(c1)", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        if (c_in == 8) return c1_launch<H, 8>(a, nblk, st);
+        if (c_in == 16) return c1_launch<H, 16>(a, nblk, st);
+        set_error("pscv_conv3d(c1): c_in=%d dtype=%d not supported (c_in 8 or 16)", c_in, dtype);
+        return -1;
+    });
 }
 
 // merge launch for other producers of the same partials (conv3d_tail.hip)

@@ -703,13 +703,7 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
 template <typename H, int CIN, int PD, int COUT = 8>
 static int sweepc_launch_t(pscv::SweepArgs& a, long nblk, hipStream_t st) {
     using namespace pscv;
-    constexpr int lds = ScGeom<CIN>::LDS;
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(conv3d_sweepc_kernel<H, CIN, PD, COUT>), lds);
-        if (e != hipSuccess) { set_error("pscv_conv3d(sweep): hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
-    }
-    hipLaunchKernelGGL((conv3d_sweepc_kernel<H, CIN, PD, COUT>), dim3((unsigned)nblk), dim3(256), lds, st, a);
-    return 0;
+    return launch("pscv_conv3d(sweep)", conv3d_sweepc_kernel<H, CIN, PD, COUT>, dim3((unsigned)nblk), dim3(256), ScGeom<CIN>::LDS, st, a);
 }
 template <typename H, int CIN, int COUT = 8>
 static int sweepc_launch_pd(pscv::SweepArgs& a, long nblk, hipStream_t st) {
@@ -756,9 +750,11 @@ int pscv_conv3d_sweepc_launch(const void* in, int dtype, int c_in, int c_out, in
     const long nblk = tiles * a.ndc;
     a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(sweep): bad grid %ld", nblk); return -1; }
-    if (c_out == 16) return dtype == PSCV_BF16 ? sweepc_launch_pd<bf16_t, 16, 16>(a, nblk, st) : sweepc_launch_pd<f16_t, 16, 16>(a, nblk, st);
-    if (c_in == 8) return dtype == PSCV_BF16 ? sweepc_launch_pd<bf16_t, 8>(a, nblk, st) : sweepc_launch_pd<f16_t, 8>(a, nblk, st);
-    return dtype == PSCV_BF16 ? sweepc_launch_pd<bf16_t, 16>(a, nblk, st) : sweepc_launch_pd<f16_t, 16>(a, nblk, st);
+    return with_half("pscv_conv3d(sweep)", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        if (c_out == 16) return sweepc_launch_pd<H, 16, 16>(a, nblk, st);
+        return c_in == 8 ? sweepc_launch_pd<H, 8>(a, nblk, st) : sweepc_launch_pd<H, 16>(a, nblk, st);
+    });
 }
 
 // entry used by pscv_conv3d (conv3d.hip) for kind == PSCV_CONV_S1P8
@@ -797,21 +793,14 @@ int pscv_conv3d_sweep8_launch(const void* in, int dtype, int in_cstride, int in_
         a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
         if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(sweep): bad grid %ld", nblk); return -1; }
         const int pd = g_sweep_kdm_pd > 0 ? g_sweep_kdm_pd : 1;
-        const int ti = (dtype == PSCV_BF16 ? 0 : 1) + (skip ? 2 : 0) + (pd >= 2 ? 4 : 0);
-#define PSCV_KDM(I, HT, SK, PDV)                                                                                                  \
-        if (ti == I) {                                                                                                            \
-            {                                                                                                   \
-                hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(conv3d_sweep8_kdm_kernel<HT, SK, PDV>), \
-                                                   KM_LDS);                           \
-                if (e != hipSuccess) { set_error("pscv_conv3d(sweep): hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; } \
-            }                                                                                                                     \
-            hipLaunchKernelGGL((conv3d_sweep8_kdm_kernel<HT, SK, PDV>), dim3((unsigned)nblk), dim3(256), KM_LDS, st, a);          \
-            return 0;                                                                                                             \
-        }
-        PSCV_KDM(0, bf16_t, false, 1) PSCV_KDM(1, f16_t, false, 1) PSCV_KDM(2, bf16_t, true, 1) PSCV_KDM(3, f16_t, true, 1)
-        PSCV_KDM(4, bf16_t, false, 2) PSCV_KDM(5, f16_t, false, 2) PSCV_KDM(6, bf16_t, true, 2) PSCV_KDM(7, f16_t, true, 2)
-#undef PSCV_KDM
-        return -1;
+        return with_half("pscv_conv3d(sweep)", dtype, [&](auto t) {
+            using H = typename decltype(t)::type;
+            const dim3 grid((unsigned)nblk);
+            if (pd >= 2) return skip ? launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, true, 2>, grid, dim3(256), KM_LDS, st, a)
+                                     : launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, false, 2>, grid, dim3(256), KM_LDS, st, a);
+            return skip ? launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, true, 1>, grid, dim3(256), KM_LDS, st, a)
+                        : launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, false, 1>, grid, dim3(256), KM_LDS, st, a);
+        });
     }
     const bool tall = g_sweep_th16 && Hh >= 16;
     const int TH = tall ? 16 : 8;
@@ -833,20 +822,10 @@ int pscv_conv3d_sweep8_launch(const void* in, int dtype, int in_cstride, int in_
     const long nblk = tiles * a.ndc;
     a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(sweep): bad grid %ld", nblk); return -1; }
-    const int ti = (dtype == PSCV_BF16 ? 0 : 1) + (tall ? 2 : 0);
-    const void* kern = ti == 0 ? reinterpret_cast<const void*>(conv3d_sweep8_kernel<bf16_t, 8>)
-                     : ti == 1 ? reinterpret_cast<const void*>(conv3d_sweep8_kernel<f16_t, 8>)
-                     : ti == 2 ? reinterpret_cast<const void*>(conv3d_sweep8_kernel<bf16_t, 16>)
-                               : reinterpret_cast<const void*>(conv3d_sweep8_kernel<f16_t, 16>);
-    const int lds = tall ? SwGeom<16>::LDS : SwGeom<8>::LDS;
-    {
-        hipError_t e = ensure_dyn_lds(kern, lds);
-        if (e != hipSuccess) { set_error("pscv_conv3d(sweep): hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
-    }
-    const dim3 grid((unsigned)nblk);
-    if (ti == 0) hipLaunchKernelGGL((conv3d_sweep8_kernel<bf16_t, 8>), grid, dim3(256), lds, st, a);
-    else if (ti == 1) hipLaunchKernelGGL((conv3d_sweep8_kernel<f16_t, 8>), grid, dim3(256), lds, st, a);
-    else if (ti == 2) hipLaunchKernelGGL((conv3d_sweep8_kernel<bf16_t, 16>), grid, dim3(512), lds, st, a);
-    else hipLaunchKernelGGL((conv3d_sweep8_kernel<f16_t, 16>), grid, dim3(512), lds, st, a);
-    return 0;
+    return with_half("pscv_conv3d(sweep)", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        const dim3 grid((unsigned)nblk);
+        return tall ? launch("pscv_conv3d(sweep)", conv3d_sweep8_kernel<H, 16>, grid, dim3(512), SwGeom<16>::LDS, st, a)
+                    : launch("pscv_conv3d(sweep)", conv3d_sweep8_kernel<H, 8>, grid, dim3(256), SwGeom<8>::LDS, st, a);
+    });
 }

@@ -280,6 +280,8 @@ int pscv_conv3d_sweep_s2_launch(const void* in, int dtype, int in_cstride, int i
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(s2 sweep): bad grid %ld", nblk); return -1; }
     a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
     const int nt = (c_out + 15) / 16;
-    if (dtype == PSCV_BF16) return nt == 1 ? s2s_launch<bf16_t, 1>(a, nblk, st) : s2s_launch<bf16_t, 2>(a, nblk, st);
-    return nt == 1 ? s2s_launch<f16_t, 1>(a, nblk, st) : s2s_launch<f16_t, 2>(a, nblk, st);
+    return with_half("pscv_conv3d(s2 sweep)", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        return nt == 1 ? s2s_launch<H, 1>(a, nblk, st) : s2s_launch<H, 2>(a, nblk, st);
+    });
 }

@@ -207,7 +207,7 @@ int pscv_conv3d_t2p8_launch(const void* in, int dtype, int in_cstride, int in_co
     a.mg_td = fast_div_magic(a.ntd); a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw);
     const long nblk = (long)B * a.ntd * a.nth * a.ntw;
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(t2p8): bad grid %ld", nblk); return -1; }
-    if (dtype == PSCV_BF16) hipLaunchKernelGGL(conv3d_t2p8_kernel<bf16_t>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(conv3d_t2p8_kernel<f16_t>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-    return 0;
+    return with_half("pscv_conv3d(t2p8)", dtype, [&](auto t) {
+        return launch("pscv_conv3d(t2p8)", conv3d_t2p8_kernel<typename decltype(t)::type>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+    });
 }

@@ -491,18 +491,15 @@ extern "C" int pscv_tail_sweep(const void* in, int dtype, int in_cstride, int in
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool up_post = (up_epi & PSCV_EPI_RELU_POST) != 0, hd_clamp = (hd_epi & (PSCV_EPI_RELU_PRE | PSCV_EPI_RELU_POST)) != 0;
     const bool plain = !up_post && !hd_clamp;
-#define PSCV_TAIL_LAUNCH(HT, P, C, F)                                                                                  \
-    {                                                                                                                  \
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(conv3d_tail_kernel<HT, P, C, F>), TL_LDS);         \
-        if (e != hipSuccess) { set_error("pscv_tail_sweep: hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; } \
-        hipLaunchKernelGGL((conv3d_tail_kernel<HT, P, C, F>), dim3((unsigned)nblk), dim3(256), TL_LDS, st, a);         \
-    }
-#define PSCV_TAIL_DT(HT)                                                                                               \
-    if (plain) { if (fuse) PSCV_TAIL_LAUNCH(HT, false, false, true) else PSCV_TAIL_LAUNCH(HT, false, false, false) }   \
-    else { if (fuse) PSCV_TAIL_LAUNCH(HT, true, true, true) else PSCV_TAIL_LAUNCH(HT, true, true, false) }
-    if (dtype == PSCV_BF16) { PSCV_TAIL_DT(bf16_t) } else { PSCV_TAIL_DT(f16_t) }
-#undef PSCV_TAIL_DT
-#undef PSCV_TAIL_LAUNCH
+    const int rc = with_half("pscv_tail_sweep", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        const dim3 grid((unsigned)nblk);
+        if (plain) return fuse ? launch("pscv_tail_sweep", conv3d_tail_kernel<H, false, false, true>, grid, dim3(256), TL_LDS, st, a)
+                               : launch("pscv_tail_sweep", conv3d_tail_kernel<H, false, false, false>, grid, dim3(256), TL_LDS, st, a);
+        return fuse ? launch("pscv_tail_sweep", conv3d_tail_kernel<H, true, true, true>, grid, dim3(256), TL_LDS, st, a)
+                    : launch("pscv_tail_sweep", conv3d_tail_kernel<H, true, true, false>, grid, dim3(256), TL_LDS, st, a);
+    });
+    if (rc) return rc;
     if (fuse) pscv_softargmin_merge_launch(workspace, logits, ndc, B, D, (long)H * W, out_depth, out_conf, st);
     PSCV_CHECK_LAUNCH("pscv_tail_sweep");
     return 0;

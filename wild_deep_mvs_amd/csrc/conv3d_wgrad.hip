@@ -364,13 +364,7 @@ template <typename H, int S, int TZ, int TY, int NB, int NA = 1>
 static int wgrad_launch(const WgradArgs& a, const WgPlan& p, hipStream_t st) {
     using G = WgGeom<S, TZ, TY, NB, NA>;
     static_assert(G::LDS <= 160 * 1024, "wgrad tile does not fit the LDS");
-    auto kern = wgrad_kernel<H, S, TZ, TY, NB, NA>;
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), G::LDS);
-        if (e != hipSuccess) { set_error("pscv_conv3d_wgrad: hipFuncSetAttribute(%d B LDS): %s", G::LDS, hipGetErrorString(e)); return -2; }
-    }
-    hipLaunchKernelGGL(kern, dim3(p.nblk, p.ny), dim3(256), G::LDS, st, a);
-    return 0;
+    return launch("pscv_conv3d_wgrad", wgrad_kernel<H, S, TZ, TY, NB, NA>, dim3(p.nblk, p.ny), dim3(256), G::LDS, st, a);
 }
 
 }  // namespace pscv
@@ -408,16 +402,14 @@ extern "C" int pscv_conv3d_wgrad(const void* p, int p_cstride, int p_coff, int c
     a.abl = pscv::g_fuse_c0;
 #endif
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc;
-#define PSCV_WG(HT)                                                                       \
-    if (pl.tz == 1 && pl.na == 4) rc = pl.nb == 2 ? wgrad_launch<HT, 1, 1, 8, 2, 4>(a, pl, st) : wgrad_launch<HT, 1, 1, 8, 1, 4>(a, pl, st); \
-    else if (pl.tz == 1) rc = pl.nb == 2 ? wgrad_launch<HT, 1, 1, 8, 2>(a, pl, st) : wgrad_launch<HT, 1, 1, 8, 1>(a, pl, st); \
-    else if (stride == 1) rc = pl.nb == 2 ? wgrad_launch<HT, 1, 2, 4, 2>(a, pl, st) : wgrad_launch<HT, 1, 2, 4, 1>(a, pl, st); \
-    else rc = pl.nb == 2 ? wgrad_launch<HT, 2, 2, 2, 2>(a, pl, st) : wgrad_launch<HT, 2, 2, 2, 1>(a, pl, st);
-    if (dtype == PSCV_BF16) { PSCV_WG(bf16_t) } else { PSCV_WG(f16_t) }
-#undef PSCV_WG
+    const int rc = with_half("pscv_conv3d_wgrad", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        if (pl.tz == 1 && pl.na == 4) return pl.nb == 2 ? wgrad_launch<H, 1, 1, 8, 2, 4>(a, pl, st) : wgrad_launch<H, 1, 1, 8, 1, 4>(a, pl, st);
+        if (pl.tz == 1) return pl.nb == 2 ? wgrad_launch<H, 1, 1, 8, 2>(a, pl, st) : wgrad_launch<H, 1, 1, 8, 1>(a, pl, st);
+        if (stride == 1) return pl.nb == 2 ? wgrad_launch<H, 1, 2, 4, 2>(a, pl, st) : wgrad_launch<H, 1, 2, 4, 1>(a, pl, st);
+        return pl.nb == 2 ? wgrad_launch<H, 2, 2, 2, 2>(a, pl, st) : wgrad_launch<H, 2, 2, 2, 1>(a, pl, st);
+    });
     if (rc) return rc;
-    PSCV_CHECK_LAUNCH("pscv_conv3d_wgrad");
     const int n = 27 * ca * cb;
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3((n + 15) / 16), dim3(256), 0, st, workspace, pl.nblk, ca, cb, pl.ca16, pl.cb16, dw, accumulate, pl.tz == 1 ? 1 : 0);
     PSCV_CHECK_LAUNCH("pscv_conv3d_wgrad(finish)");

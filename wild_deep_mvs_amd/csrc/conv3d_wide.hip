@@ -314,16 +314,12 @@ template <typename H, int CIN, int NT>
 static int widep_launch(const WideArgs& a, long nblk, hipStream_t st) {
     constexpr int LDS = wp_lds(CIN, NT);
     static_assert(LDS <= 160 * 1024, "brick + weight double buffer do not fit the LDS");
-    auto kern = conv3d_widep_kernel<H, CIN, NT>;
-    hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS);
-    if (e != hipSuccess) { set_error("pscv_conv3d(wide): hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e)); return -2; }
     const int n_cu = device_cu_count();            // of the current device (several GPUs in one process: not a per-process constant)
     if (n_cu <= 0) { set_error("pscv_conv3d(wide): device query failed"); return -2; }
     // one workgroup per CU; a multiple of 8 where the device has that many (the XCD-contiguous walk), the kernel takes any grid
     const long per_dev = n_cu >= 8 ? (long)(n_cu & ~7) : (long)n_cu;
     const long grid = nblk < per_dev ? nblk : per_dev;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, st, a, (int)nblk);
-    return 0;
+    return launch("pscv_conv3d(wide)", conv3d_widep_kernel<H, CIN, NT>, dim3((unsigned)grid), dim3(512), LDS, st, a, (int)nblk);
 }
 
 }  // namespace pscv
@@ -360,9 +356,9 @@ int pscv_conv3d_wide_launch(const void* in, int dtype, int in_cstride, int in_co
     const int nt = c_out / 16;
     // a batch item's input volume is addressed through a 32-bit buffer descriptor
     if ((long)D * Hh * W * in_cstride * 2 >= 0x7fffffffL) return 1;
-#define PSCV_WIDE_CASE(HT, CI, NTV) if (c_in == CI && nt == NTV) return widep_launch<HT, CI, NTV>(a, nblk, st);
-    if (dtype == PSCV_BF16) { PSCV_WIDE_CASE(bf16_t, 64, 4) PSCV_WIDE_CASE(bf16_t, 64, 2) PSCV_WIDE_CASE(bf16_t, 32, 4) PSCV_WIDE_CASE(bf16_t, 32, 2) }
-    else { PSCV_WIDE_CASE(f16_t, 64, 4) PSCV_WIDE_CASE(f16_t, 64, 2) PSCV_WIDE_CASE(f16_t, 32, 4) PSCV_WIDE_CASE(f16_t, 32, 2) }
-#undef PSCV_WIDE_CASE
-    return 1;
+    return with_half("pscv_conv3d(wide)", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        if (c_in == 64) return nt == 4 ? widep_launch<H, 64, 4>(a, nblk, st) : widep_launch<H, 64, 2>(a, nblk, st);
+        return nt == 4 ? widep_launch<H, 32, 4>(a, nblk, st) : widep_launch<H, 32, 2>(a, nblk, st);
+    });
 }

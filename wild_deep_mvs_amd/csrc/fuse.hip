@@ -155,15 +155,15 @@ extern "C" int pscv_variance_finish(const float* sums, long n, int n_views, int 
     PSCV_CHECK_ARG(sums && out, "pscv_variance_finish: null pointer argument");
     PSCV_CHECK_ARG(n > 0 && n % 8 == 0 && n_views >= 2, "pscv_variance_finish: bad sizes");
     PSCV_CHECK_ARG(cost == PSCV_COST_VARIANCE || cost == PSCV_COST_VARIANCE_CVP, "pscv_variance_finish: cost %d must be VARIANCE or VARIANCE_CVP", cost);
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_variance_finish: dtype %d must be bf16 or fp16", dtype);
     const long nchunk = n / 8;
     const unsigned nblk = (unsigned)((nchunk + 255) / 256);
     const float invN = 1.0f / (float)n_views, invN2 = 1.0f / ((float)n_views * (float)n_views);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == PSCV_BF16) hipLaunchKernelGGL(variance_finish_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, sums, sums + n, reinterpret_cast<bf16_t*>(out), nchunk, invN, invN2, cost == PSCV_COST_VARIANCE_CVP);
-    else hipLaunchKernelGGL(variance_finish_kernel<f16_t>, dim3(nblk), dim3(256), 0, st, sums, sums + n, reinterpret_cast<f16_t*>(out), nchunk, invN, invN2, cost == PSCV_COST_VARIANCE_CVP);
-    PSCV_CHECK_LAUNCH("pscv_variance_finish");
-    return 0;
+    return with_half("pscv_variance_finish", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        return launch("pscv_variance_finish", variance_finish_kernel<H>, dim3(nblk), dim3(256), 0, st, sums, sums + n, reinterpret_cast<H*>(out), nchunk,
+                      invN, invN2, cost == PSCV_COST_VARIANCE_CVP);
+    });
 }
 
 extern "C" int pscv_fuse_pairs_bwd(const void* const* interm, const float* const* uncert, int n_src, int dtype, const void* grad_fused,
@@ -171,7 +171,6 @@ extern "C" int pscv_fuse_pairs_bwd(const void* const* interm, const float* const
     using namespace pscv;
     PSCV_CHECK_ARG(interm && uncert && grad_fused && dinterm && duncert, "pscv_fuse_pairs_bwd: null pointer argument");
     PSCV_CHECK_ARG(n_src >= 1 && n_src <= PSCV_MAX_SRC, "pscv_fuse_pairs_bwd: n_src=%d outside [1,%d]", n_src, PSCV_MAX_SRC);
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_fuse_pairs_bwd: dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(B > 0 && D > 0 && h > 0 && w > 0, "pscv_fuse_pairs_bwd: bad sizes");
     FuseBwdArgs a;
     for (int i = 0; i < PSCV_MAX_SRC; ++i) {
@@ -183,25 +182,23 @@ extern "C" int pscv_fuse_pairs_bwd(const void* const* interm, const float* const
     const long npix = (long)B * h * w;
     const unsigned nblk = (unsigned)((npix + FB_PX - 1) / FB_PX);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == PSCV_BF16) hipLaunchKernelGGL(fuse_pairs_bwd_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(fuse_pairs_bwd_kernel<f16_t>, dim3(nblk), dim3(256), 0, st, a);
-    PSCV_CHECK_LAUNCH("pscv_fuse_pairs_bwd");
-    return 0;
+    return with_half("pscv_fuse_pairs_bwd", dtype, [&](auto t) {
+        return launch("pscv_fuse_pairs_bwd", fuse_pairs_bwd_kernel<typename decltype(t)::type>, dim3(nblk), dim3(256), 0, st, a);
+    });
 }
 
 extern "C" int pscv_fuse_finish(const float* partial, const float* wsum, int dtype, void* out, int B, int D, int h, int w,
                                 void* stream) {
     using namespace pscv;
     PSCV_CHECK_ARG(partial && wsum && out, "pscv_fuse_finish: null pointer argument");
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_fuse_finish: dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(B > 0 && D > 0 && h > 0 && w > 0, "pscv_fuse_finish: bad sizes");
     const long nvox = (long)B * D * h * w;
     const unsigned nblk = (unsigned)((nvox + 255) / 256);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == PSCV_BF16) hipLaunchKernelGGL(fuse_finish_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, partial, wsum, reinterpret_cast<bf16_t*>(out), B, D, h * w);
-    else hipLaunchKernelGGL(fuse_finish_kernel<f16_t>, dim3(nblk), dim3(256), 0, st, partial, wsum, reinterpret_cast<f16_t*>(out), B, D, h * w);
-    PSCV_CHECK_LAUNCH("pscv_fuse_finish");
-    return 0;
+    return with_half("pscv_fuse_finish", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        return launch("pscv_fuse_finish", fuse_finish_kernel<H>, dim3(nblk), dim3(256), 0, st, partial, wsum, reinterpret_cast<H*>(out), B, D, h * w);
+    });
 }
 
 extern "C" int pscv_fuse_pairs(const void* const* interm, const float* const* uncert, int n_src, int dtype, void* out,
@@ -209,7 +206,6 @@ extern "C" int pscv_fuse_pairs(const void* const* interm, const float* const* un
     using namespace pscv;
     PSCV_CHECK_ARG(interm && uncert && out, "pscv_fuse_pairs: null pointer argument");
     PSCV_CHECK_ARG(n_src >= 1 && n_src <= PSCV_MAX_SRC, "pscv_fuse_pairs: n_src=%d outside [1,%d]", n_src, PSCV_MAX_SRC);
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_fuse_pairs: dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(B > 0 && D > 0 && h > 0 && w > 0, "pscv_fuse_pairs: bad sizes");
     FuseArgs a;
     for (int i = 0; i < PSCV_MAX_SRC; ++i) { a.interm[i] = i < n_src ? interm[i] : nullptr; a.uncert[i] = i < n_src ? uncert[i] : nullptr; }
@@ -218,8 +214,7 @@ extern "C" int pscv_fuse_pairs(const void* const* interm, const float* const* un
     const long nvox = (long)B * D * h * w;
     const unsigned nblk = (unsigned)((nvox + 255) / 256);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == PSCV_BF16) hipLaunchKernelGGL(fuse_pairs_kernel<bf16_t>, dim3(nblk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(fuse_pairs_kernel<f16_t>, dim3(nblk), dim3(256), 0, st, a);
-    PSCV_CHECK_LAUNCH("pscv_fuse_pairs");
-    return 0;
+    return with_half("pscv_fuse_pairs", dtype, [&](auto t) {
+        return launch("pscv_fuse_pairs", fuse_pairs_kernel<typename decltype(t)::type>, dim3(nblk), dim3(256), 0, st, a);
+    });
 }

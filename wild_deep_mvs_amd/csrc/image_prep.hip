@@ -57,12 +57,8 @@ extern "C" int pscv_image_prep(const float* img, int B, int C, int H, int W, int
     PSCV_CHECK_ARG(!(half_img || half_cl8) || (H >= 2 && W >= 2 && W % 2 == 0), "pscv_image_prep: the half-resolution outputs need an even width (8-byte row pairs) and H, W >= 2");
     const long n = out_cl8 ? (long)H * W : (long)(H / 2) * (W / 2);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == PSCV_BF16)
-        hipLaunchKernelGGL(image_prep_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, img, C, H, W, reinterpret_cast<uint4*>(out_cl8),
-                           half_img, reinterpret_cast<uint4*>(half_cl8));
-    else
-        hipLaunchKernelGGL(image_prep_kernel<f16_t>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, img, C, H, W, reinterpret_cast<uint4*>(out_cl8),
-                           half_img, reinterpret_cast<uint4*>(half_cl8));
-    PSCV_CHECK_LAUNCH("pscv_image_prep");
-    return 0;
+    return with_half("pscv_image_prep", dtype, [&](auto t) {
+        return launch("pscv_image_prep", image_prep_kernel<typename decltype(t)::type>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, img, C, H, W,
+                      reinterpret_cast<uint4*>(out_cl8), half_img, reinterpret_cast<uint4*>(half_cl8));
+    });
 }

@@ -79,6 +79,27 @@ PSCV_KNOB_TABLE(PSCV_KNOB_DECLARE)
         }                                                                              \
     } while (0)
 
+// ---- launching ------------------------------------------------------------------------------------------------------
+// A workgroup gets up to 64 KiB of LDS (static + dynamic) without asking; more needs the per-kernel opt-in of ensure_dyn_lds.
+// The rule, once: a launch asks when its DYNAMIC request exceeds this constant.  60000 leaves 5536 B of the 64 KiB for a kernel's
+// static LDS; the kernels that take dynamic LDS declare at most 1504 B of it (scripts/dev/kernel_resources.py, column lds_static;
+// the ones with large static arrays are launched with none), so a launch below the constant never needs the attribute, and the
+// launch-bound forwards pay no device query for it.
+constexpr size_t DYN_LDS_OPT_IN = 60000;
+int dyn_lds_opt_in(const char* what, const void* kernel, size_t lds);   // ensure_dyn_lds + the error text; 0 / -2
+int launch_status(const char* what);                                     // PSCV_CHECK_LAUNCH as a function; 0 / -2
+
+// Opt in where the rule says so (for the kernel that is launched, named once), launch, check.  Returns 0 / -2 with the error set.
+template <typename... KArgs, typename... Args>
+int launch(const char* what, void (*kern)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args&&... args) {
+    if (lds > DYN_LDS_OPT_IN) {
+        const int rc = dyn_lds_opt_in(what, reinterpret_cast<const void*>(kern), lds);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, st, static_cast<KArgs>(args)...);
+    return launch_status(what);
+}
+
 // ---- phase timing (development builds only: -DPSCV_PROFILE) ---------------------------------------------------------
 // Cycle stamps are kept in registers and written once per workgroup (wave 0) at the end: slots 0..5 = cycles of phases 0..5,
 // 6 / 7 = absolute begin / end (low 32 bits), 8 = HW_ID, 9 = XCC_ID.  Each translation unit owns its buffer and exports a getter
@@ -326,5 +347,15 @@ template <typename H> struct Elem16 {
 };
 template <> struct Elem<bf16_t> : Elem16<bf16_t> {};
 template <> struct Elem<f16_t> : Elem16<f16_t> {};
+
+// ---- storage-type dispatch --------------------------------------------------------------------------------------------
+template <typename T> struct TypeTag { using type = T; };
+// f(TypeTag<bf16_t>{}) or f(TypeTag<f16_t>{}) by the dtype code; any other code is the caller's error (-1)
+template <typename F> int with_half(const char* what, int dtype, F&& f) {
+    if (dtype == PSCV_BF16) return f(TypeTag<bf16_t>{});
+    if (dtype == PSCV_F16) return f(TypeTag<f16_t>{});
+    set_error("%s: dtype %d must be bf16 or fp16", what, dtype);
+    return -1;
+}
 
 }  // namespace pscv

@@ -54,6 +54,18 @@ hipError_t ensure_dyn_lds(const void* kernel, int bytes) {
     return hipSuccess;
 }
 
+int dyn_lds_opt_in(const char* what, const void* kernel, size_t lds) {
+    const hipError_t e = ensure_dyn_lds(kernel, (int)lds);
+    if (e == hipSuccess) return 0;
+    set_error("%s: hipFuncSetAttribute(%zu B LDS): %s", what, lds, hipGetErrorString(e));
+    return -2;
+}
+
+int launch_status(const char* what) {
+    PSCV_CHECK_LAUNCH(what);
+    return 0;
+}
+
 // Compute units of the CURRENT device (persistent kernels size their grids with it); cached per device, not per process.
 int device_cu_count() {
     constexpr int MAXDEV = 64;

@@ -360,10 +360,9 @@ extern "C" long pscv_train_workspace_floats(void) { return (long)RED_BLOCKS * 2 
 // a 2-D extractor batch, normalised per view like the reference's per-view calls, models/MVSNet/model.py:101-107).  Constants of
 // group g start `param_stride` floats after those of group g - 1 (pscv_bn_finalize_grouped writes [groups][4][C]:
 // scale, bias, mean, invstd; pscv_bn_bwd_coeffs_grouped [groups][5][C]: ca, cb, cc, d gamma, d beta).  groups = 1 is the plain form.
-static int bn_check(const char* fn, const void* y, int dtype, long nvox, int groups, int C) {
+static int bn_check(const char* fn, const void* y, long nvox, int groups, int C) {
     PSCV_CHECK_ARG(y, "%s: null pointer argument", fn);
     PSCV_CHECK_ARG(C == 8 || C == 16 || C == 32 || C == 64 || C == 128, "%s: C=%d must be 8, 16, 32, 64 or 128", fn, C);
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "%s: dtype %d must be bf16 or fp16", fn, dtype);
     PSCV_CHECK_ARG(nvox > 0 && groups >= 1 && groups <= 256, "%s: empty volume or bad group count %d", fn, groups);
     return 0;
 }
@@ -374,24 +373,24 @@ static int red_grid_grouped(long nchunk, int groups) {
 }
 
 extern "C" int pscv_bn_stats_grouped(const void* y, int dtype, long nvox, int groups, int C, float* workspace, float* sums, void* stream) {
-    if (bn_check("pscv_bn_stats", y, dtype, nvox, groups, C)) return -1;
+    if (bn_check("pscv_bn_stats", y, nvox, groups, C)) return -1;
     PSCV_CHECK_ARG(workspace && sums, "pscv_bn_stats: null pointer argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long nchunk = nvox * (C / 8);
     const int nb = red_grid_grouped(nchunk, groups);
     const uint4* yp = reinterpret_cast<const uint4*>(y);
     const dim3 grid(nb, groups);
-#define PSCV_STATS(HT)                                                                                     \
-    switch (C / 8) {                                                                                       \
-        case 1: hipLaunchKernelGGL((bn_stats_kernel<HT, 1>), grid, dim3(256), 0, st, yp, nchunk, workspace, C); break; \
-        case 2: hipLaunchKernelGGL((bn_stats_kernel<HT, 2>), grid, dim3(256), 0, st, yp, nchunk, workspace, C); break; \
-        case 4: hipLaunchKernelGGL((bn_stats_kernel<HT, 4>), grid, dim3(256), 0, st, yp, nchunk, workspace, C); break; \
-        case 8: hipLaunchKernelGGL((bn_stats_kernel<HT, 8>), grid, dim3(256), 0, st, yp, nchunk, workspace, C); break; \
-        default: hipLaunchKernelGGL((bn_stats_kernel<HT, 16>), grid, dim3(256), 0, st, yp, nchunk, workspace, C); break; \
-    }
-    if (dtype == PSCV_BF16) { PSCV_STATS(bf16_t) } else { PSCV_STATS(f16_t) }
-#undef PSCV_STATS
-    PSCV_CHECK_LAUNCH("pscv_bn_stats");
+    int rc = with_half("pscv_bn_stats", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        switch (C / 8) {
+            case 1: return launch("pscv_bn_stats", bn_stats_kernel<H, 1>, grid, dim3(256), 0, st, yp, nchunk, workspace, C);
+            case 2: return launch("pscv_bn_stats", bn_stats_kernel<H, 2>, grid, dim3(256), 0, st, yp, nchunk, workspace, C);
+            case 4: return launch("pscv_bn_stats", bn_stats_kernel<H, 4>, grid, dim3(256), 0, st, yp, nchunk, workspace, C);
+            case 8: return launch("pscv_bn_stats", bn_stats_kernel<H, 8>, grid, dim3(256), 0, st, yp, nchunk, workspace, C);
+            default: return launch("pscv_bn_stats", bn_stats_kernel<H, 16>, grid, dim3(256), 0, st, yp, nchunk, workspace, C);
+        }
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(finish_partials_kernel, dim3((2 * C + 15) / 16, groups), dim3(256), 0, st, workspace, nb, 2 * C, sums);
     PSCV_CHECK_LAUNCH("pscv_bn_stats(finish)");
     return 0;
@@ -402,17 +401,14 @@ extern "C" int pscv_bn_stats(const void* y, int dtype, long nvox, int C, float* 
 
 extern "C" int pscv_bn_act_grouped(const void* y, int dtype, long nvox, int groups, int C, const float* scale, const float* bias,
                                    int param_stride, int relu, const void* skip, void* out, void* stream) {
-    if (bn_check("pscv_bn_act", y, dtype, nvox, groups, C)) return -1;
+    if (bn_check("pscv_bn_act", y, nvox, groups, C)) return -1;
     PSCV_CHECK_ARG(scale && bias && out, "pscv_bn_act: null pointer argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long nchunk = nvox * (C / 8);
     const dim3 grid(grid_for(nchunk), groups);
-    if (dtype == PSCV_BF16)
-        hipLaunchKernelGGL(bn_act_kernel<bf16_t>, grid, dim3(256), 0, st, (const uint4*)y, scale, bias, (const uint4*)skip, (uint4*)out, nchunk, C / 8, relu, param_stride);
-    else
-        hipLaunchKernelGGL(bn_act_kernel<f16_t>, grid, dim3(256), 0, st, (const uint4*)y, scale, bias, (const uint4*)skip, (uint4*)out, nchunk, C / 8, relu, param_stride);
-    PSCV_CHECK_LAUNCH("pscv_bn_act");
-    return 0;
+    return with_half("pscv_bn_act", dtype, [&](auto t) {
+        return launch("pscv_bn_act", bn_act_kernel<typename decltype(t)::type>, grid, dim3(256), 0, st, (const uint4*)y, scale, bias, (const uint4*)skip, (uint4*)out, nchunk, C / 8, relu, param_stride);
+    });
 }
 extern "C" int pscv_bn_act(const void* y, int dtype, long nvox, int C, const float* scale, const float* bias, int relu,
                            const void* skip, void* out, void* stream) {
@@ -421,24 +417,24 @@ extern "C" int pscv_bn_act(const void* y, int dtype, long nvox, int C, const flo
 
 extern "C" int pscv_bn_bwd_reduce_grouped(const void* dact, const void* y, int dtype, long nvox, int groups, int C, const float* scale,
                                           const float* bias, int param_stride, int relu, float* workspace, float* sums, void* stream) {
-    if (bn_check("pscv_bn_bwd_reduce", y, dtype, nvox, groups, C)) return -1;
+    if (bn_check("pscv_bn_bwd_reduce", y, nvox, groups, C)) return -1;
     PSCV_CHECK_ARG(dact && scale && bias && workspace && sums, "pscv_bn_bwd_reduce: null pointer argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long nchunk = nvox * (C / 8);
     const int nb = red_grid_grouped(nchunk, groups);
     const dim3 grid(nb, groups);
     const uint4 *gp = (const uint4*)dact, *yp = (const uint4*)y;
-#define PSCV_RED(HT)                                                                                                              \
-    switch (C / 8) {                                                                                                              \
-        case 1: hipLaunchKernelGGL((bn_bwd_reduce_kernel<HT, 1>), grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride); break; \
-        case 2: hipLaunchKernelGGL((bn_bwd_reduce_kernel<HT, 2>), grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride); break; \
-        case 4: hipLaunchKernelGGL((bn_bwd_reduce_kernel<HT, 4>), grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride); break; \
-        case 8: hipLaunchKernelGGL((bn_bwd_reduce_kernel<HT, 8>), grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride); break; \
-        default: hipLaunchKernelGGL((bn_bwd_reduce_kernel<HT, 16>), grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride); break; \
-    }
-    if (dtype == PSCV_BF16) { PSCV_RED(bf16_t) } else { PSCV_RED(f16_t) }
-#undef PSCV_RED
-    PSCV_CHECK_LAUNCH("pscv_bn_bwd_reduce");
+    int rc = with_half("pscv_bn_bwd_reduce", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        switch (C / 8) {
+            case 1: return launch("pscv_bn_bwd_reduce", bn_bwd_reduce_kernel<H, 1>, grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride);
+            case 2: return launch("pscv_bn_bwd_reduce", bn_bwd_reduce_kernel<H, 2>, grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride);
+            case 4: return launch("pscv_bn_bwd_reduce", bn_bwd_reduce_kernel<H, 4>, grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride);
+            case 8: return launch("pscv_bn_bwd_reduce", bn_bwd_reduce_kernel<H, 8>, grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride);
+            default: return launch("pscv_bn_bwd_reduce", bn_bwd_reduce_kernel<H, 16>, grid, dim3(256), 0, st, gp, yp, scale, bias, nchunk, workspace, C, relu, param_stride);
+        }
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(finish_partials_kernel, dim3((2 * C + 15) / 16, groups), dim3(256), 0, st, workspace, nb, 2 * C, sums);
     PSCV_CHECK_LAUNCH("pscv_bn_bwd_reduce(finish)");
     return 0;
@@ -451,17 +447,14 @@ extern "C" int pscv_bn_bwd_reduce(const void* dact, const void* y, int dtype, lo
 extern "C" int pscv_bn_bwd_apply_grouped(const void* dact, const void* y, int dtype, long nvox, int groups, int C, const float* scale,
                                          const float* bias, int param_stride, int relu, const float* ca, const float* cb, const float* cc,
                                          int coeff_stride, void* dy, void* stream) {
-    if (bn_check("pscv_bn_bwd_apply", y, dtype, nvox, groups, C)) return -1;
+    if (bn_check("pscv_bn_bwd_apply", y, nvox, groups, C)) return -1;
     PSCV_CHECK_ARG(dact && scale && bias && ca && cb && cc && dy, "pscv_bn_bwd_apply: null pointer argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long nchunk = nvox * (C / 8);
     const dim3 grid(grid_for(nchunk), groups);
-    if (dtype == PSCV_BF16)
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(256), 0, st, (const uint4*)dact, (const uint4*)y, scale, bias, ca, cb, cc, (uint4*)dy, nchunk, C / 8, relu, param_stride, coeff_stride);
-    else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<f16_t>, grid, dim3(256), 0, st, (const uint4*)dact, (const uint4*)y, scale, bias, ca, cb, cc, (uint4*)dy, nchunk, C / 8, relu, param_stride, coeff_stride);
-    PSCV_CHECK_LAUNCH("pscv_bn_bwd_apply");
-    return 0;
+    return with_half("pscv_bn_bwd_apply", dtype, [&](auto t) {
+        return launch("pscv_bn_bwd_apply", bn_bwd_apply_kernel<typename decltype(t)::type>, grid, dim3(256), 0, st, (const uint4*)dact, (const uint4*)y, scale, bias, ca, cb, cc, (uint4*)dy, nchunk, C / 8, relu, param_stride, coeff_stride);
+    });
 }
 extern "C" int pscv_bn_bwd_apply(const void* dact, const void* y, int dtype, long nvox, int C, const float* scale,
                                  const float* bias, int relu, const float* ca, const float* cb, const float* cc, void* dy,
@@ -476,51 +469,46 @@ extern "C" int pscv_softargmin_bwd(const float* logits, const float* depth, long
     PSCV_CHECK_ARG(grad_depth || grad_index || grad_entropy, "pscv_softargmin_bwd: no upstream gradient given");
     PSCV_CHECK_ARG(!grad_depth || depth, "pscv_softargmin_bwd: grad_depth needs the depth planes");
     PSCV_CHECK_ARG(B > 0 && D > 0 && h > 0 && w > 0, "pscv_softargmin_bwd: bad sizes");
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_softargmin_bwd: dtype %d must be bf16 or fp16", dtype);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long npix = (long)B * h * w;
     const int nb = (int)((npix + SB_PX - 1) / SB_PX);
-    if (dtype == PSCV_BF16)
-        hipLaunchKernelGGL(softargmin_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, logits, depth, depth_bstride, depth_per_pixel, grad_depth, grad_index, grad_entropy, (uint4*)dlogits8, B, D, h * w);
-    else
-        hipLaunchKernelGGL(softargmin_bwd_kernel<f16_t>, dim3(nb), dim3(256), 0, st, logits, depth, depth_bstride, depth_per_pixel, grad_depth, grad_index, grad_entropy, (uint4*)dlogits8, B, D, h * w);
-    PSCV_CHECK_LAUNCH("pscv_softargmin_bwd");
-    return 0;
+    return with_half("pscv_softargmin_bwd", dtype, [&](auto t) {
+        return launch("pscv_softargmin_bwd", softargmin_bwd_kernel<typename decltype(t)::type>, dim3(nb), dim3(256), 0, st, logits, depth, depth_bstride, depth_per_pixel, grad_depth, grad_index, grad_entropy, (uint4*)dlogits8, B, D, h * w);
+    });
 }
 
 extern "C" int pscv_leaky_relu_bwd(const void* dout, const void* out, int dtype, long nvox, int C, float slope, void* dpre, void* stream) {
     PSCV_CHECK_ARG(dout && out && dpre, "pscv_leaky_relu_bwd: null pointer argument");
     PSCV_CHECK_ARG(C % 8 == 0 && C > 0 && nvox > 0, "pscv_leaky_relu_bwd: bad sizes");
     PSCV_CHECK_ARG(slope >= 0.0f && slope <= 1.0f, "pscv_leaky_relu_bwd: slope %g outside [0,1]", (double)slope);
-    PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_leaky_relu_bwd: dtype %d must be bf16 or fp16", dtype);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long nchunk = nvox * (C / 8);
     const int nb = grid_for(nchunk);
-    if (dtype == PSCV_BF16) hipLaunchKernelGGL(relu_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const uint4*)dout, (const uint4*)out, (uint4*)dpre, nchunk, slope);
-    else hipLaunchKernelGGL(relu_bwd_kernel<f16_t>, dim3(nb), dim3(256), 0, st, (const uint4*)dout, (const uint4*)out, (uint4*)dpre, nchunk, slope);
-    PSCV_CHECK_LAUNCH("pscv_leaky_relu_bwd");
-    return 0;
+    return with_half("pscv_leaky_relu_bwd", dtype, [&](auto t) {
+        return launch("pscv_leaky_relu_bwd", relu_bwd_kernel<typename decltype(t)::type>, dim3(nb), dim3(256), 0, st, (const uint4*)dout, (const uint4*)out,
+                      (uint4*)dpre, nchunk, slope);
+    });
 }
 extern "C" int pscv_leaky_relu_bwd_sum(const void* dout, const void* out, int dtype, long nvox, int C, float slope, void* dpre,
                                        float* workspace, float* sums, void* stream) {
-    if (bn_check("pscv_leaky_relu_bwd_sum", out, dtype, nvox, 1, C)) return -1;
+    if (bn_check("pscv_leaky_relu_bwd_sum", out, nvox, 1, C)) return -1;
     PSCV_CHECK_ARG(dout && dpre && workspace && sums, "pscv_leaky_relu_bwd_sum: null pointer argument");
     PSCV_CHECK_ARG(slope >= 0.0f && slope <= 1.0f, "pscv_leaky_relu_bwd_sum: slope %g outside [0,1]", (double)slope);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long nchunk = nvox * (C / 8);
     const int nb = red_grid_for(nchunk);
     const uint4 *gp = (const uint4*)dout, *op = (const uint4*)out;
-#define PSCV_RBS(HT)                                                                                                              \
-    switch (C / 8) {                                                                                                              \
-        case 1: hipLaunchKernelGGL((relu_bwd_sum_kernel<HT, 1>), dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C); break; \
-        case 2: hipLaunchKernelGGL((relu_bwd_sum_kernel<HT, 2>), dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C); break; \
-        case 4: hipLaunchKernelGGL((relu_bwd_sum_kernel<HT, 4>), dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C); break; \
-        case 8: hipLaunchKernelGGL((relu_bwd_sum_kernel<HT, 8>), dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C); break; \
-        default: hipLaunchKernelGGL((relu_bwd_sum_kernel<HT, 16>), dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C); break; \
-    }
-    if (dtype == PSCV_BF16) { PSCV_RBS(bf16_t) } else { PSCV_RBS(f16_t) }
-#undef PSCV_RBS
-    PSCV_CHECK_LAUNCH("pscv_leaky_relu_bwd_sum");
+    int rc = with_half("pscv_leaky_relu_bwd_sum", dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        switch (C / 8) {
+            case 1: return launch("pscv_leaky_relu_bwd_sum", relu_bwd_sum_kernel<H, 1>, dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C);
+            case 2: return launch("pscv_leaky_relu_bwd_sum", relu_bwd_sum_kernel<H, 2>, dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C);
+            case 4: return launch("pscv_leaky_relu_bwd_sum", relu_bwd_sum_kernel<H, 4>, dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C);
+            case 8: return launch("pscv_leaky_relu_bwd_sum", relu_bwd_sum_kernel<H, 8>, dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C);
+            default: return launch("pscv_leaky_relu_bwd_sum", relu_bwd_sum_kernel<H, 16>, dim3(nb), dim3(256), 0, st, gp, op, (uint4*)dpre, nchunk, slope, workspace, C);
+        }
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(finish_partials_kernel, dim3((2 * C + 15) / 16, 1), dim3(256), 0, st, workspace, nb, 2 * C, sums);
     PSCV_CHECK_LAUNCH("pscv_leaky_relu_bwd_sum(finish)");
     return 0;

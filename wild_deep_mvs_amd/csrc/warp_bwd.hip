@@ -670,16 +670,8 @@ static int bwd_tile_launch(WarpBwdArgs& A, int geom, int cost, hipStream_t st) {
     const long nblk = (long)a.npb_batch * a.B * a.n_dchunks;
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost_bwd: bad grid size %ld", nblk); return -1; }
     constexpr int LDS = bt_texels<C>() * (C + 1) * 4;
-#define PSCV_BWDT(GEOMV, COSTV)                                                                                           \
-    if (geom == GEOMV && cost == COSTV) {                                                                                 \
-        auto kern = warp_bwd_tile_kernel<TIn, TG, C, GEOMV, COSTV>;                                                       \
-        {                                                                                                 \
-            hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LDS); \
-            if (e != hipSuccess) { set_error("pscv_warp_cost_bwd: hipFuncSetAttribute(%d B LDS): %s", LDS, hipGetErrorString(e)); return -2; } \
-        }                                                                                                                 \
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(256), LDS, st, A);                                            \
-        return 0;                                                                                                         \
-    }
+#define PSCV_BWDT(GEOMV, COSTV) \
+    if (geom == GEOMV && cost == COSTV) return launch("pscv_warp_cost_bwd", warp_bwd_tile_kernel<TIn, TG, C, GEOMV, COSTV>, dim3((unsigned)nblk), dim3(256), LDS, st, A);
     PSCV_BWDT(PSCV_GEOM_PROJ, PSCV_COST_VARIANCE)
     PSCV_BWDT(PSCV_GEOM_PROJ, PSCV_COST_VARIANCE_CVP)
     PSCV_BWDT(PSCV_GEOM_PROJ, PSCV_COST_SOFTMIN)
@@ -705,11 +697,8 @@ static int bwd_launch(WarpBwdArgs& A, int geom, int cost, hipStream_t st) {
     a.n_dchunks = (a.D + ppd - 1) / ppd;
     const long nblk = n_pixblocks * a.n_dchunks;
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost_bwd: bad grid size %ld", nblk); return -1; }
-#define PSCV_BWD(GEOMV, COSTV)                                                                                          \
-    if (geom == GEOMV && cost == COSTV) {                                                                               \
-        hipLaunchKernelGGL((warp_bwd_kernel<TIn, TG, C, LPV, GEOMV, COSTV>), dim3((unsigned)nblk), dim3(256), 0, st, A);  \
-        return 0;                                                                                                       \
-    }
+#define PSCV_BWD(GEOMV, COSTV) \
+    if (geom == GEOMV && cost == COSTV) return launch("pscv_warp_cost_bwd", warp_bwd_kernel<TIn, TG, C, LPV, GEOMV, COSTV>, dim3((unsigned)nblk), dim3(256), 0, st, A);
     PSCV_BWD(PSCV_GEOM_PROJ, PSCV_COST_VARIANCE)
     PSCV_BWD(PSCV_GEOM_PROJ, PSCV_COST_VARIANCE_CVP)
     PSCV_BWD(PSCV_GEOM_PROJ, PSCV_COST_SOFTMIN)
@@ -772,14 +761,7 @@ extern "C" int pscv_warp_cost_bwd(const void* ref, const void* const* srcs, int 
         a.ylo = -0.05f * (hs - 1); a.yhi = 1.05f * (hs - 1);
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc;
-    if (in_dtype == PSCV_BF16 && grad_dtype == PSCV_BF16) rc = bwd_channels<bf16_t, bf16_t>(A, C, geom, cost, st);
-    else if (in_dtype == PSCV_F16 && grad_dtype == PSCV_F16) rc = bwd_channels<f16_t, f16_t>(A, C, geom, cost, st);
-    else if (in_dtype == PSCV_F32 && grad_dtype == PSCV_F32) rc = bwd_channels<float, float>(A, C, geom, cost, st);
-    else if (in_dtype == PSCV_BF16 && grad_dtype == PSCV_F32) rc = bwd_channels<bf16_t, float>(A, C, geom, cost, st);
-    else if (in_dtype == PSCV_F16 && grad_dtype == PSCV_F32) rc = bwd_channels<f16_t, float>(A, C, geom, cost, st);
-    else { set_error("pscv_warp_cost_bwd: unsupported dtype pair in=%d grad=%d", in_dtype, grad_dtype); return -1; }
-    if (rc) return rc;
-    PSCV_CHECK_LAUNCH("pscv_warp_cost_bwd");
-    return 0;
+    return with_warp_types<true>("pscv_warp_cost_bwd", in_dtype, grad_dtype, [&](auto ti, auto tg) {
+        return bwd_channels<typename decltype(ti)::type, typename decltype(tg)::type>(A, C, geom, cost, st);
+    }, "grad");
 }

@@ -200,4 +200,17 @@ __device__ __forceinline__ VecF<CPL> blend_taps(const char* __restrict__ base, c
 }
 
 
+// Forward warp kernels: f(TypeTag<TIn>{}, TypeTag<TOut>{}) for features in bf16 / fp16 and an output in the same format or fp32;
+// with F32_IN also fp32 features with an fp32 output (the generic kernels only; a compile-time flag: the 16-bit-only callers must not
+// instantiate <float, float>).  Any other pair is the caller's error (-1).
+// `second` names the second dtype in the error text ("out"; "grad" for the backward, whose second tensor is the output gradient).
+template <bool F32_IN, typename F> int with_warp_types(const char* what, int in_dtype, int out_dtype, F&& f, const char* second = "out") {
+    if constexpr (F32_IN)
+        if (in_dtype == PSCV_F32 && out_dtype == PSCV_F32) return f(TypeTag<float>{}, TypeTag<float>{});
+    if (out_dtype == in_dtype) return with_half(what, in_dtype, [&](auto t) { return f(t, t); });
+    if (out_dtype == PSCV_F32 && (in_dtype == PSCV_BF16 || in_dtype == PSCV_F16)) return with_half(what, in_dtype, [&](auto t) { return f(t, TypeTag<float>{}); });
+    set_error("%s: unsupported dtype pair in=%d %s=%d (%s must be the input's 16-bit format or fp32)", what, in_dtype, second, out_dtype, second);
+    return -1;
+}
+
 }  // namespace pscv

@@ -244,23 +244,13 @@ int warp_gc_lv_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out
 
 // Instantiated (geometry, cost) pairs: the variance / softmin statistics belong to the PROJ models (MVSNet,
 // CVP), group-wise correlation to the HOMOG model (Vis); the plain warp exists for both.
-// dynamic LDS = the per-(view, pixel) ray terms; above the 64 KiB default (many views) the kernel needs the opt-in
-template <typename K>
-static int launch_one(K kern, const WarpArgs& a, int nblk, size_t ray_bytes, hipStream_t st) {
-    if (ray_bytes > 60000) {   // rare (> 14 HOMOG views): not worth caching per kernel
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), (int)ray_bytes);
-        if (e != hipSuccess) { set_error("pscv_warp_cost: hipFuncSetAttribute(%zu B LDS): %s", ray_bytes, hipGetErrorString(e)); return -2; }
-    }
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), ray_bytes, st, a);
-    return 0;
-}
-
+// dynamic LDS = the per-(view, pixel) ray terms; above the 64 KiB default (> 14 HOMOG views) launch() opts in
 template <typename TIn, typename TOut, int C, int LPV, int GEOM>
 static int launch_cost(const WarpArgs& a, int cost, int nblk, hipStream_t st) {
     const size_t ray_bytes = (size_t)a.n_src * (256 / LPV) * (GEOM == PSCV_GEOM_HOMOG ? 32 : 16);
 #define PSCV_LAUNCH_COST(COSTV)                                                                              \
     case COSTV:                                                                                              \
-        return launch_one(warp_cost_kernel<TIn, TOut, C, LPV, GEOM, COSTV>, a, nblk, ray_bytes, st);
+        return launch("pscv_warp_cost", warp_cost_kernel<TIn, TOut, C, LPV, GEOM, COSTV>, dim3(nblk), dim3(256), ray_bytes, st, a);
     if constexpr (GEOM == PSCV_GEOM_PROJ) {
         switch (cost) {
             PSCV_LAUNCH_COST(PSCV_COST_VARIANCE)
@@ -269,7 +259,7 @@ static int launch_cost(const WarpArgs& a, int cost, int nblk, hipStream_t st) {
             PSCV_LAUNCH_COST(PSCV_COST_WARP_ONLY)
             case PSCV_COST_VARIANCE_PARTIAL:
                 if constexpr (sizeof(TOut) == 4)
-                    return launch_one(warp_cost_kernel<TIn, TOut, C, LPV, GEOM, PSCV_COST_VARIANCE_PARTIAL>, a, nblk, ray_bytes, st);
+                    return launch("pscv_warp_cost", warp_cost_kernel<TIn, TOut, C, LPV, GEOM, PSCV_COST_VARIANCE_PARTIAL>, dim3(nblk), dim3(256), ray_bytes, st, a);
                 break;
         }
     } else {
@@ -380,27 +370,13 @@ extern "C" int pscv_warp_cost_rows(const void* ref, const void* const* srcs, int
         if (rc == 1 && g_warp_gc_lds && (g_warp_gc_lds >= 2 || !depth_per_pixel)) rc = warp_gc_lv_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
         if (rc == 1)
             rc = warp_cost_tiled_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
-        if (rc < 0) return rc;
-        if (rc == 0) {
-            PSCV_CHECK_LAUNCH("pscv_warp_cost(tiled)");
-            return 0;
-        }
+        if (rc <= 0) return rc;
     }
     if (g_warp_q2 && g_warp_lpv_override == 0) {
         rc = warp_cost_q2_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
-        if (rc < 0) return rc;
-        if (rc == 0) {
-            PSCV_CHECK_LAUNCH("pscv_warp_cost(q2)");
-            return 0;
-        }
+        if (rc <= 0) return rc;
     }
-    if (in_dtype == PSCV_BF16 && out_dtype == PSCV_BF16) rc = launch_channels<bf16_t, bf16_t>(a, C, geom, cost, st);
-    else if (in_dtype == PSCV_F16 && out_dtype == PSCV_F16) rc = launch_channels<f16_t, f16_t>(a, C, geom, cost, st);
-    else if (in_dtype == PSCV_BF16 && out_dtype == PSCV_F32) rc = launch_channels<bf16_t, float>(a, C, geom, cost, st);
-    else if (in_dtype == PSCV_F16 && out_dtype == PSCV_F32) rc = launch_channels<f16_t, float>(a, C, geom, cost, st);
-    else if (in_dtype == PSCV_F32 && out_dtype == PSCV_F32) rc = launch_channels<float, float>(a, C, geom, cost, st);
-    else { set_error("pscv_warp_cost: unsupported dtype pair in=%d out=%d (out must be the input's 16-bit format or fp32)", in_dtype, out_dtype); return -1; }
-    if (rc) return rc;
-    PSCV_CHECK_LAUNCH("pscv_warp_cost");
-    return 0;
+    return with_warp_types<true>("pscv_warp_cost", in_dtype, out_dtype, [&](auto ti, auto to) {
+        return launch_channels<typename decltype(ti)::type, typename decltype(to)::type>(a, C, geom, cost, st);
+    });
 }

@@ -64,16 +64,9 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     static_assert(COST == PSCV_COST_VARIANCE || COST == PSCV_COST_VARIANCE_CVP, "variance costs");
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
 
-    // ---- work decode (as warp_cost_tiled.hip): XCD k gets a contiguous run of tiles ----
     const int dc = blockIdx.y;
-    const int tpx = gridDim.x >> 3;
-    const int ntx = (a.w + LV_T - 1) / LV_T, nty = (a.h + LV_TH - 1) / LV_TH;
-    const int tile = ((int)blockIdx.x & 7) * tpx + ((int)blockIdx.x >> 3);
-    if (tile >= a.B * nty * ntx) return;
-    const int trow = (int)(((float)tile + 0.5f) * (1.0f / (float)ntx));     // exact: tile < 2^22
-    const int txi = tile - trow * ntx;
-    const int b = (int)(((float)trow + 0.5f) * (1.0f / (float)nty));
-    const int tyi = trow - b * nty;
+    int b, tyi, txi;
+    if (!wl_tile_decode<LV_T, LV_TH>(a, b, tyi, txi)) return;
 
     __builtin_amdgcn_s_setprio(3);                                   // box / staging phase ahead of the other blocks' sweeps
     __builtin_amdgcn_s_setreg((1 - 1) << 11 | 23 << 6 | 1, 1);       // MODE.FP16_OVFL: saturating f32 -> f16 stores
@@ -507,21 +500,14 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
 }
 
 template <typename TIn, typename TOut, int COST>
-static int lv_launch(const WarpArgs& a, hipStream_t st) {
-    auto kern = warp_cost_lv_kernel<TIn, TOut, COST>;
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LV_LDS);
-        if (e != hipSuccess) { set_error("pscv_warp_cost(lv): hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
-    }
-    const int tiles = a.B * ((a.h + LV_TH - 1) / LV_TH) * ((a.w + LV_T - 1) / LV_T);
-    hipLaunchKernelGGL(kern, dim3(8 * ((tiles + 7) / 8), a.n_dchunks), dim3(LV_THREADS), LV_LDS, st, a);
-    return 0;
+static int lv_launch(const WarpArgs& a, dim3 grid, hipStream_t st) {
+    return launch("pscv_warp_cost(lv)", warp_cost_lv_kernel<TIn, TOut, COST>, grid, dim3(LV_THREADS), LV_LDS, st, a);
 }
 
 template <typename TIn, typename TOut>
-static int lv_dispatch(const WarpArgs& a, int cost, hipStream_t st) {
-    if (cost == PSCV_COST_VARIANCE) return lv_launch<TIn, TOut, PSCV_COST_VARIANCE>(a, st);
-    if (cost == PSCV_COST_VARIANCE_CVP) return lv_launch<TIn, TOut, PSCV_COST_VARIANCE_CVP>(a, st);
+static int lv_dispatch(const WarpArgs& a, int cost, dim3 grid, hipStream_t st) {
+    if (cost == PSCV_COST_VARIANCE) return lv_launch<TIn, TOut, PSCV_COST_VARIANCE>(a, grid, st);
+    if (cost == PSCV_COST_VARIANCE_CVP) return lv_launch<TIn, TOut, PSCV_COST_VARIANCE_CVP>(a, grid, st);
     return 1;
 }
 
@@ -529,23 +515,18 @@ extern int* g_wl_mode_hist;   // warp_cost_tiled.hip (pscv_debug_wl_mode_hist)
 
 // Returns 0 if launched, 1 if this configuration is not covered (the caller tries the quad-owner kernel next), negative on error.
 int warp_cost_lv_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (C != 32 || a.depth_per_pixel || geom != PSCV_GEOM_PROJ || (in_dtype != PSCV_F16 && in_dtype != PSCV_BF16)) return 1;
+    if (a.depth_per_pixel || geom != PSCV_GEOM_PROJ) return 1;
     if (cost != PSCV_COST_VARIANCE && cost != PSCV_COST_VARIANCE_CVP) return 1;
     if (out_dtype != in_dtype && out_dtype != PSCV_F32) return 1;
     if (a.n_src < 1 || a.n_src > WL_MAX_SRC) return 1;
-    if (a.ws > 16384 || a.hs > 16384) return 1;
-    const long tiles = (long)a.B * ((a.h + LV_TH - 1) / LV_TH) * ((a.w + LV_T - 1) / LV_T);
-    if (tiles >= (1L << 22)) return 1;   // tile index decode is exact below 2^22
-    int ppd = ppd_override > 0 ? min((ppd_override + 1) & ~1, 64) : 32;   // planes per block: amortises the box staging
-    while (ppd > 4 && tiles * ((a.D + ppd - 1) / ppd) < 1024) ppd >>= 1;
-    a.ppd = ppd;
-    a.n_dchunks = (a.D + ppd - 1) / ppd;
+    dim3 grid;
+    const int rc = wl_plan("pscv_warp_cost(lv)", a, C, in_dtype, LV_T, LV_TH, ppd_override, 32, 64, grid);
+    if (rc) return rc;
     a.mode_hist = g_wl_mode_hist;
     a.variant = g_warp_tile;
-    const long nblk = tiles * a.n_dchunks;
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost(lv): bad grid %ld", nblk); return -1; }
-    if (in_dtype == PSCV_F16) return out_dtype == PSCV_F32 ? lv_dispatch<f16_t, float>(a, cost, st) : lv_dispatch<f16_t, f16_t>(a, cost, st);
-    return out_dtype == PSCV_F32 ? lv_dispatch<bf16_t, float>(a, cost, st) : lv_dispatch<bf16_t, bf16_t>(a, cost, st);
+    return with_warp_types<false>("pscv_warp_cost(lv)", in_dtype, out_dtype, [&](auto ti, auto to) {
+        return lv_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, cost, grid, st);
+    });
 }
 
 }  // namespace pscv

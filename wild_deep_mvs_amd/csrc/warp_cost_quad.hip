@@ -332,10 +332,8 @@ __global__ __launch_bounds__(256, 4) void warp_cost_q2_kernel(const WarpArgs a) 
 
 template <typename TIn, typename TOut, int GEOM, int COST>
 static int q2_launch(const WarpArgs& a, int nblk, hipStream_t st) {
-    auto kern = warp_cost_q2_kernel<TIn, TOut, GEOM, COST>;
-    const size_t ray_bytes = (size_t)a.n_src * 64 * (GEOM == PSCV_GEOM_HOMOG ? 32 : 16);
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), ray_bytes, st, a);   // <= 32 KiB: inside the default limit
-    return 0;
+    const size_t ray_bytes = (size_t)a.n_src * 64 * (GEOM == PSCV_GEOM_HOMOG ? 32 : 16);   // <= 32 KiB: inside the default limit
+    return launch("pscv_warp_cost(q2)", warp_cost_q2_kernel<TIn, TOut, GEOM, COST>, dim3(nblk), dim3(256), ray_bytes, st, a);
 }
 
 template <typename TIn, typename TOut>
@@ -368,10 +366,9 @@ int warp_cost_q2_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int o
     a.n_dchunks = (a.D + ppd - 1) / ppd;
     const long nblk = n_pixblocks * a.n_dchunks;
     if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost(q2): bad grid %ld", nblk); return -1; }
-    if (in_dtype == PSCV_F16) return out_dtype == PSCV_F32 ? q2_dispatch<f16_t, float>(a, geom, cost, (int)nblk, st)
-                                                           : q2_dispatch<f16_t, f16_t>(a, geom, cost, (int)nblk, st);
-    return out_dtype == PSCV_F32 ? q2_dispatch<bf16_t, float>(a, geom, cost, (int)nblk, st)
-                                 : q2_dispatch<bf16_t, bf16_t>(a, geom, cost, (int)nblk, st);
+    return with_warp_types<false>("pscv_warp_cost(q2)", in_dtype, out_dtype, [&](auto ti, auto to) {
+        return q2_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, geom, cost, (int)nblk, st);
+    });
 }
 
 }  // namespace pscv

@@ -106,18 +106,9 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
     static_assert(GEOM == PSCV_GEOM_PROJ, "PROJ geometry (three depth-independent ray terms per (view, pixel))");
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
 
-    // ---- work decode: grid = (8 x tiles-per-XCD, depth chunks).  Hardware places consecutive workgroups on consecutive XCDs,
-    //      so blockIdx.x & 7 is the XCD: give XCD k a contiguous run of tiles (its source footprint stays inside that XCD's
-    //      4 MiB L2; the depth chunks of a tile re-read nearly the same texels).  Float reciprocals replace integer division. ----
     const int dc = blockIdx.y;
-    const int tpx = gridDim.x >> 3;
-    const int ntx = (a.w + WL_T - 1) / WL_T, nty = (a.h + WL_TH - 1) / WL_TH;
-    const int tile = ((int)blockIdx.x & 7) * tpx + ((int)blockIdx.x >> 3);
-    if (tile >= a.B * nty * ntx) return;
-    const int trow = (int)(((float)tile + 0.5f) * (1.0f / (float)ntx));     // exact: tile < 2^22
-    const int txi = tile - trow * ntx;
-    const int b = (int)(((float)trow + 0.5f) * (1.0f / (float)nty));
-    const int tyi = trow - b * nty;
+    int b, tyi, txi;
+    if (!wl_tile_decode<WL_T, WL_TH>(a, b, tyi, txi)) return;
 
     // the box / staging phase of a new workgroup runs at raised priority: the (older) waves of the CU's other workgroup are in
     // their vector-ALU-bound sweep and would otherwise win every issue slot (arbitration is priority, then age), stretching
@@ -524,25 +515,18 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
 }
 
 template <typename TIn, typename TOut, int COST>
-static int wl_launch(const WarpArgs& a, int nblk, hipStream_t st) {
-    auto kern = warp_cost_lds_kernel<TIn, TOut, PSCV_GEOM_PROJ, COST>;
+static int wl_launch(const WarpArgs& a, dim3 grid, hipStream_t st) {
     // "warp_lds_pad" (KiB, measurement knob): ask for more LDS than the kernel needs = fewer workgroups per CU with the same code --
     // the occupancy experiment of scripts/dev/wl_residency.py and the stream-mode co-residency runs (room for another stream's conv0)
     const int lds = min(WL_LDS + 1024 * max(0, (int)g_warp_lds_pad), 160 * 1024);
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), 160 * 1024);
-        if (e != hipSuccess) { set_error("pscv_warp_cost(lds): hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
-    }
-    const int tiles = a.B * ((a.h + WL_TH - 1) / WL_TH) * ((a.w + WL_T - 1) / WL_T);
-    hipLaunchKernelGGL(kern, dim3(8 * ((tiles + 7) / 8), a.n_dchunks), dim3(WL_THREADS), lds, st, a);
-    return 0;
+    return launch("pscv_warp_cost(lds)", warp_cost_lds_kernel<TIn, TOut, PSCV_GEOM_PROJ, COST>, grid, dim3(WL_THREADS), lds, st, a);
 }
 
 template <typename TIn, typename TOut>
-static int wl_dispatch(const WarpArgs& a, int cost, int nblk, hipStream_t st) {
-    if (cost == PSCV_COST_VARIANCE) return wl_launch<TIn, TOut, PSCV_COST_VARIANCE>(a, nblk, st);
-    if (cost == PSCV_COST_VARIANCE_CVP) return wl_launch<TIn, TOut, PSCV_COST_VARIANCE_CVP>(a, nblk, st);
-    if (cost == PSCV_COST_SOFTMIN) return wl_launch<TIn, TOut, PSCV_COST_SOFTMIN>(a, nblk, st);
+static int wl_dispatch(const WarpArgs& a, int cost, dim3 grid, hipStream_t st) {
+    if (cost == PSCV_COST_VARIANCE) return wl_launch<TIn, TOut, PSCV_COST_VARIANCE>(a, grid, st);
+    if (cost == PSCV_COST_VARIANCE_CVP) return wl_launch<TIn, TOut, PSCV_COST_VARIANCE_CVP>(a, grid, st);
+    if (cost == PSCV_COST_SOFTMIN) return wl_launch<TIn, TOut, PSCV_COST_SOFTMIN>(a, grid, st);
     return 1;
 }
 
@@ -551,28 +535,21 @@ static int wl_dispatch(const WarpArgs& a, int cost, int nblk, hipStream_t st) {
 int* g_wl_mode_hist = nullptr;   // set by pscv_debug_wl_mode_hist (development aid, not thread-safe; shared with warp_cost_lv.hip)
 
 int warp_cost_tiled_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (C != 32 || a.depth_per_pixel || geom != PSCV_GEOM_PROJ || (in_dtype != PSCV_F16 && in_dtype != PSCV_BF16)) return 1;
+    if (a.depth_per_pixel || geom != PSCV_GEOM_PROJ) return 1;
     if (out_dtype != in_dtype && out_dtype != PSCV_F32) return 1;
     if (a.n_src < 1 || a.n_src > WL_MAX_SRC) return 1;
-    if (a.ws > 16384 || a.hs > 16384) return 1;
-    if ((long)((a.h + WL_TH - 1) / WL_TH) * ((a.w + WL_T - 1) / WL_T) * a.B >= (1L << 22)) return 1;   // tile index decode is exact below 2^22
-    const long tiles = (long)a.B * ((a.h + WL_TH - 1) / WL_TH) * ((a.w + WL_T - 1) / WL_T);
     // planes per block: amortises the box + staging phases (13 % of a 32-plane workgroup's lifetime).  Round 6: 48 planes where the
     // depth axis has room for two such chunks -- the adaptive split (halves, quarters) takes care of the blocks whose 48-plane boxes do
     // not fit: 3-view step 0.900 -> 0.884 / 0.912 -> 0.899 ms on the probe rig, 0.987 -> 0.977 / 0.970 -> 0.970 on the DTU-like rig
     // (free-running per-view graphs, alternating; 64 planes: no better, 24: worse)
-    int ppd = ppd_override > 0 ? min((ppd_override + 1) & ~1, 64) : (a.D >= 96 ? 48 : 32);
-    while (ppd > 4 && tiles * ((a.D + ppd - 1) / ppd) < 1024) ppd >>= 1;
-    a.ppd = ppd;
-    a.n_dchunks = (a.D + ppd - 1) / ppd;
+    dim3 grid;
+    const int rc = wl_plan("pscv_warp_cost(lds)", a, C, in_dtype, WL_T, WL_TH, ppd_override, a.D >= 96 ? 48 : 32, 64, grid);
+    if (rc) return rc;
     a.variant = g_warp_tile;
     a.mode_hist = g_wl_mode_hist;
-    const long nblk = tiles * a.n_dchunks;
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost(lds): bad grid %ld", nblk); return -1; }
-    if (in_dtype == PSCV_F16) return out_dtype == PSCV_F32 ? wl_dispatch<f16_t, float>(a, cost, (int)nblk, st)
-                                                           : wl_dispatch<f16_t, f16_t>(a, cost, (int)nblk, st);
-    return out_dtype == PSCV_F32 ? wl_dispatch<bf16_t, float>(a, cost, (int)nblk, st)
-                                 : wl_dispatch<bf16_t, bf16_t>(a, cost, (int)nblk, st);
+    return with_warp_types<false>("pscv_warp_cost(lds)", in_dtype, out_dtype, [&](auto ti, auto to) {
+        return wl_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, cost, grid, st);
+    });
 }
 
 }  // namespace pscv

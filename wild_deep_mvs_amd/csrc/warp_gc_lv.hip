@@ -36,14 +36,8 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
 
     const int dc = blockIdx.y;
-    const int tpx = gridDim.x >> 3;
-    const int ntx = (a.w + LV_T - 1) / LV_T, nty = (a.h + LV_TH - 1) / LV_TH;
-    const int tile = ((int)blockIdx.x & 7) * tpx + ((int)blockIdx.x >> 3);
-    if (tile >= a.B * nty * ntx) return;
-    const int trow = (int)(((float)tile + 0.5f) * (1.0f / (float)ntx));     // exact: tile < 2^22
-    const int txi = tile - trow * ntx;
-    const int b = (int)(((float)trow + 0.5f) * (1.0f / (float)nty));
-    const int tyi = trow - b * nty;
+    int b, tyi, txi;
+    if (!wl_tile_decode<LV_T, LV_TH>(a, b, tyi, txi)) return;
 
     __builtin_amdgcn_s_setprio(3);
     __builtin_amdgcn_s_setreg((1 - 1) << 11 | 23 << 6 | 1, 1);       // MODE.FP16_OVFL: saturating f32 -> f16 stores
@@ -287,45 +281,29 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     }
 }
 
-template <typename TIn, typename TOut>
-static int gc_launch(const WarpArgs& a, hipStream_t st) {
-    auto kern = warp_gc_lv_kernel<TIn, TOut>;
-    {
-        hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(kern), LV_LDS);
-        if (e != hipSuccess) { set_error("pscv_warp_cost(gc): hipFuncSetAttribute: %s", hipGetErrorString(e)); return -2; }
-    }
-    const int tiles = a.B * ((a.h + LV_TH - 1) / LV_TH) * ((a.w + LV_T - 1) / LV_T);
-    hipLaunchKernelGGL(kern, dim3(8 * ((tiles + 7) / 8), a.n_dchunks), dim3(LV_THREADS), LV_LDS, st, a);
-    return 0;
-}
-
 extern int* g_wl_mode_hist;   // warp_cost_tiled.hip (pscv_debug_wl_mode_hist)
 
 // Returns 0 if launched (one launch per group of four source views), 1 if this configuration is not covered (the caller uses the quad
 // kernel), negative on error.
 int warp_gc_lv_try(WarpArgs& a0, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (C != 32 || geom != PSCV_GEOM_HOMOG || cost != PSCV_COST_GROUPCORR) return 1;
-    if ((in_dtype != PSCV_F16 && in_dtype != PSCV_BF16) || out_dtype != in_dtype) return 1;
+    if (geom != PSCV_GEOM_HOMOG || cost != PSCV_COST_GROUPCORR || out_dtype != in_dtype) return 1;
     if (a0.n_src < 1 || a0.n_src > PSCV_MAX_SRC) return 1;
-    if (a0.ws > 16384 || a0.hs > 16384 || a0.ws < 21 || a0.hs < 21) return 1;     // (below 21 texels the grid clamp reaches inside the image's tap range)
-    const long tiles = (long)a0.B * ((a0.h + LV_TH - 1) / LV_TH) * ((a0.w + LV_T - 1) / LV_T);
-    if (tiles >= (1L << 22)) return 1;
-    const int ppd_max = a0.depth_per_pixel ? 32 : 64;
-    int ppd = ppd_override > 0 ? min((ppd_override + 1) & ~1, ppd_max) : 32;
-    while (ppd > 4 && tiles * ((a0.D + ppd - 1) / ppd) < 1024) ppd >>= 1;
-    const long nblk = tiles * ((a0.D + ppd - 1) / ppd);
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost(gc): bad grid %ld", nblk); return -1; }
+    if (a0.ws < 21 || a0.hs < 21) return 1;     // (below 21 texels the grid clamp reaches inside the image's tap range)
+    dim3 grid;
+    const int plan = wl_plan("pscv_warp_cost(gc)", a0, C, in_dtype, LV_T, LV_TH, ppd_override, 32, a0.depth_per_pixel ? 32 : 64, grid);
+    if (plan) return plan;
     for (int v0 = 0; v0 < a0.n_src; v0 += WL_MAX_SRC) {
         WarpArgs a = a0;
         a.n_src = min(WL_MAX_SRC, a0.n_src - v0);
         for (int i = 0; i < PSCV_MAX_SRC; ++i) a.src[i] = (i < a.n_src) ? a0.src[v0 + i] : nullptr;
         a.cams = a0.cams + (long)v0 * a0.B * PSCV_CAM_FLOATS;
         a.out = reinterpret_cast<char*>(a0.out) + (unsigned long)v0 * a0.out_view_stride * 2;
-        a.ppd = ppd;
-        a.n_dchunks = (a0.D + ppd - 1) / ppd;
         a.mode_hist = g_wl_mode_hist ? g_wl_mode_hist + 0 : nullptr;
         a.variant = g_warp_tile;
-        const int rc = in_dtype == PSCV_F16 ? gc_launch<f16_t, f16_t>(a, st) : gc_launch<bf16_t, bf16_t>(a, st);
+        const int rc = with_half("pscv_warp_cost(gc)", in_dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            return launch("pscv_warp_cost(gc)", warp_gc_lv_kernel<T, T>, grid, dim3(LV_THREADS), LV_LDS, st, a);
+        });
         if (rc) return rc;
     }
     return 0;

@@ -1,5 +1,6 @@
-// Pieces shared by the two LDS-staged plane-sweep kernels (warp_cost_tiled.hip: a quad of lanes owns a voxel; warp_cost_lv.hip: a lane
-// owns a voxel): DPP broadcasts / reductions, the saturating 16-bit pack, the per-(block, view) staging modes.
+// Pieces shared by the LDS-staged plane-sweep kernels (warp_cost_tiled.hip: a quad of lanes owns a voxel; warp_cost_lv.hip, warp_gc_lv.hip:
+// a lane owns a voxel): DPP broadcasts / reductions, the saturating 16-bit pack, the per-(block, view) staging modes, the tile decode
+// and the launch plan.
 #pragma once
 #include "warp_common.h"
 
@@ -55,5 +56,41 @@ constexpr int WL_DIRECT = 0;   // not staged (a corner at / behind the source ca
 constexpr int WL_GEN = 1;      // box clipped at the image border: LDS taps, general (zero-padding) weights
 constexpr int WL_FAST = 2;     // box strictly inside the image: LDS taps, no masks / clamps
 constexpr int WL_ZERO = 3;     // box entirely outside the image: every tap is zero padding, the view contributes f = 0
+
+
+// ---- work decode of the LDS-staged kernels: grid = (8 x tiles-per-XCD, depth chunks), tiles of T x TH reference pixels.  Hardware
+//      places consecutive workgroups on consecutive XCDs, so blockIdx.x & 7 is the XCD: XCD k gets a contiguous run of tiles (its source
+//      footprint stays inside that XCD's 4 MiB L2; the depth chunks of a tile re-read nearly the same texels).  Float reciprocals
+//      replace integer division.  False for the workgroups that pad the grid to a multiple of 8. ----
+template <int T, int TH> __device__ __forceinline__ bool wl_tile_decode(const WarpArgs& a, int& b, int& tyi, int& txi) {
+    const int tpx = gridDim.x >> 3;
+    const int ntx = (a.w + T - 1) / T, nty = (a.h + TH - 1) / TH;
+    const int tile = ((int)blockIdx.x & 7) * tpx + ((int)blockIdx.x >> 3);
+    if (tile >= a.B * nty * ntx) return false;
+    const int trow = (int)(((float)tile + 0.5f) * (1.0f / (float)ntx));     // exact: tile < 2^22
+    txi = tile - trow * ntx;
+    b = (int)(((float)trow + 0.5f) * (1.0f / (float)nty));
+    tyi = trow - b * nty;
+    return true;
+}
+
+// Host side of the same: what the three kernels cover in common (C = 32, 16-bit features, source maps of <= 16384 texels a side,
+// fewer than 2^22 tiles: the decode above is exact below that), the planes per workgroup (`ppd_default`, or the "warp_ppd" override
+// rounded to even and capped at `ppd_max`; halved while fewer than 1024 workgroups would result: the box + staging phases amortise
+// over the planes, but the chip wants filling first) and the grid.  Fills a.ppd / a.n_dchunks.  0 = covered, 1 = not, -1 = bad grid.
+inline int wl_plan(const char* what, WarpArgs& a, int C, int in_dtype, int T, int TH, int ppd_override, int ppd_default, int ppd_max, dim3& grid) {
+    if (C != 32 || (in_dtype != PSCV_F16 && in_dtype != PSCV_BF16)) return 1;
+    if (a.ws > 16384 || a.hs > 16384) return 1;
+    const long tiles = (long)a.B * ((a.h + TH - 1) / TH) * ((a.w + T - 1) / T);
+    if (tiles >= (1L << 22)) return 1;
+    int ppd = ppd_override > 0 ? min((ppd_override + 1) & ~1, ppd_max) : ppd_default;
+    while (ppd > 4 && tiles * ((a.D + ppd - 1) / ppd) < 1024) ppd >>= 1;
+    a.ppd = ppd;
+    a.n_dchunks = (a.D + ppd - 1) / ppd;
+    const long nblk = tiles * a.n_dchunks;
+    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("%s: bad grid %ld", what, nblk); return -1; }
+    grid = dim3(8 * (unsigned)((tiles + 7) / 8), a.n_dchunks);
+    return 0;
+}
 
 }  // namespace pscv
