@@ -494,6 +494,26 @@ int pscv_colmap_fuse_pass_normals(int view, int tag, const float* const* depth, 
                                   void* stream);
 
 /*
+ * View covisibility from the depth maps (an addition to ABI 14: new exports only, no existing signature changes): the overlap graph of the COLMAP-style fusion without a sparse model
+ * ("Overlap without a sparse model").  For every ordered pair (v, u != v) of n_views views
+ *   counts[v][u][0] = the samples of v that u sees, counts[v][u][1] = those that are also consistent with u's depth map.
+ * A sample is a pixel (col, row) of v with row % stride == 0, col % stride == 0 and a valid depth (0 < d finite).  With
+ * X = R_v^T (d K_v^-1 (col, row, 1) - t_v) and q = K_u (R_u X + t_u), all fp64 and exactly as phase A of pscv_colmap_fuse_pass
+ * computes them, u sees the sample when q_z > 0 and the pixel (round(q_x / q_z), round(q_y / q_z)) (half away from zero, pixel =
+ * the integer pair, no half-pixel offset) lies inside u's map; it is consistent when u's depth d_u there is valid and
+ * |(q_z - d_u) / d_u| <= max_depth_error.
+ *   depth, hw   as pscv_colmap_fuse_pass (host arrays: n_views device pointers to fp32 [h_v, w_v], 0 = invalid; (h_v, w_v) pairs)
+ *   n_views     >= 2, not bounded by PSCV_FUSE_MAX_VIEWS;  cams device fp32 [n_views][PSCV_GEO_CAM_FLOATS]
+ *   stride      >= 1;  max_depth_error in (0, 1) relative
+ *   counts      device int32 [n_views][n_views][2], zero-filled by the call; the diagonal stays 0
+ *   workspace   device scratch of pscv_view_covisibility_workspace(n_views) bytes (the view table)
+ * No host synchronisation; integer atomics only, so the result does not depend on the order of the adds.
+ */
+long pscv_view_covisibility_workspace(int n_views);
+int pscv_view_covisibility(const float* const* depth, const int* hw, int n_views, const float* cams, int stride,
+                           float max_depth_error, int* counts, void* workspace, long workspace_bytes, void* stream);
+
+/*
  * Point-cloud metrics (ABI 11; the step after fusion).  Replaces the scipy cKDTree calls of evaluation/metrics.py: reduce_pts,
  * chamfer, chamfer_imw.  The rules are INTEGRATION.md section 2f.  Points are fp32 [n][3]; distances are fp64 from those
  * coordinates.  All calls are asynchronous on `stream`; every result is bit-reproducible.

@@ -58,31 +58,6 @@ static_assert(sizeof(CfArgsN) <= 4096, "the kernel-argument segment holds 4 KB")
 template <bool NORMALS> struct CfArgsOf { using type = CfArgs; };
 template <> struct CfArgsOf<true> { using type = CfArgsN; };
 
-// R^T (d K^-1 (x, y, 1) - t)
-__device__ __forceinline__ void cf_unproject(const float* c, double x, double y, double d, double& X, double& Y, double& Z) {
-    const float *Ki = c + CAM_KINV, *R = c + CAM_R, *t = c + CAM_T;
-    const double px = x * d, py = y * d, pz = d;
-    const double a0 = (double)Ki[0] * px + (double)Ki[1] * py + (double)Ki[2] * pz;
-    const double a1 = (double)Ki[3] * px + (double)Ki[4] * py + (double)Ki[5] * pz;
-    const double a2 = (double)Ki[6] * px + (double)Ki[7] * py + (double)Ki[8] * pz;
-    const double b0 = a0 - (double)t[0], b1 = a1 - (double)t[1], b2 = a2 - (double)t[2];
-    X = (double)R[0] * b0 + (double)R[3] * b1 + (double)R[6] * b2;
-    Y = (double)R[1] * b0 + (double)R[4] * b1 + (double)R[7] * b2;
-    Z = (double)R[2] * b0 + (double)R[5] * b1 + (double)R[8] * b2;
-}
-// K (R X + t)
-__device__ __forceinline__ void cf_project(const float* c, double X, double Y, double Z, double& x, double& y, double& z) {
-    const float *K = c + CAM_K, *R = c + CAM_R, *t = c + CAM_T;
-    const double e0 = (double)R[0] * X + (double)R[1] * Y + (double)R[2] * Z + (double)t[0];
-    const double e1 = (double)R[3] * X + (double)R[4] * Y + (double)R[5] * Z + (double)t[1];
-    const double e2 = (double)R[6] * X + (double)R[7] * Y + (double)R[8] * Z + (double)t[2];
-    x = (double)K[0] * e0 + (double)K[1] * e1 + (double)K[2] * e2;
-    y = (double)K[3] * e0 + (double)K[4] * e1 + (double)K[5] * e2;
-    z = (double)K[6] * e0 + (double)K[7] * e1 + (double)K[8] * e2;
-}
-__device__ __forceinline__ bool cf_depth_ok(float d) { return d > 0.0f && d <= 3.402823466e38f; }   // (false for NaN, inf)
-constexpr double CF_PIX_LIMIT = 1073741824.0;   // 2^30: a projection further out is no pixel of any view
-
 // window bit of round(P_m X) relative to the window at (c0x, c0y), or -1
 template <int W>
 __device__ __forceinline__ int cf_target(const float* cm, double X, double Y, double Z, int c0x, int c0y) {

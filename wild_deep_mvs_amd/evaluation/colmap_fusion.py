@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..utils.colmap_array import read_array
-from ..utils.colmap_model import overlap_from_counts, shared_point_counts
+from ..utils.colmap_model import overlap_from_counts, overlap_from_covisibility, shared_point_counts
 from ..utils.point_cloud import write_colmap_point_cloud
 from .filtering import depth_folder_name
 from .fusibile import get_mask
@@ -66,15 +66,38 @@ def view_inputs(args, batch, depth_file):
             batch["t"][0, 0].to(torch.float32).reshape(3, 1))
 
 
-def scene_overlap(args, names):
-    """COLMAP's overlapping images from the sparse model at IntRes/colmap_sparse/<scene> when there is one (shared 3-D points,
-    descending, ties by index, at most CHECK_NUM_IMAGES), else every other view.  -> (lists, description of the source)."""
-    sparse = Path(args.data_path) / "IntRes" / "colmap_sparse" / str(args.scene)
-    if (sparse / "images.bin").exists() and (sparse / "points3D.bin").exists():
-        counts = shared_point_counts(sparse, [n + ".jpg" for n in names])
-        return overlap_from_counts(counts, CHECK_NUM_IMAGES), f"sparse model {sparse}"
+OVERLAP_SOURCES = ("auto", "sparse", "all", "depth")
+
+
+def scene_overlap(args, names, depths=None, cams=None):
+    """COLMAP's overlapping images of every view, from the source ``args.fusion_overlap`` names (default "auto"):
+      "auto"    the sparse model at IntRes/colmap_sparse/<scene> when there is one (shared 3-D points, descending, ties by index,
+                at most CHECK_NUM_IMAGES), else every other view;
+      "sparse"  the sparse model, which has to be there;
+      "all"     every other view (the first CHECK_NUM_IMAGES by index);
+      "depth"   the views whose depth maps agree ("Overlap without a sparse model"):
+                ``ops.view_covisibility`` over ``depths`` (the masked maps on the GPU, the ones the fusion reads) and ``cams`` with
+                ``args.fusion_depth_threshold`` and ``args.fusion_overlap_stride`` (default 4), consistent samples descending.
+    -> (lists, description of the source)."""
+    mode = getattr(args, "fusion_overlap", "auto")
+    if mode not in OVERLAP_SOURCES:
+        raise ValueError(f"colmap_fusion: fusion_overlap must be one of {OVERLAP_SOURCES}, got {mode!r}")
     n = len(names)
-    return [[u for u in range(n) if u != v][:CHECK_NUM_IMAGES] for v in range(n)], "all other views (no sparse model)"
+    if mode == "depth":
+        if depths is None or cams is None:
+            raise ValueError("colmap_fusion: fusion_overlap 'depth' needs the depth maps and cameras on the GPU")
+        stride = int(getattr(args, "fusion_overlap_stride", 4))
+        counts = ops.view_covisibility(depths, cams, stride=stride, max_depth_error=args.fusion_depth_threshold)
+        return overlap_from_covisibility(counts, CHECK_NUM_IMAGES), f"depth-map covisibility (stride {stride})"
+    sparse = Path(args.data_path) / "IntRes" / "colmap_sparse" / str(args.scene)
+    have = (sparse / "images.bin").exists() and (sparse / "points3D.bin").exists()
+    if mode == "sparse" and not have:
+        raise FileNotFoundError(f"colmap_fusion: fusion_overlap 'sparse' needs the sparse model {sparse} (images.bin, points3D.bin)")
+    if have and mode != "all":
+        counts = shared_point_counts(sparse, [name + ".jpg" for name in names])
+        return overlap_from_counts(counts, CHECK_NUM_IMAGES), f"sparse model {sparse}"
+    return ([[u for u in range(n) if u != v][:CHECK_NUM_IMAGES] for v in range(n)],
+            "all other views" + (" (no sparse model)" if mode == "auto" else ""))
 
 
 def view_normals(normal_dir, filename, shape):
@@ -119,13 +142,14 @@ def colmap_fusion(dataloader, args):
         names.append(filename)
         if use_normals:
             normals.append(view_normals(normal_dir, filename, views[-1][0].shape))
-    overlap, source = scene_overlap(args, names)
-    print(f"COLMAP fusion of {len(views)} views, overlap from {source}")
     depths, colors, K, R, t = zip(*views)
     extra = dict(normals=[torch.from_numpy(n).cuda() for n in normals], max_normal_error=MAX_NORMAL_ERROR) if use_normals else {}
     with torch.no_grad():
         cams = ops.geo_filter_cams(torch.stack(K), torch.stack(R), torch.stack(t)).cuda()
-        xyz, normal, rgb, _ = ops.colmap_fuse([torch.from_numpy(d).cuda() for d in depths], [torch.from_numpy(c).cuda() for c in colors],
+        depths = [torch.from_numpy(d).cuda() for d in depths]          # uploaded once: the overlap pass and the fusion share them
+        overlap, source = scene_overlap(args, names, depths, cams)
+        print(f"COLMAP fusion of {len(views)} views, overlap from {source}")
+        xyz, normal, rgb, _ = ops.colmap_fuse(depths, [torch.from_numpy(c).cuda() for c in colors],
                                               cams, overlap, max_depth_error=args.fusion_depth_threshold,
                                               max_reproj_error=args.fusion_max_reproj_error, min_num_pixels=args.fusion_num_consistent,
                                               max_traversal_depth=MAX_TRAVERSAL_DEPTH, max_num_pixels=MAX_NUM_PIXELS, **extra)

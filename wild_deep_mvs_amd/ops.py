@@ -796,6 +796,33 @@ def colmap_fuse(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], 
     return res + (pixel,) if want_pixel else res
 
 
+def view_covisibility(depths: Sequence[torch.Tensor], cams: torch.Tensor, *, stride: int = 4, max_depth_error: float) -> torch.Tensor:
+    """Which views see the same surface, from the depth maps alone ("Overlap without a sparse model"):
+    depths V x fp32 [h_v,w_v] (0 = invalid), cams [V,30] (``geo_filter_cams``; intrinsics at each map's size), on the GPU, V >= 2
+    with no upper bound -> int32 [V,V,2] on the GPU.  ``[v,u,0]`` counts the samples of v (every ``stride``-th row and column with a
+    valid depth) that project inside u's map at a positive depth, ``[v,u,1]`` those whose depth there agrees with u's map within
+    ``max_depth_error`` (relative); pixel, rounding and depth test are those of phase A of ``colmap_fuse``.  The diagonal is 0.  One
+    pscv_view_covisibility call on the current stream, no host synchronisation; ``utils.colmap_model.overlap_from_covisibility``
+    turns the counts into the overlap lists of ``colmap_fuse``."""
+    cams = cams.to(torch.float32).contiguous()
+    _dev(cams)
+    depths, dptr, hw = _maps([d.to(torch.float32).contiguous() for d in depths], "pscv.view_covisibility")
+    n = len(depths)
+    _check_cams(cams, n if n else None, "pscv.view_covisibility")
+    dev = cams.device
+    if any(d.device != dev for d in depths):
+        raise ValueError("pscv.view_covisibility: depth maps and cams must be on the same device")
+    counts = torch.empty((n, n, 2), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(L.lib().pscv_view_covisibility_workspace(n)), 1), dtype=torch.uint8, device=dev)
+    samples = sum(-(-d.shape[0] // max(int(stride), 1)) * -(-d.shape[1] // max(int(stride), 1)) for d in depths)
+    rc = _launch("view_covisibility", lambda: L.lib().pscv_view_covisibility(
+        dptr, hw, n, _p(cams), int(stride), float(max_depth_error), _p(counts), _p(ws), int(ws.numel()), _stream()),
+        # per (sample, target): one depth gather at most; ~45 fp64 operations (projection, two divisions, the depth test)
+        cost=lambda: (float(samples * (n - 1) * 4), 45.0 * samples * (n - 1)))
+    L.check(rc, "pscv_view_covisibility")
+    return counts
+
+
 # --------------------------------------------------------------------------------------------
 # PatchMatch multi-view stereo (the COLMAP baseline: utils/colmap_utils.py:depthmap_colmap)
 # --------------------------------------------------------------------------------------------

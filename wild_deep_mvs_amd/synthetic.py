@@ -463,6 +463,20 @@ def make_yfcc_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, overlap: st
     return {"depths": depths, "colors": colors, "K": f32(K), "R": f32(R), "t": f32(t), "overlap": lists}
 
 
+def make_permuted_yfcc_fusion_scene(V: int, H: int, W: int, *, perm_seed: int = 0, **kw) -> Dict[str, object]:
+    """``make_yfcc_fusion_scene(V, H, W, **kw)`` with the view order shuffled by a seeded permutation, so that index neighbours are
+    not spatial neighbours (an unordered photo collection): view k of the result is view ``perm[k]`` of the grid rig.  The
+    ``overlap`` lists are renumbered with the views; ``perm`` is returned with the scene."""
+    sc = make_yfcc_fusion_scene(V, H, W, **kw)
+    perm = np.random.default_rng(perm_seed).permutation(V)
+    inv = np.empty(V, dtype=np.int64)
+    inv[perm] = np.arange(V)
+    idx = torch.from_numpy(perm)
+    return {"depths": [sc["depths"][p] for p in perm], "colors": [sc["colors"][p] for p in perm], "K": sc["K"][idx].contiguous(),
+            "R": sc["R"][idx].contiguous(), "t": sc["t"][idx].contiguous(),
+            "overlap": [[int(inv[u]) for u in sc["overlap"][p]] for p in perm], "perm": perm}
+
+
 def _pm_texture(X: np.ndarray, freqs: np.ndarray, phases: np.ndarray) -> np.ndarray:
     """Procedural colour in [0,1] of world points X [N,3]: per channel tanh of a sum of 3-D sinusoids (freqs [3,k,3], phases
     [3,k]), so every view sees the same surface pattern."""

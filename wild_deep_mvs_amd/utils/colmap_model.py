@@ -6,7 +6,8 @@
     points3D.bin  uint64 n; per point: uint64 point3D_id, double xyz[3], uint8 rgb[3], double error, uint64 track_length,
                   then track_length x (uint32 image_id, uint32 point2D_idx)
 
-The fusion step needs only which images see which points (``shared_point_counts``), to order COLMAP's overlapping images."""
+The fusion step needs only which images see which points (``shared_point_counts``), to order COLMAP's overlapping images.
+Without a sparse model the same lists come from the depth maps (``overlap_from_covisibility`` over ``ops.view_covisibility``)."""
 from __future__ import annotations
 
 import struct
@@ -88,3 +89,21 @@ def overlap_from_counts(counts, check_num_images: int = 50):
         others = [u for u in range(counts.shape[0]) if u != v and counts[v, u] > 0]
         out.append(sorted(others, key=lambda u: (-int(counts[v, u]), u))[:check_num_images])
     return out
+
+
+def overlap_from_covisibility(counts, check_num_images: int = 50, min_share: float = 0.0):
+    """The overlap lists of ``overlap_from_counts`` from the [V,V,2] counts of ``ops.view_covisibility`` (a tensor or an array):
+    view u is in v's list when ``counts[v,u,1]`` (the samples of v consistent with u's depth map) is positive and at least
+    ``min_share`` x the number of valid samples of v; ordered by that count as ``overlap_from_counts`` orders shared points.  The
+    number of valid samples of v is not an input: every valid sample is seen by at most every other view, so it is taken as the
+    largest seen count of v's row, ``max_u counts[v,u,0]``, which equals it as soon as one view sees all of v's samples and is a
+    lower bound (a more permissive share) otherwise.  A view with no valid depth gets an empty list."""
+    c = np.asarray(counts.cpu() if hasattr(counts, "cpu") else counts).astype(np.int64)
+    if c.ndim != 3 or c.shape[0] != c.shape[1] or c.shape[2] != 2:
+        raise ValueError(f"overlap_from_covisibility: counts [V,V,2] expected, got {c.shape}")
+    consistent = c[:, :, 1].copy()
+    if min_share > 0.0:
+        n_samples = c[:, :, 0].max(axis=1, keepdims=True)
+        consistent[consistent < min_share * n_samples] = 0
+    np.fill_diagonal(consistent, 0)
+    return overlap_from_counts(consistent, check_num_images)
