@@ -514,6 +514,41 @@ int pscv_view_covisibility(const float* const* depth, const int* hw, int n_views
                            float max_depth_error, int* counts, void* workspace, long workspace_bytes, void* stream);
 
 /*
+ * Scene set-up from a COLMAP sparse model (an addition to ABI 14: new exports only, no existing signature changes): what
+ * utils/colmap_utils.py:compute_src_imgs and compute_min_max_depth_yao compute for every YFCC scene (INTEGRATION.md section 2i,
+ * csrc/scene_setup.hip).  All arrays are device memory; all calls are asynchronous on `stream`, need no workspace and are
+ * bit-reproducible (integer atomics; one lane per output elsewhere).
+ *
+ * pscv_sparse_pair_counts: for every point p and every ordered pair (i, j) of its track
+ *   adj[i][j] += 1 (the diagonal included), and for i != j
+ *   adj_tri[i][j] += 1 when the angle between xyz_p and xyz_p + c[i][j], c[i][j] = R_i (R_j^T t_j) - t_i, acos of the clipped
+ *   cosine in degrees, all fp64 from the fp32 R and t, is > min_triangulation_angle (the reference's rel_opt_center; NaN fails).
+ *   xyz         fp64 [n_points][3]
+ *   track_off   int64 [n_points + 1], track_img int32 [nnz]: the tracks in CSR form, IMAGE INDICES in [0, n_images), sorted and
+ *               without duplicates per point (an index out of range, offsets outside [0, nnz], or a track of more than
+ *               n_images entries are skipped, never followed)
+ *   R, t        fp32 [n_images][3][3], [n_images][3];  1 <= n_images <= 46340;  min_triangulation_angle >= 0, degrees
+ *   adj, adj_tri  int32 [n_images][n_images], zero-filled by the call
+ *
+ * pscv_sparse_obs_depths: one 64-bit sort key per observation k of point obs_pt[k] by image obs_img[k]:
+ *   keys[k] = obs_img[k] << 32 | ordered(fp32((R_i x + t_i).z + 1e-6)), the depth of utils_3D.project in fp64 rounded to fp32;
+ *   ordered() maps fp32 to 32 bits that compare like the values.  An index out of range gives the key 2^63 - 1, behind every
+ *   image's keys whether they are sorted as signed or as unsigned integers (image indices are below 2^31).  Sorted
+ *   ascending (the caller's job), the keys of image i are the run [seg_off[i], seg_off[i+1]) of its depths in ascending order.
+ *
+ * pscv_segment_percentiles: out_lo[s], out_hi[s] = the q_lo and q_hi quantiles (fractions in [0,1]) of the depths in the sorted
+ *   keys' run [seg_off[s], seg_off[s+1]), numpy.percentile's linear interpolation in fp64; an empty run gives 0, 0.
+ *   seg_off     int64 [n_segments + 1];  out_lo, out_hi  fp64 [n_segments]
+ */
+int pscv_sparse_pair_counts(const double* xyz, const long* track_off, const int* track_img, long n_points, long nnz,
+                            const float* R, const float* t, int n_images, double min_triangulation_angle, int* adj, int* adj_tri,
+                            void* stream);
+int pscv_sparse_obs_depths(const double* xyz, long n_points, const int* obs_img, const int* obs_pt, long n_obs, const float* R,
+                           const float* t, int n_images, unsigned long long* keys, void* stream);
+int pscv_segment_percentiles(const unsigned long long* keys, long n_keys, const long* seg_off, int n_segments, double q_lo,
+                             double q_hi, double* out_lo, double* out_hi, void* stream);
+
+/*
  * Point-cloud metrics (ABI 11; the step after fusion).  Replaces the scipy cKDTree calls of evaluation/metrics.py: reduce_pts,
  * chamfer, chamfer_imw.  The rules are INTEGRATION.md section 2f.  Points are fp32 [n][3]; distances are fp64 from those
  * coordinates.  All calls are asynchronous on `stream`; every result is bit-reproducible.

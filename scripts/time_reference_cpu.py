@@ -2,7 +2,11 @@
 """Container-only cross-check of bench.py's cpu_baseline: times the REFERENCE's own hot path
 (/root/reference models/MVSNet/model.py: build_cost_volume :109-139, cost_regularization :74-84, softmax + regression :207-209,
 eval mode) and the oracle's streaming hot path on the same configuration-2 inputs and the same host threads.
-Needs /root/reference; never runs on the GPU box.  Usage: python scripts/time_reference_cpu.py [--threads N] [--reps 3]"""
+Needs /root/reference; never runs on the GPU box.  Usage: python scripts/time_reference_cpu.py [--threads N] [--reps 3]
+
+--scene-setup times instead the numpy restatement of the scene set-up (tests/_scene_setup_ref.py: pair counts, selection, depth
+ranges) on the scene of scripts/bench_scene_setup.py, once, and prints one JSON line.  It does not time the reference's own
+compute_src_imgs, which builds dense N x N arrays per point (hours at this size), and needs no reference tree."""
 import argparse
 import os
 import statistics
@@ -16,12 +20,33 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
 
 
+def scene_setup(args):
+    import json
+    from tests import _scene_setup_ref as SR
+    sc = SR.bench_scene(args.images, args.points, args.mean)
+    t0 = time.perf_counter()
+    adj, tri, _ = SR.pair_counts(sc["xyz"], sc["track_off"], sc["track_img"], sc["R"], sc["t"], 5.0)
+    t1 = time.perf_counter()
+    SR.select(adj, tri, 4)
+    t2 = time.perf_counter()
+    SR.depth_ranges(sc["xyz"], sc["obs_img"], sc["obs_pt"], sc["R"], sc["t"])
+    t3 = time.perf_counter()
+    print(json.dumps({"case": f"{args.images} images x {args.points} points", "observations": int(sc["track_off"][-1]),
+                      "numpy_pair_counts_s": t1 - t0, "numpy_select_s": t2 - t1, "numpy_depth_ranges_s": t3 - t2}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--threads", type=int, default=os.cpu_count())
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--scene-setup", action="store_true")
+    ap.add_argument("--images", type=int, default=2000)
+    ap.add_argument("--points", type=int, default=300000)
+    ap.add_argument("--mean", type=float, default=8.0)
     args = ap.parse_args()
     torch.set_num_threads(args.threads)
+    if args.scene_setup:
+        return scene_setup(args)
     import gen_golden
     gen_golden.import_reference()
     from models.MVSNet.model import MVSNet              # reference

@@ -824,6 +824,96 @@ def view_covisibility(depths: Sequence[torch.Tensor], cams: torch.Tensor, *, str
 
 
 # --------------------------------------------------------------------------------------------
+# scene set-up from a COLMAP sparse model (utils/colmap_utils.py: compute_src_imgs, compute_min_max_depth_yao)
+# --------------------------------------------------------------------------------------------
+def _sparse_inputs(what, xyz, R, t, **index_arrays):
+    """The shared checks of the two sparse-model ops: xyz fp64 [P,3], R fp32 [N,3,3], t fp32 [N,3] or [N,3,1], the named index
+    tensors (name -> (tensor, dtype)) one-dimensional, everything contiguous on one HIP device.  -> (t as [N,3], P, N)."""
+    tensors = [xyz, R, t] + [v[0] for v in index_arrays.values()]
+    _dev(*tensors)
+    if xyz.dtype != torch.float64 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{what}: xyz fp64 [P,3] expected, got {xyz.dtype} {tuple(xyz.shape)}")
+    if R.dtype != torch.float32 or R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] < 1:
+        raise ValueError(f"{what}: R fp32 [N,3,3] expected, got {R.dtype} {tuple(R.shape)}")
+    n = int(R.shape[0])
+    if t.dtype != torch.float32 or tuple(t.shape) not in ((n, 3), (n, 3, 1)):
+        raise ValueError(f"{what}: t fp32 [{n},3] (or [{n},3,1]) expected, got {t.dtype} {tuple(t.shape)}")
+    for name, (x, dtype) in index_arrays.items():
+        if x.dtype != dtype or x.dim() != 1:
+            raise ValueError(f"{what}: {name} must be a one-dimensional {dtype} tensor, got {x.dtype} {tuple(x.shape)}")
+    if any(x.device != xyz.device for x in tensors):
+        raise ValueError(f"{what}: all tensors must be on the same device")
+    return t.reshape(n, 3), int(xyz.shape[0]), n
+
+
+def _in_range(what, name, x, hi):
+    """Raise unless every index of ``x`` is in [0, hi): one host read per call; the kernels skip such entries, never follow them."""
+    if x.numel() and bool(((x < 0) | (x >= hi)).any()):
+        raise ValueError(f"{what}: {name} holds an index outside [0,{hi})")
+
+
+def sparse_pair_counts(xyz: torch.Tensor, track_off: torch.Tensor, track_img: torch.Tensor, R: torch.Tensor, t: torch.Tensor,
+                       min_triangulation_angle: float):
+    """The two matrices behind the reference's source-view selection (utils/colmap_utils.py:compute_src_imgs; INTEGRATION.md
+    section 2i): xyz fp64 [P,3]; the tracks in CSR form, track_off int64 [P+1] and track_img int32 [nnz] of IMAGE INDICES, sorted
+    and without duplicates per point; R fp32 [N,3,3], t fp32 [N,3] (or [N,3,1]), all on the GPU -> (adj, adj_tri) int32 [N,N] on
+    the GPU.  ``adj[i,j]`` counts the points images i and j both observe (the diagonal: the points of image i); ``adj_tri[i,j]``
+    those whose reference angle for the ordered pair exceeds ``min_triangulation_angle`` degrees (diagonal 0).  One
+    pscv_sparse_pair_counts call on the current stream; integer atomics, bit-reproducible.  The index checks before the launch
+    read a few flags back to the host (this is a once-per-scene step, not a hot path)."""
+    what = "pscv.sparse_pair_counts"
+    t, npts, n = _sparse_inputs(what, xyz, R, t, track_off=(track_off, torch.int64), track_img=(track_img, torch.int32))
+    nnz = int(track_img.numel())
+    if track_off.numel() != npts + 1:
+        raise ValueError(f"{what}: track_off must have P + 1 = {npts + 1} entries, got {track_off.numel()}")
+    if not float(min_triangulation_angle) >= 0.0:
+        raise ValueError(f"{what}: min_triangulation_angle={min_triangulation_angle} must be >= 0")
+    _in_range(what, "track_img", track_img, n)
+    if bool((track_off[1:] < track_off[:-1]).any()) or int(track_off[0]) != 0 or int(track_off[-1]) != nnz:
+        raise ValueError(f"{what}: track_off must rise from 0 to nnz = {nnz}")
+    adj = torch.empty((n, n), dtype=torch.int32, device=xyz.device)
+    adj_tri = torch.empty_like(adj)
+    rc = _launch("sparse_pair_counts", lambda: L.lib().pscv_sparse_pair_counts(
+        _p(xyz), _p(track_off), _p(track_img), npts, nnz, _p(R), _p(t), n, float(min_triangulation_angle), _p(adj), _p(adj_tri),
+        _stream()))
+    L.check(rc, "pscv_sparse_pair_counts")
+    return adj, adj_tri
+
+
+def sparse_depth_ranges(xyz: torch.Tensor, obs_img: torch.Tensor, obs_pt: torch.Tensor, R: torch.Tensor, t: torch.Tensor,
+                        perc=(1, 99)):
+    """Per-image depth range of the reference (utils/colmap_utils.py:compute_min_max_depth_yao): xyz
+    fp64 [P,3]; one entry per observation, obs_img int32 [M] (image index) and obs_pt int32 [M] (row of xyz), in any order, a
+    point as often as the image observes it; R fp32 [N,3,3], t fp32 [N,3] (or [N,3,1]), all on the GPU -> (depth_min, depth_max)
+    fp64 [N] on the GPU: the ``perc`` percentiles (numpy's linear interpolation) of the fp32-rounded depths (R x + t).z + 1e-6 of
+    each image's observations, 0 and 0 for an image without any.  pscv_sparse_obs_depths, ``torch.sort`` of the 64-bit keys
+    (plumbing), pscv_segment_percentiles, on the current stream."""
+    what = "pscv.sparse_depth_ranges"
+    t, npts, n = _sparse_inputs(what, xyz, R, t, obs_img=(obs_img, torch.int32), obs_pt=(obs_pt, torch.int32))
+    m = int(obs_img.numel())
+    if obs_pt.numel() != m:
+        raise ValueError(f"{what}: obs_img and obs_pt differ in length ({m} and {obs_pt.numel()})")
+    q_lo, q_hi = (float(q) / 100.0 for q in perc)
+    if not (0.0 <= q_lo <= 1.0 and 0.0 <= q_hi <= 1.0):
+        raise ValueError(f"{what}: percentiles {tuple(perc)} outside [0,100]")
+    _in_range(what, "obs_img", obs_img, n)
+    _in_range(what, "obs_pt", obs_pt, npts)
+    keys = torch.empty(m, dtype=torch.int64, device=xyz.device)
+    rc = _launch("sparse_obs_depths", lambda: L.lib().pscv_sparse_obs_depths(
+        _p(xyz), npts, _p(obs_img), _p(obs_pt), m, _p(R), _p(t), n, _p(keys), _stream()))
+    L.check(rc, "pscv_sparse_obs_depths")
+    keys = torch.sort(keys).values                 # (image indices are below 2^31: the signed order is the unsigned one)
+    seg_off = torch.zeros(n + 1, dtype=torch.int64, device=xyz.device)
+    seg_off[1:] = torch.cumsum(torch.bincount(obs_img.long(), minlength=n), 0)
+    lo = torch.empty(n, dtype=torch.float64, device=xyz.device)
+    hi = torch.empty_like(lo)
+    rc = _launch("segment_percentiles", lambda: L.lib().pscv_segment_percentiles(
+        _p(keys), m, _p(seg_off), n, q_lo, q_hi, _p(lo), _p(hi), _stream()))
+    L.check(rc, "pscv_segment_percentiles")
+    return lo, hi
+
+
+# --------------------------------------------------------------------------------------------
 # PatchMatch multi-view stereo (the COLMAP baseline: utils/colmap_utils.py:depthmap_colmap)
 # --------------------------------------------------------------------------------------------
 PM_DELTA0, PM_THETA0_DEG = 0.25, 30.0      # candidate 9: inverse-depth fraction and normal angle, halved every iteration

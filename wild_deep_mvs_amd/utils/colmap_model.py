@@ -1,12 +1,15 @@
-"""Minimal reader of COLMAP's binary sparse model: ``images.bin`` (image names and the 3-D point each keypoint observes) and
-``points3D.bin`` (point tracks), written from COLMAP's documented layout (little-endian):
+"""Minimal reader of COLMAP's binary sparse model: ``cameras.bin`` (intrinsics), ``images.bin`` (poses, image names and the 3-D
+point each keypoint observes) and ``points3D.bin`` (point tracks), written from COLMAP's documented layout (little-endian):
 
+    cameras.bin   uint64 n; per camera: int32 camera_id, int32 model_id, uint64 width, uint64 height, then the model's
+                  parameters as doubles (SIMPLE_PINHOLE f cx cy; PINHOLE fx fy cx cy; ... the table of COLMAP's camera models)
     images.bin    uint64 n; per image: uint32 image_id, double qvec[4], double tvec[3], uint32 camera_id, name (NUL-terminated),
                   uint64 n_points2D, then n_points2D x (double x, double y, int64 point3D_id; -1 when unmatched)
     points3D.bin  uint64 n; per point: uint64 point3D_id, double xyz[3], uint8 rgb[3], double error, uint64 track_length,
                   then track_length x (uint32 image_id, uint32 point2D_idx)
 
 The fusion step needs only which images see which points (``shared_point_counts``), to order COLMAP's overlapping images.
+Scene set-up (``utils/colmap_utils.py``) reads all three files.
 Without a sparse model the same lists come from the depth maps (``overlap_from_covisibility`` over ``ops.view_covisibility``)."""
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ from pathlib import Path
 
 import numpy as np
 
+Camera = namedtuple("Camera", ["id", "model", "width", "height", "params"])
 Image = namedtuple("Image", ["id", "qvec", "tvec", "camera_id", "name", "xys", "point3D_ids"])
 Point3D = namedtuple("Point3D", ["id", "xyz", "rgb", "error", "image_ids", "point2D_idxs"])
 
@@ -26,6 +30,26 @@ def _read(fh, fmt):
     if len(buf) != size:
         raise ValueError(f"{fh.name}: truncated COLMAP model file")
     return struct.unpack("<" + fmt, buf)
+
+
+# COLMAP's camera models: model_id -> (name, number of parameters)
+CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
+                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
+                 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+
+
+def read_cameras_binary(path):
+    """{camera_id: Camera} of a ``cameras.bin``."""
+    cameras = {}
+    with open(path, "rb") as fh:
+        (n,) = _read(fh, "Q")
+        for _ in range(n):
+            camera_id, model_id, width, height = _read(fh, "iiQQ")
+            if model_id not in CAMERA_MODELS:
+                raise ValueError(f"{path}: unknown camera model id {model_id}")
+            name, nparams = CAMERA_MODELS[model_id]
+            cameras[camera_id] = Camera(camera_id, name, width, height, np.array(_read(fh, f"{nparams}d")))
+    return cameras
 
 
 def read_images_binary(path):

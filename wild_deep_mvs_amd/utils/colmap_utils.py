@@ -1,0 +1,143 @@
+"""Scene set-up from a COLMAP sparse model, the part of the reference's ``utils/colmap_utils.py`` that every YFCC scene starts with
+(``data/yfcc_scene.py:init_calibs``): calibration arrays, each image's source views and its depth range.  INTEGRATION.md
+section 2i.
+
+``compute_Kmatrix_colmap`` and ``get_calib_from_sparse`` are host code.  ``compute_src_imgs`` and ``compute_min_max_depth_yao``
+flatten the model into index arrays on the host (once, O(observations)), upload them and run on the GPU:
+``ops.sparse_pair_counts`` / ``ops.sparse_depth_ranges`` (csrc/scene_setup.hip).  There is no CPU path: without a HIP device the
+ops raise.  The functions take the dicts of namedtuples of ``utils/colmap_model.py`` or of the reference's own model reader
+(same field names), in the dict's order, which is the order of the rows of ``K``, ``R`` and ``t``."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import ops
+
+
+def compute_Kmatrix_colmap(params):
+    """3 x 3 intrinsics of a PINHOLE camera's (fx, fy, cx, cy)."""
+    return np.array([[params[0], 0, params[2]], [0, params[1], params[3]], [0, 0, 1]])
+
+
+def _rotations_from_qvec(qvec):
+    """[n,4] unit quaternions in COLMAP's order (w, x, y, z) -> [n,3,3] rotations: with scalar part w and vector part v,
+    R = (w^2 - v.v) I + 2 v v^T + 2 w [v]_x, where [v]_x is the cross-product matrix of v."""
+    qvec = np.asarray(qvec, dtype=np.float64).reshape(-1, 4)
+    w, v = qvec[:, 0], qvec[:, 1:]
+    cross = np.zeros((len(qvec), 3, 3))
+    cross[:, 0, 1], cross[:, 0, 2], cross[:, 1, 2] = -v[:, 2], v[:, 1], -v[:, 0]
+    cross -= cross.transpose(0, 2, 1)
+    scale = w * w - np.einsum("ni,ni->n", v, v)
+    return scale[:, None, None] * np.eye(3) + 2.0 * np.einsum("ni,nj->nij", v, v) + 2.0 * w[:, None, None] * cross
+
+
+def get_calib_from_sparse(cameras, images):
+    """(K fp32 [N,3,3], R fp32 [N,3,3], t fp32 [N,3,1], sizes fp32 [N,2] = (width, height)) in the order of ``images``."""
+    cams = [cameras[images[idx].camera_id] for idx in images]
+    K = np.array([compute_Kmatrix_colmap(c.params) for c in cams], dtype=np.float32)
+    sizes = np.array([[c.width, c.height] for c in cams], dtype=np.float32).reshape(-1, 2)
+    R = _rotations_from_qvec([images[idx].qvec for idx in images]).astype(np.float32)
+    t = np.array([images[idx].tvec for idx in images], dtype=np.float32).reshape(-1, 3)[..., None]
+    return K, R, t, sizes
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("colmap_utils: source views and depth ranges are computed on the MI355X only "
+                           "(there is no CPU / PyTorch fallback); no HIP device is available")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _pose(R, t, n, dev):
+    R = torch.as_tensor(np.asarray(R.cpu() if hasattr(R, "cpu") else R), dtype=torch.float32).reshape(-1, 3, 3)
+    t = torch.as_tensor(np.asarray(t.cpu() if hasattr(t, "cpu") else t), dtype=torch.float32).reshape(-1, 3)
+    if R.shape[0] != n or t.shape[0] != n:
+        raise ValueError(f"colmap_utils: {n} images but R {tuple(R.shape)} and t {tuple(t.shape)}")
+    return R.contiguous().to(dev), t.contiguous().to(dev)
+
+
+def _lookup(ids, sorted_keys, order, what):
+    """Position in the dict's order of every id of ``ids`` (``sorted_keys`` = the dict's keys sorted, ``order`` = their positions);
+    an unknown id raises KeyError, as the reference's dict lookup does."""
+    pos = np.searchsorted(sorted_keys, ids)
+    pos[pos >= len(sorted_keys)] = 0
+    bad = sorted_keys[pos] != ids if len(sorted_keys) else np.ones(len(ids), dtype=bool)
+    if bad.any():
+        raise KeyError(f"{what} {int(np.asarray(ids)[bad][0])} is not in the model")
+    return order[pos]
+
+
+def _index(keys):
+    keys = np.fromiter(keys, dtype=np.int64)
+    order = np.argsort(keys, kind="stable")
+    return keys[order], order
+
+
+def flatten_tracks(images, points3d):
+    """(xyz fp64 [P,3], track_off int64 [P+1], track_img int32 [nnz]): the tracks of ``points3d`` in CSR form over image INDICES
+    (positions in ``images``), sorted and de-duplicated per point -- the inputs of ``ops.sparse_pair_counts``."""
+    pts = list(points3d.values())
+    xyz = np.array([p.xyz for p in pts], dtype=np.float64).reshape(-1, 3)
+    lens = np.array([len(p.image_ids) for p in pts], dtype=np.int64)
+    ids = np.concatenate([np.asarray(p.image_ids, dtype=np.int64) for p in pts]) if len(pts) else np.zeros(0, np.int64)
+    img = _lookup(ids, *_index(images.keys()), "image id") if len(ids) else np.zeros(0, np.int64)
+    n = max(len(images), 1)
+    pair = np.unique(np.repeat(np.arange(len(pts), dtype=np.int64), lens) * n + img)     # sorted by point, then image; no duplicates
+    off = np.zeros(len(pts) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pair // n, minlength=len(pts)), out=off[1:])
+    return xyz, off, (pair % n).astype(np.int32)
+
+
+def flatten_observations(points3d, imgs):
+    """(xyz fp64 [P,3], obs_img int32 [M], obs_pt int32 [M]): every keypoint of ``imgs`` with a 3-D point (id != -1), image by
+    image, as (image index, row of xyz) -- the inputs of ``ops.sparse_depth_ranges``."""
+    xyz = np.array([p.xyz for p in points3d.values()], dtype=np.float64).reshape(-1, 3)
+    per = [np.asarray(im.point3D_ids, dtype=np.int64) for im in imgs.values()]
+    per = [p[p != -1] for p in per]
+    ids = np.concatenate(per) if per else np.zeros(0, np.int64)
+    obs_img = np.repeat(np.arange(len(per), dtype=np.int32), [len(p) for p in per]) if per else np.zeros(0, np.int32)
+    obs_pt = _lookup(ids, *_index(points3d.keys()), "point3D id") if len(ids) else np.zeros(0, np.int64)
+    return xyz, obs_img.astype(np.int32), obs_pt.astype(np.int32)
+
+
+def select_source_views(adj, adj_tri, nsrc):
+    """The reference's choice from the two count matrices (device tensors) -> int64 [N, min(nsrc, N)] on the device: row i zeroes
+    every ``adj[i,j]`` with ``adj_tri[i,j] < 0.75 adj[i,j]`` (4 adj_tri < 3 adj, exact in integers), sorts the row ascending with a
+    stable sort and keeps the last ``nsrc`` indices in that order -- ``np.argsort(row)[-nsrc:]`` wherever that is deterministic."""
+    a, tri = adj.to(torch.int64), adj_tri.to(torch.int64)
+    common = torch.where(4 * tri < 3 * a, torch.zeros_like(a), a)
+    return torch.sort(common, dim=1, stable=True).indices[:, -int(nsrc):]
+
+
+def compute_src_imgs(images, points3d, R, t, min_triangulation_angle, nsrc, nb_points_thresh):
+    """Each image's ``nsrc`` source views, a list of lists of image indices (ascending by shared points, best last), as the
+    reference's function of the same name returns with ``nb_points_thresh=None``."""
+    if nb_points_thresh is not None:
+        raise NotImplementedError(
+            "compute_src_imgs: nb_points_thresh is not supported.  The reference's branch takes len() of np.nonzero()'s TUPLE, "
+            "which is 1, so it returns an empty list for every image whenever nsrc > 1, and otherwise draws at random: there is "
+            "no defined answer to reproduce.  Pass nb_points_thresh=None.")
+    if int(nsrc) < 1:
+        raise ValueError(f"compute_src_imgs: nsrc={nsrc} < 1")
+    dev = _device()
+    xyz, off, img = flatten_tracks(images, points3d)
+    Rd, td = _pose(R, t, len(images), dev)
+    adj, adj_tri = ops.sparse_pair_counts(torch.from_numpy(xyz).to(dev), torch.from_numpy(off).to(dev), torch.from_numpy(img).to(dev),
+                                          Rd, td, float(min_triangulation_angle))
+    return select_source_views(adj, adj_tri, nsrc).cpu().tolist()
+
+
+def compute_min_max_depth_yao(points3d, imgs, K, R, t, perc=(1, 99)):
+    """(depth_min fp64 [N], depth_max fp64 [N], None, None): per image the ``perc`` percentiles of the depths of the 3-D points it
+    observes (0, 0 for an image that observes none), as the reference's function of the same name.  ``K`` enters the reference's
+    depth only through its last row, which must be (0, 0, 1)."""
+    K = np.asarray(K.cpu() if hasattr(K, "cpu") else K).reshape(-1, 3, 3)
+    if len(K) != len(imgs) or not np.array_equal(K[:, 2], np.broadcast_to(np.array([0, 0, 1], dtype=K.dtype), (len(K), 3))):
+        raise ValueError("compute_min_max_depth_yao: K must be [N,3,3] with last rows (0, 0, 1)")
+    dev = _device()
+    xyz, obs_img, obs_pt = flatten_observations(points3d, imgs)
+    Rd, td = _pose(R, t, len(imgs), dev)
+    lo, hi = ops.sparse_depth_ranges(torch.from_numpy(xyz).to(dev), torch.from_numpy(obs_img).to(dev), torch.from_numpy(obs_pt).to(dev),
+                                     Rd, td, perc)
+    return lo.cpu().numpy(), hi.cpu().numpy(), None, None
