@@ -549,6 +549,34 @@ int pscv_segment_percentiles(const unsigned long long* keys, long n_keys, const 
                              double q_hi, double* out_lo, double* out_hi, void* stream);
 
 /*
+ * Visible depth ranges of image tuples (an addition to ABI 14: new exports only): utils/colmap_utils.py:
+ * compute_min_max_depth_visible for T tuples of V images in one call, the depth range of a MegaDepth training tuple
+ * (csrc/scene_setup.hip).  For tuple k with views v = 0..V-1 (image indices tuples[k][v]):
+ *   a point takes part when at least 3 of the tuple's images are in its track; n_pts[k] counts those points;
+ *   it is projected into every view, all in fp64 without fused multiply-adds from the fp32 K, R, t and the fp64 xyz:
+ *     y = R x + t,  u = K y,  depth = u_z + 1e-6,  proj = u_xy / depth;
+ *   it is valid in view v iff proj_x >= 0 && proj_y >= 0 && proj_x < w && proj_y < h && depth > 0 (a NaN fails);
+ *   min_d[k][v], max_d[k][v] are the smallest and largest valid depth, min_row[k][v], max_row[k][v] the LOWEST row of xyz that
+ *   attains each (numpy's nanargmin / nanargmax over the participating points); a view without a valid point gives NaN depths
+ *   and rows of -1.
+ *   xyz, track_off, track_img   as pscv_sparse_pair_counts (no image twice in a track)
+ *   tuples      int32 [T][V] image indices in [0, n_images), distinct within a tuple.  The call copies them to the host and checks
+ *               this before it launches: ONE synchronisation of `stream`, the only one of this header's scene set-up calls
+ *   K           fp32 [T][V][3][3] the views' intrinsics (per tuple: the miner rescales them);  R, t fp32 [n_images][3][3], [n_images][3]
+ *   sizes       fp64 [T][V][2] = (w, h)
+ *   3 <= V <= 32;  1 <= T <= 65535;  1 <= n_images <= 46340
+ *   min_d, max_d fp64 [T][V];  min_row, max_row int64 [T][V];  n_pts int32 [T]
+ *   workspace   device scratch of pscv_tuple_visible_depths_workspace(T, V) bytes, initialised by the call
+ * Integer minima and maxima (of the ordered bits of the depths, then of the rows): exact fp64 depths, and no result depends on the
+ * order of the atomics.
+ */
+long pscv_tuple_visible_depths_workspace(int n_tuples, int n_views);
+int pscv_tuple_visible_depths(const double* xyz, const long* track_off, const int* track_img, long n_points, long nnz,
+                              const int* tuples, const float* K, const float* R, const float* t, const double* sizes, int n_images,
+                              int T, int V, double* min_d, double* max_d, long* min_row, long* max_row, int* n_pts, void* workspace,
+                              void* stream);
+
+/*
  * Point-cloud metrics (ABI 11; the step after fusion).  Replaces the scipy cKDTree calls of evaluation/metrics.py: reduce_pts,
  * chamfer, chamfer_imw.  The rules are INTEGRATION.md section 2f.  Points are fp32 [n][3]; distances are fp64 from those
  * coordinates.  All calls are asynchronous on `stream`; every result is bit-reproducible.

@@ -1,5 +1,6 @@
 // Scene set-up from a COLMAP sparse model: the pair counts behind the source-view selection (utils/colmap_utils.py:
-// compute_src_imgs) and the per-image depth ranges (compute_min_max_depth_yao).  INTEGRATION.md section 2i.  gfx950.
+// compute_src_imgs), the per-image depth ranges (compute_min_max_depth_yao), INTEGRATION.md section 2i, and the visible depth
+// ranges of image tuples (compute_min_max_depth_visible), section 2j.  gfx950.
 //
 // ---- pscv_sparse_pair_counts ------------------------------------------------------------------------------------------
 // The reference builds, for all N images at once,
@@ -33,6 +34,23 @@
 // order alike as signed and as unsigned 64-bit integers); the caller sorts the
 // keys, after which image i's depths are the ascending run [seg_off[i], seg_off[i+1]).  One lane per image then evaluates
 // numpy's percentile (method "linear"): virtual index (n - 1) q, lerp of the two neighbours as numpy's _lerp does.
+//
+// ---- pscv_tuple_visible_depths ---------------------------------------------------------------------------------------
+// compute_min_max_depth_visible for T tuples of V images at once (the MegaDepth tuple mining).  A point
+// takes part in tuple k when at least 3 of the tuple's images are in its track; it is then projected into ALL V views,
+//     y = R x + t,  u = K y,  depth = u_z + 1e-6,  proj = u_xy / depth      (fp64 from the fp32 K, R, t; no fused multiply-adds)
+// and is valid in a view iff 0 <= proj_x < w, 0 <= proj_y < h and depth > 0 (NaN fails).  Per (tuple, view): the smallest and the
+// largest valid depth and the LOWEST row of xyz that attains each (numpy's nanargmin / nanargmax over the participating points).
+// Mapping: grid (chunks of TVD_THREADS * TVD_ITERS points, T).  A workgroup keeps its tuple's membership bitmask (one bit per
+// image, ceil(N / 32) words) and the V cameras in LDS; each lane walks one point's track against the mask and, from 3 hits on,
+// projects into the V views.  Pass 1 takes the minimum / maximum of the ORDERED BITS of the fp64 depths: a lane reads the
+// workgroup's running value from LDS and issues a 64-bit LDS atomic only when its own key improves it (the value moves one way
+// only, so a stale read costs an atomic, never a result), and each workgroup ends with one global 64-bit atomic per view and
+// bound.  Pass 2 repeats the walk with the identical arithmetic and takes the minimum ROW among the points whose key equals the
+// winner (fp64 depth plus a row do not fit one 64-bit key).  min / max of integers: no result depends on the order of the atomics.
+// A lane walks its whole track alone, however long; tracks are short on average and the walk is one LDS read per observation.
+#include <vector>
+
 #include "pscv_common.h"
 
 namespace pscv {
@@ -172,6 +190,151 @@ __global__ __launch_bounds__(SP_THREADS) void segment_percentiles_kernel(const u
     out_hi[i] = hi;
 }
 
+// ---- visible depth ranges of tuples ------------------------------------------------------------------------------------------
+constexpr int TVD_THREADS = 256;
+constexpr int TVD_ITERS = 8;                                   // points per lane: one mask / camera set-up per 2048 points
+constexpr int TVD_MAX_VIEWS = 32;
+constexpr int TVD_MAX_IMAGES = 46340;
+constexpr int TVD_MASK_WORDS = (TVD_MAX_IMAGES + 31) / 32;
+constexpr unsigned long long TVD_NONE = ~0ull;                 // "no key yet" of a minimum; a maximum starts at 0
+
+struct TvdCam {
+    float K[9], R[9], t[3];
+    int ok;                                                    // 0: the tuple's index is out of range (the host checks): no point is valid
+    double w, h;
+};
+
+// fp64 -> 64 bits that order like the values
+__device__ __forceinline__ unsigned long long tvd_ordered_bits(double d) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(d);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double tvd_from_ordered_bits(unsigned long long o) {
+    return __longlong_as_double((long long)((o >> 63) ? (o & 0x7fffffffffffffffull) : ~o));
+}
+
+// depth of x in the view and whether it is valid there; both passes call this, so their depths agree bit for bit
+__device__ __forceinline__ bool tvd_project(const TvdCam& c, double X, double Y, double Z, double& depth) {
+#pragma clang fp contract(off)
+    const double x = (double)c.R[0] * X + (double)c.R[1] * Y + (double)c.R[2] * Z + (double)c.t[0];
+    const double y = (double)c.R[3] * X + (double)c.R[4] * Y + (double)c.R[5] * Z + (double)c.t[1];
+    const double z = (double)c.R[6] * X + (double)c.R[7] * Y + (double)c.R[8] * Z + (double)c.t[2];
+    const double u = (double)c.K[0] * x + (double)c.K[1] * y + (double)c.K[2] * z;
+    const double v = (double)c.K[3] * x + (double)c.K[4] * y + (double)c.K[5] * z;
+    depth = (double)c.K[6] * x + (double)c.K[7] * y + (double)c.K[8] * z + 1e-6;
+    const double px = u / depth, py = v / depth;
+    return c.ok && px >= 0.0 && py >= 0.0 && px < c.w && py < c.h && depth > 0.0;    // (a NaN fails every comparison)
+}
+
+__device__ __forceinline__ unsigned long long tvd_peek(const unsigned long long* a) {
+    return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// ws: four planes of T * V 64-bit words -- the minimum's key, the maximum's key, the minimum's row, the maximum's row
+__global__ __launch_bounds__(TVD_THREADS) void tuple_visible_init_kernel(unsigned long long* ws, int* n_pts, long TV, int T) {
+    const long k = (long)blockIdx.x * TVD_THREADS + threadIdx.x;
+    if (k < TV) {
+        ws[k] = TVD_NONE;
+        ws[TV + k] = 0;
+        ws[2 * TV + k] = TVD_NONE;
+        ws[3 * TV + k] = TVD_NONE;
+    }
+    if (k < T) n_pts[k] = 0;
+}
+
+template <int PASS>
+__global__ __launch_bounds__(TVD_THREADS) void tuple_visible_kernel(const double* __restrict__ xyz, const long* __restrict__ track_off,
+                                                                    const int* __restrict__ track_img, long P, long nnz,
+                                                                    const int* __restrict__ tuples, const float* __restrict__ K,
+                                                                    const float* __restrict__ R, const float* __restrict__ t,
+                                                                    const double* __restrict__ sizes, int N, int V,
+                                                                    unsigned long long* ws, int* n_pts) {
+    __shared__ unsigned mask[TVD_MASK_WORDS];
+    __shared__ TvdCam cam[TVD_MAX_VIEWS];
+    __shared__ unsigned long long lo[TVD_MAX_VIEWS], hi[TVD_MAX_VIEWS];          // pass 1: keys; pass 2: rows
+    __shared__ unsigned long long want_lo[TVD_MAX_VIEWS], want_hi[TVD_MAX_VIEWS];  // pass 2: the winning keys
+    __shared__ int cnt;
+    const int tid = threadIdx.x;
+    const long kv = (long)blockIdx.y * V, TV = (long)gridDim.y * V;
+    for (int i = tid; i < ((N + 31) >> 5); i += TVD_THREADS) mask[i] = 0;
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+    if (tid < V) {
+        const int idx = tuples[kv + tid];
+        TvdCam& c = cam[tid];
+        c.ok = (unsigned)idx < (unsigned)N;
+        if (c.ok) atomicOr(&mask[idx >> 5], 1u << (idx & 31));
+        for (int e = 0; e < 9; ++e) {
+            c.K[e] = K[(kv + tid) * 9 + e];
+            c.R[e] = c.ok ? R[(long)idx * 9 + e] : 0.f;
+        }
+        for (int e = 0; e < 3; ++e) c.t[e] = c.ok ? t[(long)idx * 3 + e] : 0.f;
+        c.w = sizes[(kv + tid) * 2];
+        c.h = sizes[(kv + tid) * 2 + 1];
+        lo[tid] = TVD_NONE;
+        hi[tid] = PASS == 1 ? 0 : TVD_NONE;
+        if (PASS == 2) {
+            want_lo[tid] = ws[kv + tid];
+            want_hi[tid] = ws[TV + kv + tid];
+        }
+    }
+    __syncthreads();
+    const long base = (long)blockIdx.x * (TVD_THREADS * TVD_ITERS);
+    int mine = 0;
+    for (int it = 0; it < TVD_ITERS; ++it) {
+        const long p = base + (long)it * TVD_THREADS + tid;
+        if (p >= P) break;
+        const long beg = track_off[p], end = track_off[p + 1];
+        if (beg < 0 || end > nnz || end - beg < 3) continue;
+        int hits = 0;
+        for (long q = beg; q < end; ++q) {
+            const unsigned i = (unsigned)track_img[q];
+            if (i < (unsigned)N) hits += (mask[i >> 5] >> (i & 31)) & 1u;
+        }
+        if (hits < 3) continue;
+        ++mine;
+        const double X = xyz[3 * p], Y = xyz[3 * p + 1], Z = xyz[3 * p + 2];
+        for (int v = 0; v < V; ++v) {
+            double depth;
+            if (!tvd_project(cam[v], X, Y, Z, depth)) continue;
+            const unsigned long long key = tvd_ordered_bits(depth);
+            if (PASS == 1) {
+                if (key < tvd_peek(&lo[v])) atomicMin(&lo[v], key);
+                if (key > tvd_peek(&hi[v])) atomicMax(&hi[v], key);
+            } else {
+                const unsigned long long row = (unsigned long long)p;
+                if (key == want_lo[v] && row < tvd_peek(&lo[v])) atomicMin(&lo[v], row);
+                if (key == want_hi[v] && row < tvd_peek(&hi[v])) atomicMin(&hi[v], row);
+            }
+        }
+    }
+    if (PASS == 1 && mine) atomicAdd(&cnt, mine);
+    __syncthreads();
+    if (tid < V) {
+        if (PASS == 1) {
+            if (lo[tid] != TVD_NONE) atomicMin(ws + kv + tid, lo[tid]);
+            if (hi[tid] != 0) atomicMax(ws + TV + kv + tid, hi[tid]);
+        } else {
+            if (lo[tid] != TVD_NONE) atomicMin(ws + 2 * TV + kv + tid, lo[tid]);
+            if (hi[tid] != TVD_NONE) atomicMin(ws + 3 * TV + kv + tid, hi[tid]);
+        }
+    }
+    if (PASS == 1 && tid == 0 && cnt) atomicAdd(n_pts + blockIdx.y, cnt);
+}
+
+__global__ __launch_bounds__(TVD_THREADS) void tuple_visible_finish_kernel(const unsigned long long* __restrict__ ws, long TV,
+                                                                           double* __restrict__ min_d, double* __restrict__ max_d,
+                                                                           long* __restrict__ min_row, long* __restrict__ max_row) {
+    const long k = (long)blockIdx.x * TVD_THREADS + threadIdx.x;
+    if (k >= TV) return;
+    const bool any = ws[TV + k] != 0 && ws[2 * TV + k] != TVD_NONE && ws[3 * TV + k] != TVD_NONE;     // a view without a valid point
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    min_d[k] = any ? tvd_from_ordered_bits(ws[k]) : nan;
+    max_d[k] = any ? tvd_from_ordered_bits(ws[TV + k]) : nan;
+    min_row[k] = any ? (long)ws[2 * TV + k] : -1;
+    max_row[k] = any ? (long)ws[3 * TV + k] : -1;
+}
+
 }  // namespace pscv
 
 extern "C" int pscv_sparse_pair_counts(const double* xyz, const long* track_off, const int* track_img, long n_points, long nnz,
@@ -220,4 +383,64 @@ extern "C" int pscv_segment_percentiles(const unsigned long long* keys, long n_k
     PSCV_CHECK_ARG(q_lo >= 0.0 && q_lo <= 1.0 && q_hi >= 0.0 && q_hi <= 1.0, "%s: quantiles %g, %g outside [0,1]", what, q_lo, q_hi);
     return launch(what, segment_percentiles_kernel, dim3((unsigned)((n_segments + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0,
                   reinterpret_cast<hipStream_t>(stream), keys, n_keys, seg_off, n_segments, q_lo, q_hi, out_lo, out_hi);
+}
+
+extern "C" long pscv_tuple_visible_depths_workspace(int n_tuples, int n_views) {
+    if (n_tuples < 1 || n_views < 1) return 0;
+    return 4L * (long)sizeof(unsigned long long) * n_tuples * n_views;
+}
+
+extern "C" int pscv_tuple_visible_depths(const double* xyz, const long* track_off, const int* track_img, long n_points, long nnz,
+                                         const int* tuples, const float* K, const float* R, const float* t, const double* sizes,
+                                         int n_images, int T, int V, double* min_d, double* max_d, long* min_row, long* max_row,
+                                         int* n_pts, void* workspace, void* stream) {
+    using namespace pscv;
+    const char* what = "pscv_tuple_visible_depths";
+    PSCV_CHECK_ARG(V >= 3 && V <= TVD_MAX_VIEWS, "%s: V=%d outside [3,%d] (a point takes part from 3 of the tuple's views on)", what, V,
+                   TVD_MAX_VIEWS);
+    PSCV_CHECK_ARG(T >= 1 && T <= 65535, "%s: T=%d outside [1,65535] (one grid row per tuple)", what, T);
+    PSCV_CHECK_ARG(n_images >= 1 && n_images <= TVD_MAX_IMAGES, "%s: n_images=%d outside [1,%d] (the membership bitmask in LDS)", what,
+                   n_images, TVD_MAX_IMAGES);
+    PSCV_CHECK_ARG(n_points >= 0 && nnz >= 0, "%s: n_points=%ld, nnz=%ld: negative", what, n_points, nnz);
+    PSCV_CHECK_ARG(tuples && K && R && t && sizes && min_d && max_d && min_row && max_row && n_pts && workspace,
+                   "%s: null pointer argument", what);
+    PSCV_CHECK_ARG(n_points == 0 || (xyz && track_off), "%s: null pointer argument", what);
+    PSCV_CHECK_ARG(nnz == 0 || track_img, "%s: null pointer argument", what);
+    const long chunk = (long)TVD_THREADS * TVD_ITERS;
+    const long blocks = (n_points + chunk - 1) / chunk;
+    PSCV_CHECK_ARG(blocks < (1L << 31), "%s: n_points=%ld: more than 2^31 workgroups", what, n_points);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the tuples are read back once (T * V ints, one synchronisation of the stream): a repeated index would count a point's
+    // observation twice, one out of range has no camera
+    const long TV = (long)T * V;
+    std::vector<int> host(TV);
+    hipError_t e = hipMemcpyAsync(host.data(), tuples, sizeof(int) * TV, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        set_error("%s: reading the tuples back failed: %s", what, hipGetErrorString(e));
+        return -2;
+    }
+    for (int k = 0; k < T; ++k)
+        for (int a = 0; a < V; ++a) {
+            const int ia = host[(long)k * V + a];
+            PSCV_CHECK_ARG(ia >= 0 && ia < n_images, "%s: tuples[%d][%d]=%d outside [0,%d)", what, k, a, ia, n_images);
+            for (int b = 0; b < a; ++b)
+                PSCV_CHECK_ARG(host[(long)k * V + b] != ia, "%s: tuples[%d] names image %d twice", what, k, ia);
+        }
+    unsigned long long* ws = static_cast<unsigned long long*>(workspace);
+    const long most = TV > T ? TV : (long)T;
+    int rc = launch(what, tuple_visible_init_kernel, dim3((unsigned)((most + TVD_THREADS - 1) / TVD_THREADS)), dim3(TVD_THREADS), 0, st, ws,
+                    n_pts, TV, T);
+    if (rc) return rc;
+    if (blocks > 0) {
+        const dim3 grid((unsigned)blocks, (unsigned)T);
+        rc = launch(what, tuple_visible_kernel<1>, grid, dim3(TVD_THREADS), 0, st, xyz, track_off, track_img, n_points, nnz, tuples, K, R,
+                    t, sizes, n_images, V, ws, n_pts);
+        if (rc) return rc;
+        rc = launch(what, tuple_visible_kernel<2>, grid, dim3(TVD_THREADS), 0, st, xyz, track_off, track_img, n_points, nnz, tuples, K, R,
+                    t, sizes, n_images, V, ws, n_pts);
+        if (rc) return rc;
+    }
+    return launch(what, tuple_visible_finish_kernel, dim3((unsigned)((TV + TVD_THREADS - 1) / TVD_THREADS)), dim3(TVD_THREADS), 0, st,
+                  (const unsigned long long*)ws, TV, min_d, max_d, min_row, max_row);
 }

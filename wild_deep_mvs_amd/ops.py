@@ -913,6 +913,65 @@ def sparse_depth_ranges(xyz: torch.Tensor, obs_img: torch.Tensor, obs_pt: torch.
     return lo, hi
 
 
+TVD_MAX_TUPLES = 65535      # of one pscv_tuple_visible_depths call (one grid row per tuple); longer lists go in chunks
+
+
+def tuple_visible_depths(xyz: torch.Tensor, track_off: torch.Tensor, track_img: torch.Tensor, tuples: torch.Tensor, K: torch.Tensor,
+                         R: torch.Tensor, t: torch.Tensor, sizes: torch.Tensor):
+    """The visible depth range of many image tuples at once (utils/colmap_utils.py:compute_min_max_depth_visible; INTEGRATION.md
+    section 2j): xyz fp64 [P,3] and the tracks in CSR form as for ``sparse_pair_counts`` (no image twice in a track); tuples int32
+    [T,V] of IMAGE INDICES, distinct within a tuple, 3 <= V <= 32; K fp32 [T,V,3,3] the tuples' own intrinsics; R fp32 [N,3,3], t
+    fp32 [N,3] (or [N,3,1]) of all images; sizes fp64 [T,V,2] = (width, height), all on the GPU ->
+    (min_d fp64 [T,V], max_d fp64 [T,V], min_row int64 [T,V], max_row int64 [T,V], n_pts int32 [T]) on the GPU.
+    A point takes part in a tuple when at least 3 of its images observe it (``n_pts``); per view the smallest and largest depth
+    among the points that project inside the image with a positive depth, and the lowest row of ``xyz`` that attains each; NaN
+    and -1 for a view without such a point.  One pscv_tuple_visible_depths call per 65535 tuples on the current stream;
+    bit-reproducible.  The index checks read a few flags back to the host, and the call itself reads the tuples back once."""
+    what = "pscv.tuple_visible_depths"
+    t, npts, n = _sparse_inputs(what, xyz, R, t, track_off=(track_off, torch.int64), track_img=(track_img, torch.int32))
+    _dev(tuples, K, sizes)
+    if tuples.dtype != torch.int32 or tuples.dim() != 2 or tuples.shape[0] < 1:
+        raise ValueError(f"{what}: tuples int32 [T,V] with T >= 1 expected, got {tuples.dtype} {tuple(tuples.shape)}")
+    T, V = int(tuples.shape[0]), int(tuples.shape[1])
+    if not 3 <= V <= 32:
+        raise ValueError(f"{what}: V={V} outside [3,32]")
+    if K.dtype != torch.float32 or tuple(K.shape) != (T, V, 3, 3):
+        raise ValueError(f"{what}: K fp32 [{T},{V},3,3] expected, got {K.dtype} {tuple(K.shape)}")
+    if sizes.dtype != torch.float64 or tuple(sizes.shape) != (T, V, 2):
+        raise ValueError(f"{what}: sizes fp64 [{T},{V},2] expected, got {sizes.dtype} {tuple(sizes.shape)}")
+    if any(x.device != xyz.device for x in (tuples, K, sizes)):
+        raise ValueError(f"{what}: all tensors must be on the same device")
+    if n > 46340:
+        raise ValueError(f"{what}: {n} images, more than 46340")
+    nnz = int(track_img.numel())
+    if track_off.numel() != npts + 1:
+        raise ValueError(f"{what}: track_off must have P + 1 = {npts + 1} entries, got {track_off.numel()}")
+    _in_range(what, "track_img", track_img, n)
+    _in_range(what, "tuples", tuples, n)
+    if bool((track_off[1:] < track_off[:-1]).any()) or int(track_off[0]) != 0 or int(track_off[-1]) != nnz:
+        raise ValueError(f"{what}: track_off must rise from 0 to nnz = {nnz}")
+    ordered = torch.sort(tuples, dim=1).values
+    if bool((ordered[:, 1:] == ordered[:, :-1]).any()):
+        raise ValueError(f"{what}: a tuple names an image twice")
+    dev = xyz.device
+    min_d = torch.empty((T, V), dtype=torch.float64, device=dev)
+    max_d = torch.empty_like(min_d)
+    min_row = torch.empty((T, V), dtype=torch.int64, device=dev)
+    max_row = torch.empty_like(min_row)
+    n_pts = torch.empty(T, dtype=torch.int32, device=dev)
+    for k0 in range(0, T, TVD_MAX_TUPLES):
+        k1 = min(T, k0 + TVD_MAX_TUPLES)
+        ws = torch.zeros(max(int(L.lib().pscv_tuple_visible_depths_workspace(k1 - k0, V)), 1), dtype=torch.uint8, device=dev)
+        rc = _launch("tuple_visible_depths", lambda: L.lib().pscv_tuple_visible_depths(
+            _p(xyz), _p(track_off), _p(track_img), npts, nnz, _p(tuples[k0:k1]), _p(K[k0:k1]), _p(R), _p(t), _p(sizes[k0:k1]), n,
+            k1 - k0, V, _p(min_d[k0:k1]), _p(max_d[k0:k1]), _p(min_row[k0:k1]), _p(max_row[k0:k1]), _p(n_pts[k0:k1]), _p(ws),
+            _stream()),
+            # per (tuple, observation) one LDS mask read, twice (the two passes)
+            cost=lambda: (float(2 * (k1 - k0) * (nnz * 4 + npts * 16)), 0.0))
+        L.check(rc, "pscv_tuple_visible_depths")
+    return min_d, max_d, min_row, max_row, n_pts
+
+
 # --------------------------------------------------------------------------------------------
 # PatchMatch multi-view stereo (the COLMAP baseline: utils/colmap_utils.py:depthmap_colmap)
 # --------------------------------------------------------------------------------------------

@@ -2,6 +2,9 @@
 (``data/yfcc_scene.py:init_calibs``): calibration arrays, each image's source views and its depth range.  INTEGRATION.md
 section 2i.
 
+``compute_min_max_depth_visible`` is the depth range of an image tuple that the MegaDepth tuple mining needs (``preprocess.py``;
+INTEGRATION.md section 2j), with a batched form over many tuples: ``ops.tuple_visible_depths``.
+
 ``compute_Kmatrix_colmap`` and ``get_calib_from_sparse`` are host code.  ``compute_src_imgs`` and ``compute_min_max_depth_yao``
 flatten the model into index arrays on the host (once, O(observations)), upload them and run on the GPU:
 ``ops.sparse_pair_counts`` / ``ops.sparse_depth_ranges`` (csrc/scene_setup.hip).  There is no CPU path: without a HIP device the
@@ -141,3 +144,84 @@ def compute_min_max_depth_yao(points3d, imgs, K, R, t, perc=(1, 99)):
     lo, hi = ops.sparse_depth_ranges(torch.from_numpy(xyz).to(dev), torch.from_numpy(obs_img).to(dev), torch.from_numpy(obs_pt).to(dev),
                                      Rd, td, perc)
     return lo.cpu().numpy(), hi.cpu().numpy(), None, None
+
+
+def flatten_tracks_strict(images, points3d):
+    """``flatten_tracks`` under the precondition of the tuple mining, checked: no track holds an image twice and no image's
+    ``point3D_ids`` hold a point twice (COLMAP guarantees both); ValueError otherwise.  Only then is the count of shared points a
+    set count, as the engine's ``adj``, and a multiset count, as the reference's script, at once."""
+    xyz, off, img = flatten_tracks(images, points3d)
+    lens = np.array([len(p.image_ids) for p in points3d.values()], dtype=np.int64)
+    if not np.array_equal(np.diff(off), lens):
+        bad = list(points3d)[int(np.nonzero(np.diff(off) != lens)[0][0])]
+        raise ValueError(f"colmap_utils: the track of point {bad} holds an image more than once")
+    for im_id, im in images.items():
+        ids = np.asarray(im.point3D_ids, dtype=np.int64)
+        ids = ids[ids != -1]
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError(f"colmap_utils: image {im_id} observes a 3-D point more than once")
+    return xyz, off, img
+
+
+def tuple_visible_depths(flat, tuples, K, R, t, sizes):
+    """The batched form of ``compute_min_max_depth_visible``: ``flat`` = (xyz, track_off, track_img) of ``flatten_tracks`` as numpy
+    arrays or device tensors; tuples [T,V] image indices; K [T,V,3,3]; R [N,3,3], t [N,3(,1)] of all images; sizes [T,V,2] = (w, h)
+    -> numpy (min_d fp64 [T,V], max_d fp64 [T,V], min_row int64 [T,V], max_row int64 [T,V], n_pts int32 [T]).  A tuple has a range
+    when ``n_pts > 0`` and no ``min_row`` is -1."""
+    dev = _device()
+    put = lambda x, dt: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt).contiguous()
+    xyz, off, img = put(flat[0], torch.float64), put(flat[1], torch.int64), put(flat[2], torch.int32)
+    tuples = np.asarray(tuples)
+    if tuples.ndim != 2:
+        raise ValueError(f"colmap_utils: tuples [T,V] expected, got {tuples.shape}")
+    T, V = tuples.shape
+    Rd, td = _pose(R, t, len(np.asarray(R.cpu() if hasattr(R, "cpu") else R).reshape(-1, 3, 3)), dev)
+    out = ops.tuple_visible_depths(xyz, off, img, put(tuples, torch.int32), put(np.asarray(K).reshape(T, V, 3, 3), torch.float32), Rd, td,
+                                   put(np.asarray(sizes).reshape(T, V, 2), torch.float64))
+    return tuple(o.cpu().numpy() for o in out)
+
+
+def compute_min_max_depth_visible(points3d, imgs, K, R, t, sizes, *, images=None):
+    """(min_d fp64 [V], max_d fp64 [V], min_point fp64 [V,3], max_point fp64 [V,3]) of the tuple of images ``imgs`` (COLMAP image
+    ids; K [V,3,3], R [V,3,3], t [V,3,1], sizes [V,2] = (w, h) are the tuple's rows), as the reference's function of the same name:
+    over the points that at least 3 of the tuple's images observe, per view the smallest and largest depth among those that
+    project inside the image with a positive depth, and the points that attain them.  (None, None, None, None) when a view has no
+    such point or no point has 3 observations.  (The reference returns the four None in the first case; in the second it fails
+    with a ValueError of its reshape, outside its ``try``: that is answered with the four None as well.)
+
+    ``images`` is not in the reference's signature: the model's image dict.  With it, ``imgs`` must be keys of it and the tracks
+    are flattened over its key order, as everywhere in this module; without it, the tuple's ids alone are indexed and other ids
+    in the tracks are ignored.  The result is the same; ``images`` checks the ids against the model."""
+    imgs = [int(i) for i in imgs]
+    V = len(imgs)
+    if images is not None:
+        keys = list(images.keys())
+        missing = [i for i in imgs if i not in images]
+        if missing:
+            raise KeyError(f"image id {missing[0]} is not in the model")
+    else:
+        keys = imgs
+    if len(set(imgs)) != V:
+        raise ValueError("compute_min_max_depth_visible: an image id occurs twice in the tuple")
+    sorted_keys, order = _index(keys)
+    pts = list(points3d.values())
+    xyz = np.array([p.xyz for p in pts], dtype=np.float64).reshape(-1, 3)
+    lens = np.array([len(p.image_ids) for p in pts], dtype=np.int64)
+    ids = np.concatenate([np.asarray(p.image_ids, dtype=np.int64) for p in pts]) if len(pts) else np.zeros(0, np.int64)
+    pos = np.minimum(np.searchsorted(sorted_keys, ids), len(sorted_keys) - 1)
+    known = sorted_keys[pos] == ids                                       # (ids outside ``keys``: no image of the tuple)
+    n = len(keys)
+    pair = np.unique(np.repeat(np.arange(len(pts), dtype=np.int64), lens)[known] * n + order[pos[known]])
+    off = np.zeros(len(pts) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pair // n, minlength=len(pts)), out=off[1:])
+    idx = _lookup(np.array(imgs, dtype=np.int64), sorted_keys, order, "image id")
+    as_np = lambda x: np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+    R_all = np.tile(np.eye(3, dtype=np.float32), (n, 1, 1))
+    t_all = np.zeros((n, 3), dtype=np.float32)
+    R_all[idx] = as_np(R).reshape(V, 3, 3)
+    t_all[idx] = as_np(t).reshape(V, 3)
+    min_d, max_d, min_row, max_row, n_pts = tuple_visible_depths((xyz, off, (pair % n).astype(np.int32)), idx[None], as_np(K).reshape(1, V, 3, 3),
+                                                                 R_all, t_all, as_np(sizes).reshape(1, V, 2))
+    if n_pts[0] == 0 or (min_row[0] < 0).any():
+        return None, None, None, None
+    return min_d[0], max_d[0], xyz[min_row[0]], xyz[max_row[0]]
