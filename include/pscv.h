@@ -920,6 +920,38 @@ int pscv_ssim(const float* img1, const float* img2, float* out, int n1, int rep,
 int pscv_ssim_bwd(const float* img1, const float* img2, const float* grad_out, float* workspace, float* grad_img2, int n1, int rep,
                   int C, int h, int w, void* stream);
 
+/*
+ * Image preparation (an addition to ABI 14: new exports only, no existing signature changes): what the reference does with PIL
+ * before an image reaches a network -- preprocess.py:157-164 and data/MVSDataset.py:read_img, `Image.resize(size, resample=
+ * Image.LANCZOS)` on 8-bit images, and the nearest-neighbour resize of the ground-truth depth of data/md_yao.py:99-102,123
+ * (csrc/image_resample.hip).  Asynchronous on `stream`, no workspace, integer arithmetic: the bytes are
+ * PIL's.
+ *
+ * pscv_resample_u8_pass: ONE separable pass of PIL's resampling over an interleaved 8-bit image.  A resize is the horizontal pass
+ * into an 8-bit intermediate, then the vertical pass; a pass whose length does not change is left out, as PIL does.
+ *   axis 0 (horizontal): src = `lines` rows of in_len pixels;  dst [lines][out_count][C];  dst_f32 [C][lines][out_count]
+ *   axis 1 (vertical):   src = in_len rows of `lines` pixels;  dst [out_count][lines][C];  dst_f32 [C][out_count][lines]
+ *   src_pitch   bytes between two source rows (>= the row's pixels * C: a column window of a wider image is a pointer and a pitch)
+ *   C           1 or 3 interleaved channels
+ *   coeff       device int32: the weights of every output sample in 22-bit fixed point, zero past the sample's n;
+ *               axis 0: TRANSPOSED, [ksize][out_len];  axis 1: [out_len][ksize]
+ *   bounds      device int32 [out_len][2] = (first, n): the sample reads source indices first .. first + n - 1, n <= ksize
+ *   out_first, out_count   the output samples to produce, [out_first, out_first + out_count) of out_len: a crop computes its window
+ *   per sample and channel: acc = 2^21 + sum_k coeff[k] * src[first + k] (int32), out = clamp(acc >> 22, 0, 255)
+ *   dst_f32     optional planar fp32 copy of the output, value lut[v];  lut device fp32 [256], the caller's float(v) / 255.0f
+ *   coeff == NULL with axis 1 and out_len == in_len: the identity pass, output row o = source row out_first + o (the crop and the
+ *               fp32 copy of an image that is not resampled)
+ *
+ * pscv_depth_nearest_crop: depth fp32 [th][tw] resized to oh x ow by F.interpolate(mode="nearest")'s rule on CPU torch -- per axis
+ * src = min((int)floorf(dst * scale), in - 1) with scale = (float)in / (float)out -- of which the window of ch rows from y0 and cw
+ * columns from x0 is written: out_depth fp32 [ch][cw], out_mask uint8 [ch][cw] = (d >= min_d) && (d < max_d).
+ */
+int pscv_resample_u8_pass(const unsigned char* src, long src_pitch, int lines, int in_len, int C, int axis, const int* coeff,
+                          const int* bounds, int ksize, int out_len, int out_first, int out_count, unsigned char* dst, float* dst_f32,
+                          const float* lut, void* stream);
+int pscv_depth_nearest_crop(const float* depth, int th, int tw, int oh, int ow, int y0, int x0, int ch, int cw, float min_d,
+                            float max_d, float* out_depth, unsigned char* out_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

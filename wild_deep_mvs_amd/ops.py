@@ -8,7 +8,9 @@ Layouts: feature maps ``[B,h,w,C]`` and volumes ``[B,D,h,w,C]`` (channels-last),
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import functools
 import math
 import weakref
 from dataclasses import dataclass
@@ -970,6 +972,159 @@ def tuple_visible_depths(xyz: torch.Tensor, track_off: torch.Tensor, track_img: 
             cost=lambda: (float(2 * (k1 - k0) * (nnz * 4 + npts * 16)), 0.0))
         L.check(rc, "pscv_tuple_visible_depths")
     return min_d, max_d, min_row, max_row, n_pts
+
+
+# --------------------------------------------------------------------------------------------
+# image preparation (preprocess.py:157-164, data/MVSDataset.py:read_img, data/md_yao.py:99-102: PIL's Lanczos resize, nearest depth)
+# --------------------------------------------------------------------------------------------
+LANCZOS_PRECISION_BITS = 32 - 8 - 2      # PIL's fixed point for 8-bit images
+
+
+@functools.lru_cache(maxsize=256)
+def lanczos_tables(in_len: int, out_len: int):
+    """PIL's resampling tables of one axis for ``Image.LANCZOS`` on 8-bit images -> (coeff int32
+    [out_len, ksize], bounds int32 [out_len, 2] = (first, n), ksize): output sample o reads source samples first .. first + n - 1
+    with the 22-bit fixed-point weights coeff[o, :n] (zero past n).  Host code in float64, PIL's operations in PIL's order, whole
+    tables at a time except the sines: those are ``math.sin`` (libm, as PIL; numpy's vectorised sine may differ in the last bit).
+    Cached per (in_len, out_len); the arrays are read-only."""
+    in_len, out_len = int(in_len), int(out_len)
+    if in_len < 1 or out_len < 1:
+        raise ValueError(f"pscv.lanczos_tables: lengths {in_len} -> {out_len} must be >= 1")
+    scale = in_len / out_len
+    fs = max(scale, 1.0)
+    support = 3.0 * fs
+    ksize = 2 * int(math.ceil(support)) + 1
+    inv_fs = 1.0 / fs                                     # PIL multiplies by the reciprocal
+    center = (np.arange(out_len) + 0.5) * scale
+    first = np.maximum((center - support + 0.5).astype(np.int64), 0)              # (a C cast: truncation)
+    n = np.minimum((center + support + 0.5).astype(np.int64), in_len) - first
+    k = np.arange(ksize, dtype=np.int64)
+    x = ((k[None, :] + first[:, None]) - center[:, None] + 0.5) * inv_fs
+    live = (k[None, :] < n[:, None]) & (x >= -3.0) & (x < 3.0) & (x != 0.0)      # L(x) = sinc(x) sinc(x / 3) there, 1 at 0, else 0
+    a, b = x[live] * math.pi, x[live] / 3 * math.pi
+    w = np.where((k[None, :] < n[:, None]) & (x == 0.0), 1.0, 0.0)
+    w[live] = (np.array([math.sin(v) for v in a.tolist()]) / a) * (np.array([math.sin(v) for v in b.tolist()]) / b)
+    total = np.zeros(out_len)
+    for j in range(ksize):                                # in index order, as PIL sums (the zeros past n change nothing)
+        total += w[:, j]
+    w = np.where(total[:, None] != 0.0, w / np.where(total != 0.0, total, 1.0)[:, None], w)
+    one = float(1 << LANCZOS_PRECISION_BITS)
+    coeff = np.where(w < 0, np.trunc(-0.5 + w * one), np.trunc(0.5 + w * one)).astype(np.int32)
+    bounds = np.stack([first, n], axis=1).astype(np.int32)
+    coeff.setflags(write=False)
+    bounds.setflags(write=False)
+    return coeff, bounds, ksize
+
+
+_LANCZOS_DEVICE_TABLES = 64      # device copies kept, least recently used first out
+_lanczos_device = collections.OrderedDict()
+_u8_to_unit = {}
+
+
+def _lanczos_device_tables(in_len, out_len, axis, device):
+    """(coeff, bounds, ksize) on ``device``; the horizontal pass (axis 0) reads its weights transposed, [ksize, out_len]."""
+    key = (in_len, out_len, axis, device)
+    hit = _lanczos_device.get(key)
+    if hit is None:
+        coeff, bounds, ksize = lanczos_tables(in_len, out_len)
+        coeff = np.ascontiguousarray(coeff.T) if axis == 0 else coeff
+        hit = (torch.from_numpy(coeff.copy()).to(device), torch.from_numpy(bounds.copy()).to(device), ksize)
+        _lanczos_device[key] = hit
+        if len(_lanczos_device) > _LANCZOS_DEVICE_TABLES:
+            _lanczos_device.popitem(last=False)
+    else:
+        _lanczos_device.move_to_end(key)
+    return hit
+
+
+def _unit_table(device):
+    """fp32 [256] = numpy's float32(v) / float32(255) on ``device``: the values ``np.array(img, dtype=np.float32) / 255.`` holds."""
+    t = _u8_to_unit.get(device)
+    if t is None:
+        t = _u8_to_unit[device] = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(device)
+    return t
+
+
+def _resample_pass(src, pitch, lines, in_len, C, axis, tables, out_len, out_first, out_count, dst, dst_f32, lut):
+    coeff, bounds, ksize = tables if tables is not None else (None, None, 0)
+    rc = _launch("resample_u8_pass", lambda: L.lib().pscv_resample_u8_pass(
+        src, pitch, lines, in_len, C, axis, _p(coeff), _p(bounds), ksize, out_len, out_first, out_count, _p(dst), _p(dst_f32), _p(lut),
+        _stream()),
+        cost=lambda: (float(out_count * lines * C * (ksize + 1 + (4 if dst_f32 is not None else 0))), 0.0))
+    L.check(rc, "pscv_resample_u8_pass")
+
+
+def resize_lanczos_u8(img: torch.Tensor, size, crop=None, want_f32: bool = False):
+    """``PIL.Image.resize(size, resample=Image.LANCZOS)`` of an 8-bit image on the GPU, byte for byte.
+    img uint8 [H,W,3], [H,W,1] or [H,W] on the GPU, contiguous; ``size`` = (width, height) as PIL takes it; ``crop`` = (x0, y0, w,
+    h) in pixels of the resized image: only that window is computed and returned.  -> uint8 [h,w,C] ([h,w] for a [H,W] input);
+    with ``want_f32`` also fp32 [C,h,w] = float32(v) / float32(255), the network's input layout.
+    At most two pscv_resample_u8_pass launches on the current stream, in PIL's order: the horizontal pass (the window's columns,
+    into an 8-bit intermediate) when the width changes, then the vertical pass (the window's rows) when the height changes; an
+    image whose size does not change takes the identity pass, which crops and converts."""
+    what = "pscv.resize_lanczos_u8"
+    _dev(img)
+    if img.dtype != torch.uint8:
+        raise ValueError(f"{what}: uint8 image expected, got {img.dtype}")
+    if img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] not in (1, 3)) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"{what}: [H,W,3], [H,W,1] or [H,W] expected, got {tuple(img.shape)}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    C = 1 if img.dim() == 2 else int(img.shape[2])
+    w, h = (int(v) for v in size)
+    if w < 1 or h < 1:
+        raise ValueError(f"{what}: size {(w, h)} below 1")
+    x0, y0, cw, ch = (0, 0, w, h) if crop is None else (int(v) for v in crop)
+    if x0 < 0 or y0 < 0 or cw < 1 or ch < 1 or x0 + cw > w or y0 + ch > h:
+        raise ValueError(f"{what}: crop {(x0, y0, cw, ch)} outside the {w} x {h} output")
+    dev = img.device
+    lut = _unit_table(dev) if want_f32 else None
+    out = torch.empty((ch, cw, C), dtype=torch.uint8, device=dev)
+    out_f32 = torch.empty((C, ch, cw), dtype=torch.float32, device=dev) if want_f32 else None
+    tv = _lanczos_device_tables(H, h, 1, dev) if h != H else None
+    src, pitch = img.data_ptr(), W * C
+    if w != W:
+        th = _lanczos_device_tables(W, w, 0, dev)
+        if tv is None:                                     # the rows are kept: the window's rows of the horizontal pass are the result
+            _resample_pass(src + y0 * pitch, pitch, ch, W, C, 0, th, w, x0, cw, out, out_f32, lut)
+            return _resize_result(img, out, out_f32, want_f32)
+        # every source row, the window's columns (which rows the window needs is the vertical table's business)
+        tmp = torch.empty((H, cw, C), dtype=torch.uint8, device=dev)
+        _resample_pass(src, pitch, H, W, C, 0, th, w, x0, cw, tmp, None, None)
+        src, pitch = tmp.data_ptr(), cw * C
+    else:
+        src += x0 * C                                      # a column window of the source: a pointer and the source's pitch
+    # (tmp is freed when this returns; the caching allocator reuses it in stream order, behind the launch below)
+    _resample_pass(src, pitch, cw, H, C, 1, tv, h, y0, ch, out, out_f32, lut)
+    return _resize_result(img, out, out_f32, want_f32)
+
+
+def _resize_result(img, out, out_f32, want_f32):
+    out = out[:, :, 0] if img.dim() == 2 else out
+    return (out, out_f32) if want_f32 else out
+
+
+def depth_nearest_crop(depth: torch.Tensor, size, crop=None, min_d: float = 0.0, max_d: float = float("inf")):
+    """The ground-truth depth of a training view (data/md_yao.py:99-102,123): depth fp32 [th,tw] on the GPU resized to ``size`` =
+    (height, width) by ``F.interpolate(mode="nearest")``'s index rule on CPU torch, of which the window ``crop`` = (y0, x0, h, w)
+    is kept -> (depth fp32 [h,w], mask uint8 [h,w] = (depth >= min_d) & (depth < max_d), the bounds rounded to fp32 as torch
+    compares an fp32 tensor with a number).  One pscv_depth_nearest_crop launch on the current stream."""
+    what = "pscv.depth_nearest_crop"
+    _dev(depth)
+    if depth.dtype != torch.float32 or depth.dim() != 2 or depth.shape[0] < 1 or depth.shape[1] < 1:
+        raise ValueError(f"{what}: depth fp32 [th,tw] expected, got {depth.dtype} {tuple(depth.shape)}")
+    oh, ow = (int(v) for v in size)
+    if oh < 1 or ow < 1:
+        raise ValueError(f"{what}: size {(oh, ow)} below 1")
+    y0, x0, ch, cw = (0, 0, oh, ow) if crop is None else (int(v) for v in crop)
+    if y0 < 0 or x0 < 0 or ch < 1 or cw < 1 or y0 + ch > oh or x0 + cw > ow:
+        raise ValueError(f"{what}: crop {(y0, x0, ch, cw)} outside the {oh} x {ow} map")
+    out = torch.empty((ch, cw), dtype=torch.float32, device=depth.device)
+    mask = torch.empty((ch, cw), dtype=torch.uint8, device=depth.device)
+    rc = _launch("depth_nearest_crop", lambda: L.lib().pscv_depth_nearest_crop(
+        _p(depth), int(depth.shape[0]), int(depth.shape[1]), oh, ow, y0, x0, ch, cw, float(min_d), float(max_d), _p(out), _p(mask),
+        _stream()))
+    L.check(rc, "pscv_depth_nearest_crop")
+    return out, mask
 
 
 # --------------------------------------------------------------------------------------------

@@ -16,9 +16,12 @@ The script's control flow is kept as it stands, quirks included:
     in: with the same seed the tuples are the script's.
 Precondition (checked, ValueError): no track holds an image twice and no image observes a point twice.
 
-Out of scope: reading and resampling the images (PIL, Lanczos) and copying the ``.h5`` depth files.  ``usable``, ``has_depth`` and
-``image_sizes`` stand for what the script learns from the files.  There is no CPU path: without a HIP device ``mine_tuples``
-raises, like the functions of ``utils/colmap_utils.py``."""
+The images of a tuple are resampled on the GPU too: ``resize_tuple_images`` is the script's ``getResizedSize`` +
+``Image.resize(size, resample=Image.LANCZOS)``, byte for byte (``ops.resize_lanczos_u8``).
+
+Out of scope: decoding and encoding the JPEG files and copying the ``.h5`` depth files.  ``usable``, ``has_depth`` and
+``image_sizes`` stand for what the script learns from the files.  There is no CPU path: without a HIP device ``mine_tuples`` and
+``resize_tuple_images`` raise, like the functions of ``utils/colmap_utils.py``."""
 from __future__ import annotations
 
 import os
@@ -38,6 +41,15 @@ def getResizedSize(size, minSize):
     w, h = size
     ratio = min(w / minSize, h / minSize)
     return int(w / ratio / 32) * 32, int(h / ratio / 32) * 32
+
+
+def resize_tuple_images(images_u8, minSize=512):
+    """The images of one tuple as the script saves them (``preprocess.py:157-163``): every decoded image (uint8 [H,W,3] on the GPU,
+    sizes may differ) resized to ``getResizedSize((W, H), minSize)`` with PIL's Lanczos filter -> (the resized uint8 [h,w,3] GPU
+    images, their (width, height) as int64 [V,2]: the ``sizes`` of a mined tuple, what ``mine_tuples`` derives from
+    ``image_sizes``).  One or two launches per image on the current stream."""
+    sizes = [getResizedSize((int(im.shape[1]), int(im.shape[0])), minSize) for im in images_u8]
+    return [ops.resize_lanczos_u8(im, s) for im, s in zip(images_u8, sizes)], np.array(sizes, dtype=np.int64).reshape(-1, 2)
 
 
 def select_tuple_candidates(adj, adj_tri, usable, perm_ref, perms_src, *, nb_src, nb_points_thresh):
