@@ -92,6 +92,50 @@ def test_storage_dtype_dispatch_rejects_fp32_before_any_launch():
     assert rc != 0 and "pscv_leaky_relu_bwd" in msg and "dtype 0" in msg, msg
 
 
+def _conv3d_rc(kind, c_in, c_out, dtype=None, in_cs=None, in_co=0, out_cs=None, out_co=0, dims=(1, 4, 8, 16)):
+    """pscv_conv3d with fake non-null pointers (never dereferenced on the host) -> (rc, error text)."""
+    lib = L.lib()
+    dtype = L.BF16 if dtype is None else dtype
+    in_cs = c_in if in_cs is None else in_cs
+    out_cs = c_out if out_cs is None else out_cs
+    rc = lib.pscv_conv3d(64, dtype, in_cs, in_co, 64, None, None, None, None, 0, 0, 128, out_cs, out_co, dtype, *dims, c_in, c_out, kind, 0, None)
+    return rc, lib.pscv_last_error().decode()
+
+
+@pytest.mark.parametrize("kwargs, reasons", [
+    (dict(kind=L.CONV_S1, c_in=8, c_out=8, in_cs=12), ("input channel slice [0,8) of stride 12", "8-aligned")),
+    (dict(kind=L.CONV_S1, c_in=8, c_out=8, in_cs=16, in_co=4), ("input channel slice [4,12) of stride 16", "8-aligned")),
+    (dict(kind=L.CONV_S1, c_in=8, c_out=8, out_cs=8, out_co=4), ("output channel slice exceeds stride",)),
+    (dict(kind=L.CONV_S1, c_in=8, c_out=8, dtype=L.F32), ("storage dtype 0", "bf16 or fp16")),
+    (dict(kind=L.CONV_S1P8, c_in=64, c_out=8), ("the sweep kernels (S1P8) are for", "got 64 -> 8")),
+    (dict(kind=L.CONV_S1P8, c_in=8, c_out=8, dims=(1, 4, 32768, 32768)), ("pscv_conv3d(sweep)", "exceeds 2 GiB")),     # the narrow sweep
+    (dict(kind=L.CONV_S1P8, c_in=32, c_out=8, dims=(1, 4, 32768, 32768)), ("pscv_conv3d(sweep)", "exceeds 2 GiB")),    # conv0's sweep
+    (dict(kind=L.CONV_T2P8, c_in=8, c_out=8), ("the parity-pair kernel (T2P8) is for c_in=16, c_out=8", "got 8 -> 8")),
+    (dict(kind=L.CONV_S1C1, c_in=8, c_out=2), ("the 1-channel kernel (S1C1) is for", "got 8 -> 2")),
+])
+def test_conv3d_rejects_before_any_launch(kwargs, reasons):
+    """The argument checks of pscv_conv3d and of the launchers behind it name the entry point and the reason, and come before any HIP call."""
+    rc, msg = _conv3d_rc(**kwargs)
+    assert rc == -1 and "pscv_conv3d" in msg and all(r in msg for r in reasons), (rc, msg)
+
+
+def test_conv3d_cat2_and_fused_head_reject_before_any_launch():
+    lib = L.lib()
+
+    def cat2(c_out, b_cs=8, b_co=0):
+        rc = lib.pscv_conv3d_cat2(64, 8, 0, 128, b_cs, b_co, L.BF16, 64, None, None, None, None, 0, 0, 256, c_out, 0, L.BF16, 1, 4, 8, 16, c_out, 0, None)
+        return rc, lib.pscv_last_error().decode()
+
+    rc, msg = cat2(32)
+    assert rc == -1 and "pscv_conv3d_cat2: c_out=32 must be 8 or 16" in msg, (rc, msg)
+    for b_cs, b_co in ((12, 0), (16, 4), (8, 8)):
+        rc, msg = cat2(8, b_cs, b_co)
+        assert rc == -1 and "pscv_conv3d_cat2: both inputs contribute an 8-aligned slice of 8 channels" in msg, (rc, msg)
+    rc = lib.pscv_prob_softargmin(64, L.BF16, 8, 0, 64, None, None, None, 8, 0, 64, 48, 64, None, 0, 64, 64, 1, 48, 8, 16, None)
+    msg = lib.pscv_last_error().decode()
+    assert rc == -1 and "pscv_prob_softargmin: null pointer argument" in msg, (rc, msg)
+
+
 # ---- conv3d weight packing vs a numpy emulation of the kernel ------------------------------------
 def _bf16(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(torch.bfloat16).to(torch.float32).numpy()

@@ -16,24 +16,15 @@
 // Replaces (fdarmon/wild_deep_mvs): models/MVSNet/module.py:41-58 ConvBnReLU3D/ConvBn3D, the
 // Sequential(ConvTranspose3d, BatchNorm3d, ReLU) blocks and `prob` of models/MVSNet/model.py:43-84,
 // models/CVP_MVSNet/models/net.py:50-85 and the 3-D members of models/VisMVSNet/nn_utils.py:194-278.
-#include "pscv_common.h"
+#include "conv_common.h"
 #include <type_traits>
 
 namespace pscv {
 
 PSCV_PROF_BUFFER(conv)
 
-struct ConvArgs {
-    const uint16_t* in;
-    const uint16_t* wpk;
-    const float* scale;
-    const float* bias;
-    const float* floor;
-    const uint16_t* skip;
-    void* out;
-    int in_cs, in_co, skip_cs, skip_co, out_cs, out_co;
-    int out_f32;
-    int B, Di, Hi, Wi, Do, Ho, Wo;
+struct ConvArgs : ConvIO {
+    int Di, Hi, Wi, Do, Ho, Wo;
     int cout, epi;
     int ntd, nth, ntw;   // tile counts along d, h, w
     unsigned mg_td, mg_th, mg_tw;   // fast_div_magic of the tile counts
@@ -549,9 +540,8 @@ static int launch_conv(ConvArgs& a, int n_split, hipStream_t st) {
     const int rd = KIND == PSCV_CONV_T2 ? a.Di : a.Do, rh = KIND == PSCV_CONV_T2 ? a.Hi : a.Ho,
               rw = KIND == PSCV_CONV_T2 ? a.Wi : a.Wo;
     a.ntd = ceil_div(rd, TD); a.nth = ceil_div(rh, TH); a.ntw = ceil_div(rw, 16);
-    a.mg_td = fast_div_magic(a.ntd); a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw);
-    const long nblk = (long)a.B * a.ntd * a.nth * a.ntw;
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d: bad grid %ld", nblk); return -1; }
+    const long nblk = finish_grid("pscv_conv3d", a.B, a.ntd, a.nth, a.ntw, a.mg_td, a.mg_th, a.mg_tw);
+    if (nblk < 0) return -1;
     return launch("pscv_conv3d", conv3d_kernel<H, CIN, NT, KIND, TD, TH>, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
 }
 
@@ -620,36 +610,6 @@ static int launch_channels(ConvArgs& a, int c_in, int c_out, int kind, hipStream
 
 PSCV_PROF_EXPORT(conv)
 
-int pscv_conv3d_sweep8_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                              const float* scale, const float* bias, const float* floor, const void* skip,
-                              int skip_cstride, int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype,
-                              int B, int D, int Hh, int W, int epi_flags, hipStream_t st);
-
-int pscv_conv3d_sweepc_launch(const void* in, int dtype, int c_in, int c_out, int in_cstride, int in_coff, const uint16_t* packed,
-                              const float* scale, const float* bias, const float* floor, const void* skip, int skip_cstride,
-                              int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype, int B, int D, int Hh, int W,
-                              int epi_flags, hipStream_t st, const void* in2 = nullptr, int in2_cstride = 0, int in2_coff = 0);
-
-int pscv_conv3d_sweep_s2_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed, const float* scale,
-                                const float* bias, const float* floor, const void* skip, int skip_cstride, int skip_coff, void* out,
-                                int out_cstride, int out_coff, int out_dtype, int B, int Di, int Hi, int Wi, int c_in, int c_out,
-                                int epi_flags, hipStream_t st);
-
-int pscv_conv3d_wide_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed, const float* scale,
-                            const float* bias, const float* floor, const void* skip, int skip_cstride, int skip_coff, void* out,
-                            int out_cstride, int out_coff, int out_dtype, int B, int D, int Hh, int W, int c_in, int c_out, int epi_flags,
-                            hipStream_t st);
-
-int pscv_conv3d_c1_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                          const float* scale, const float* bias, const float* floor, const void* skip,
-                          int skip_cstride, int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype,
-                          int B, int D, int Hh, int W, int c_in, int epi_flags, hipStream_t st);
-
-int pscv_conv3d_t2p8_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                            const float* scale, const float* bias, const float* floor, const void* skip, int skip_cstride,
-                            int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype, int B, int Di, int Hi,
-                            int Wi, int epi_flags, hipStream_t st);
-
 extern "C" int pscv_conv3d_cat2(const void* in_a, int a_cstride, int a_coff, const void* in_b, int b_cstride, int b_coff, int dtype,
                                 const uint16_t* packed, const float* scale, const float* bias, const float* floor, const void* skip,
                                 int skip_cstride, int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype, int B, int D,
@@ -664,12 +624,13 @@ extern "C" int pscv_conv3d_cat2(const void* in_a, int a_cstride, int a_coff, con
     PSCV_CHECK_ARG(!skip || (skip_cstride % 4 == 0 && skip_coff % 4 == 0), "pscv_conv3d_cat2: skip slice must be 4-aligned");
     PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_conv3d_cat2: storage dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(out_dtype == dtype || out_dtype == PSCV_F32, "pscv_conv3d_cat2: out dtype %d must be the storage dtype or fp32", out_dtype);
-    const int rc = pscv_conv3d_sweepc_launch(in_a, dtype, 16, c_out, a_cstride, a_coff, packed, scale, bias, floor, skip, skip_cstride, skip_coff,
-                                             out, out_cstride, out_coff, out_dtype, B, D, H, W, epi_flags, reinterpret_cast<hipStream_t>(stream),
-                                             in_b, b_cstride, b_coff);
-    if (rc) return rc;
-    PSCV_CHECK_LAUNCH("pscv_conv3d_cat2");
-    return 0;
+    ConvCall c{};
+    c.io = {reinterpret_cast<const uint16_t*>(in_a), packed, scale, bias, floor, reinterpret_cast<const uint16_t*>(skip), out,
+            a_cstride, a_coff, skip_cstride, skip_coff, out_cstride, out_coff, out_dtype == PSCV_F32, B};
+    c.dtype = dtype; c.D = D; c.H = H; c.W = W; c.c_in = 16; c.c_out = c_out; c.epi = epi_flags;
+    c.st = reinterpret_cast<hipStream_t>(stream);
+    c.in2 = reinterpret_cast<const uint16_t*>(in_b); c.in2_cs = b_cstride; c.in2_co = b_coff;
+    return conv3d_sweepc_launch(c);
 }
 
 extern "C" int pscv_conv3d(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed, const float* scale,
@@ -686,63 +647,39 @@ extern "C" int pscv_conv3d(const void* in, int dtype, int in_cstride, int in_cof
     PSCV_CHECK_ARG(!skip || c_out < 4 || (skip_cstride % 4 == 0 && skip_coff % 4 == 0), "pscv_conv3d: skip slice must be 4-aligned");
     PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_conv3d: storage dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(out_dtype == dtype || out_dtype == PSCV_F32, "pscv_conv3d: out dtype %d must be the storage dtype or fp32", out_dtype);
+    ConvCall c{};
+    c.io = {reinterpret_cast<const uint16_t*>(in), packed, scale, bias, floor, reinterpret_cast<const uint16_t*>(skip), out,
+            in_cstride, in_coff, skip_cstride, skip_coff, out_cstride, out_coff, out_dtype == PSCV_F32, B};
+    c.dtype = dtype; c.D = Di; c.H = Hi; c.W = Wi; c.c_in = c_in; c.c_out = c_out; c.epi = epi_flags;
+    c.st = reinterpret_cast<hipStream_t>(stream);
     if (kind == PSCV_CONV_S1P8) {
         PSCV_CHECK_ARG(((c_in == 8 || c_in == 16 || c_in == 32) && c_out == 8) || (c_in == 16 && c_out == 16),
                        "pscv_conv3d: the sweep kernels (S1P8) are for 8|16|32 -> 8 and 16 -> 16 (got %d -> %d)", c_in, c_out);
-        const int rc = c_in == 32
-            ? pscv_conv3d_sweep8_launch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride, skip_coff, out,
-                                        out_cstride, out_coff, out_dtype, B, Di, Hi, Wi, epi_flags, reinterpret_cast<hipStream_t>(stream))
-            : pscv_conv3d_sweepc_launch(in, dtype, c_in, c_out, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride, skip_coff,
-                                        out, out_cstride, out_coff, out_dtype, B, Di, Hi, Wi, epi_flags,
-                                        reinterpret_cast<hipStream_t>(stream));
-        if (rc) return rc;
-        PSCV_CHECK_LAUNCH("pscv_conv3d(sweep)");
-        return 0;
+        return c_in == 32 ? conv3d_sweep8_launch(c) : conv3d_sweepc_launch(c);
     }
     if (kind == PSCV_CONV_T2P8) {
         PSCV_CHECK_ARG(c_in == 16 && c_out == 8, "pscv_conv3d: the parity-pair kernel (T2P8) is for c_in=16, c_out=8 (got %d -> %d)", c_in, c_out);
-        const int rc = pscv_conv3d_t2p8_launch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride,
-                                               skip_coff, out, out_cstride, out_coff, out_dtype, B, Di, Hi, Wi, epi_flags,
-                                               reinterpret_cast<hipStream_t>(stream));
-        if (rc) return rc;
-        PSCV_CHECK_LAUNCH("pscv_conv3d(t2p8)");
-        return 0;
+        return conv3d_t2p8_launch(c);
     }
     if (kind == PSCV_CONV_S1C1) {
         PSCV_CHECK_ARG(c_out == 1 && (c_in == 8 || c_in == 16), "pscv_conv3d: the 1-channel kernel (S1C1) is for c_in 8/16 -> 1 (got %d -> %d)", c_in, c_out);
-        const int rc = pscv_conv3d_c1_launch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride,
-                                             skip_coff, out, out_cstride, out_coff, out_dtype, B, Di, Hi, Wi, c_in, epi_flags,
-                                             reinterpret_cast<hipStream_t>(stream));
-        if (rc) return rc;
-        PSCV_CHECK_LAUNCH("pscv_conv3d(c1)");
-        return 0;
+        return conv3d_c1_launch(c);
     }
+    // the two kernels that take a layer only at some sizes: 1 = not theirs, the brick kernel below runs it
     if (kind == PSCV_CONV_S2) {      // 8-channel inputs on large volumes: the stride-2 depth sweep (conv3d_sweep_s2.hip), same packing
-        const int rc = pscv_conv3d_sweep_s2_launch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride, skip_coff,
-                                                   out, out_cstride, out_coff, out_dtype, B, Di, Hi, Wi, c_in, c_out, epi_flags,
-                                                   reinterpret_cast<hipStream_t>(stream));
-        if (rc < 0) return rc;
-        if (rc == 0) { PSCV_CHECK_LAUNCH("pscv_conv3d(s2 sweep)"); return 0; }
+        const int rc = conv3d_sweep_s2_launch(c);
+        if (rc != 1) return rc;
     }
     if (kind == PSCV_CONV_S1) {      // wide layers (32 | 64 -> 32 | 64) on large volumes: 8-wave workgroups, weights through LDS (conv3d_wide.hip)
-        const int rc = pscv_conv3d_wide_launch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride, skip_coff, out,
-                                               out_cstride, out_coff, out_dtype, B, Di, Hi, Wi, c_in, c_out, epi_flags,
-                                               reinterpret_cast<hipStream_t>(stream));
-        if (rc < 0) return rc;
-        if (rc == 0) { PSCV_CHECK_LAUNCH("pscv_conv3d(wide)"); return 0; }
+        const int rc = conv3d_wide_launch(c);
+        if (rc != 1) return rc;
     }
     ConvArgs a;
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.wpk = packed; a.scale = scale; a.bias = bias; a.floor = floor;
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff;
-    a.out_cs = out_cstride; a.out_co = out_coff; a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi;
+    static_cast<ConvIO&>(a) = c.io;
+    a.Di = Di; a.Hi = Hi; a.Wi = Wi;
     if (kind == PSCV_CONV_S1) { a.Do = Di; a.Ho = Hi; a.Wo = Wi; }
     else if (kind == PSCV_CONV_S2) { a.Do = (Di + 1) / 2; a.Ho = (Hi + 1) / 2; a.Wo = (Wi + 1) / 2; }
     else { a.Do = 2 * Di; a.Ho = 2 * Hi; a.Wo = 2 * Wi; }
     a.cout = c_out; a.epi = epi_flags;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return with_half("pscv_conv3d", dtype, [&](auto t) { return launch_channels<typename decltype(t)::type>(a, c_in, c_out, kind, st); });
+    return with_half("pscv_conv3d", dtype, [&](auto t) { return launch_channels<typename decltype(t)::type>(a, c_in, c_out, kind, c.st); });
 }

@@ -15,7 +15,7 @@
 //   * zero padding of layer 2 = t is ZERO outside the volume (not act1(bias)): masked when t is written.
 // Bytes per output voxel through the CU path: 16 x 216/112 in + 16 out = 47 (93 before); MFMAs 1.43 + 1.14 row tiles per output
 // row (2 before).  8-byte stores like the narrow sweep.
-#include "pscv_common.h"
+#include "conv_common.h"
 #include <type_traits>
 
 namespace pscv {
@@ -254,20 +254,12 @@ extern "C" int pscv_conv3d_block8(const void* in, int dtype, int in_cstride, int
     a.nth = (H + B8_TH - 1) / B8_TH;
     a.ntw = (W + B8_TW - 1) / B8_TW;
     // one resident round of workgroups (3 per CU); each depth-chunk seam recomputes three x planes and one t plane
-    const long tiles = (long)B * a.nth * a.ntw;
     const int knob = g_block8_slots;
     a.dbg = knob >> 16;
-    const long slots = (knob & 0xffff) > 0 ? (long)(knob & 0xffff) : 768;
-    const long ndc_want = tiles >= slots ? 1 : slots / tiles;
-    int dc = (int)((D + ndc_want - 1) / ndc_want);
-    dc = (dc + 1) & ~1;
-    dc = dc < 8 ? 8 : dc;
-    dc = dc > D ? ((D + 1) & ~1) : dc;
-    a.dc = dc;
-    a.ndc = (D + dc - 1) / dc;
-    const long nblk = tiles * a.ndc;
-    a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d_block8: bad grid %ld", nblk); return -1; }
+    a.dc = plan_depth_chunk(D, (long)B * a.nth * a.ntw, (knob & 0xffff) > 0 ? (long)(knob & 0xffff) : 768, 8, true, 0);
+    a.ndc = (D + a.dc - 1) / a.dc;
+    const long nblk = finish_grid("pscv_conv3d_block8", B, a.nth, a.ntw, a.ndc, a.mg_th, a.mg_tw, a.mg_dc);
+    if (nblk < 0) return -1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return with_half("pscv_conv3d_block8", dtype, [&](auto t) {
         return launch("pscv_conv3d_block8", conv3d_block8_kernel<typename decltype(t)::type>, dim3((unsigned)nblk), dim3(256), B8_LDS, st, a);

@@ -18,10 +18,12 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): CostRegNet.prob models/MVSNet/model.py:72,82; prob0 models/CVP_MVSNet/models/
 // net.py:76,83; RegPair / RegFuse final_conv models/VisMVSNet/model_cas.py:55,68.
-#include "pscv_common.h"
+#include "conv_common.h"
 
 namespace pscv {
 
+// The ConvIO fields in an order of its own, not as a base: the compiler merges the scalar loads of neighbouring kernel arguments, and
+// with the shared order these kernels come out with another scalar register allocation (one of them with one SGPR more).
 struct C1Args {
     const uint16_t* in;
     const uint4* wpk;        // [NSTEPS][64 lanes] x 8 halves (A fragments)
@@ -532,41 +534,37 @@ static int c1_launch(const C1Args& a, long nblk, hipStream_t st) {
     return launch("pscv_conv3d(c1)", conv3d_c1_kernel<H, CIN>, dim3((unsigned)nblk), dim3(256), lds, st, a);
 }
 
-}  // namespace pscv
+void softargmin_merge_launch(const ConvCall& c, const HeadOut& h, int ndc) {
+    const long hw = (long)c.H * c.W, npix = c.io.B * hw;
+    hipLaunchKernelGGL(softargmin_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c.st, h.part, reinterpret_cast<const float*>(c.io.out),
+                       ndc, c.io.B, c.D, hw, h.o_depth, h.o_conf);
+}
 
-PSCV_PROF_EXPORT(c1)
-
-// depth / part / merged outputs non-null: the fused tail (pscv_prob_softargmin); returns 1 when the layer does not get the depth-sweep
-// variant (the caller then runs the two separate entry points), 0 on success, < 0 on error
-static int c1_dispatch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                       const float* scale, const float* bias, const float* floor, const void* skip, int skip_cstride, int skip_coff, void* out,
-                       int out_cstride, int out_coff, int out_dtype, int B, int D, int Hh, int W, int c_in,
-                       int epi_flags, hipStream_t st, const float* depth, long depth_bstride, float* part, long part_floats,
-                       float* o_depth, float* o_conf, float* o_index = nullptr, float* o_entropy = nullptr) {
-    using namespace pscv;
+// h.part non-null: the fused heads (pscv_prob_softargmin; with h.o_index pscv_head_index_entropy); returns 1 when the layer does not get
+// the depth-sweep variant (the caller then runs the two separate entry points), 0 on success, < 0 on error
+static int c1_dispatch(const ConvCall& c, const HeadOut& h) {
+    const ConvIO& io = c.io;
+    const int B = io.B, D = c.D, Hh = c.H, W = c.W;
     C1Args a;
-    a.depth = depth; a.depth_bstride = depth_bstride; a.part = nullptr;
-    a.o_index = o_index; a.o_entropy = o_entropy;
-    const bool ie = o_index != nullptr;       // the Vis pair head: index + entropy (FUSE = 2)
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.wpk = reinterpret_cast<const uint4*>(packed);
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.scale = scale; a.bias = bias; a.floor = floor;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff;
-    a.out_cs = out_cstride; a.out_co = out_coff; a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.D = D; a.Hh = Hh; a.W = W; a.epi = epi_flags;
+    a.in = io.in; a.wpk = reinterpret_cast<const uint4*>(io.wpk); a.skip = io.skip; a.out = io.out;
+    a.scale = io.scale; a.bias = io.bias; a.floor = io.floor;
+    a.in_cs = io.in_cs; a.in_co = io.in_co; a.skip_cs = io.skip_cs; a.skip_co = io.skip_co;
+    a.out_cs = io.out_cs; a.out_co = io.out_co; a.out_f32 = io.out_f32; a.B = B;
+    a.depth = h.depth; a.depth_bstride = h.depth_bstride; a.part = nullptr;
+    a.o_index = h.o_index; a.o_entropy = h.o_entropy;
+    const bool ie = h.o_index != nullptr;       // the Vis pair head: index + entropy (FUSE = 2)
+    a.D = D; a.Hh = Hh; a.W = W; a.epi = c.epi;
     a.nth = (Hh + C1_TH - 1) / C1_TH;
     a.ntw = (W + C1_TW - 1) / C1_TW;
     const long tiles = (long)B * a.nth * a.ntw;
     const int nblocks = (D + C1_P - 1) / C1_P;
     // two 6-plane blocks per workgroup (the 2-plane halo of the brick costs 1/6 instead of 1/3) when that still leaves
     // the chip a few rounds of workgroups; C_in = 16 keeps one (LDS: 53 KB per workgroup instead of 93)
-    a.nb = (c_in == 8 && tiles * ((nblocks + 1) / 2) >= 1024) ? 2 : 1;
+    a.nb = (c.c_in == 8 && tiles * ((nblocks + 1) / 2) >= 1024) ? 2 : 1;
     if (g_c1_nb) a.nb = g_c1_nb;
     // long depth axes with 8 input channels: the depth-sweep variant, chunks sized for about one resident round (3 per CU)
     bool sweep = false;
-    if (c_in == 8 && g_c1_sweep && (long)Hh * W * in_cstride * 2 < 0x7fffffffL) {
+    if (c.c_in == 8 && g_c1_sweep && (long)Hh * W * a.in_cs * 2 < 0x7fffffffL) {
         const long want = tiles >= 768 ? 1 : 768 / tiles;
         const int ndc = (int)(want < nblocks ? want : nblocks);
         int nbk = (nblocks + ndc - 1) / ndc;
@@ -574,56 +572,55 @@ static int c1_dispatch(const void* in, int dtype, int in_cstride, int in_coff, c
         if (nbk >= 3 || g_c1_sweep == 2) { sweep = true; a.nb = nbk; }
     }
     a.ndc = (nblocks + a.nb - 1) / a.nb;
-    const long nblk = tiles * a.ndc;
-    a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(c1): bad grid %ld", nblk); return -1; }
-    if (part) {
-        if (!sweep || skip || out_dtype != PSCV_F32 || out_cstride != 1 || (!ie && a.nb * C1_P > 256)) return 1;
-        if ((long)B * a.ndc * 4 * Hh * W > part_floats) { set_error("pscv_prob_softargmin: workspace of %ld floats is too small", part_floats); return -1; }
-        a.part = part;
+    const long nblk = finish_grid("pscv_conv3d(c1)", B, a.nth, a.ntw, a.ndc, a.mg_th, a.mg_tw, a.mg_dc);
+    if (nblk < 0) return -1;
+    if (h.part) {
+        if (!sweep || a.skip || !a.out_f32 || a.out_cs != 1 || (!ie && a.nb * C1_P > 256)) return 1;
+        if ((long)B * a.ndc * 4 * Hh * W > h.part_floats) { set_error("pscv_prob_softargmin: workspace of %ld floats is too small", h.part_floats); return -1; }
+        a.part = h.part;
     }
     if (sweep) {
         const size_t lds = (size_t)C1S_NSLOT * C1_PS * 16;
         const long npix = (long)B * Hh * W;
-        const int fuse = part ? (ie ? 2 : 1) : 0;     // FUSE of the kernel: 0 logits only, 1 + softmax partials, 2 + index / entropy partials
-        const int rc = with_half("pscv_conv3d(c1)", dtype, [&](auto t) {
+        const int fuse = h.part ? (ie ? 2 : 1) : 0;     // FUSE of the kernel: 0 logits only, 1 + softmax partials, 2 + index / entropy partials
+        const int rc = with_half("pscv_conv3d(c1)", c.dtype, [&](auto t) {
             using H = typename decltype(t)::type;
             const dim3 grid((unsigned)nblk);
-            if (fuse == 2) return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 2>, grid, dim3(256), lds, st, a);
-            if (fuse == 1) return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 1>, grid, dim3(256), lds, st, a);
-            return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 0>, grid, dim3(256), lds, st, a);
+            if (fuse == 2) return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 2>, grid, dim3(256), lds, c.st, a);
+            if (fuse == 1) return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 1>, grid, dim3(256), lds, c.st, a);
+            return launch("pscv_conv3d(c1)", conv3d_c1_sweep_kernel<H, 0>, grid, dim3(256), lds, c.st, a);
         });
         if (rc) return rc;
         if (fuse == 2 && a.ndc > 1)
-            hipLaunchKernelGGL(index_entropy_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, part, a.ndc, B, (long)Hh * W,
-                               o_index, o_entropy);
-        if (fuse == 1)
-            hipLaunchKernelGGL(softargmin_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, part, reinterpret_cast<const float*>(out),
-                               a.ndc, B, D, (long)Hh * W, o_depth, o_conf);
+            hipLaunchKernelGGL(index_entropy_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c.st, h.part, a.ndc, B, (long)Hh * W,
+                               h.o_index, h.o_entropy);
+        if (fuse == 1) softargmin_merge_launch(c, h, a.ndc);
         return 0;
     }
-    return with_half("pscv_conv3d(c1)", dtype, [&](auto t) {
+    return with_half("pscv_conv3d(c1)", c.dtype, [&](auto t) {
         using H = typename decltype(t)::type;
-        if (c_in == 8) return c1_launch<H, 8>(a, nblk, st);
-        if (c_in == 16) return c1_launch<H, 16>(a, nblk, st);
-        set_error("pscv_conv3d(c1): c_in=%d dtype=%d not supported (c_in 8 or 16)", c_in, dtype);
+        if (c.c_in == 8) return c1_launch<H, 8>(a, nblk, c.st);
+        if (c.c_in == 16) return c1_launch<H, 16>(a, nblk, c.st);
+        set_error("pscv_conv3d(c1): c_in=%d dtype=%d not supported (c_in 8 or 16)", c.c_in, c.dtype);
         return -1;
     });
 }
 
-// merge launch for other producers of the same partials (conv3d_tail.hip)
-void pscv_softargmin_merge_launch(const float* part, const float* logits, int ndc, int B, int D, long hw, float* o_depth, float* o_conf, hipStream_t st) {
-    const long npix = (long)B * hw;
-    hipLaunchKernelGGL(pscv::softargmin_merge_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, part, logits, ndc, B, D, hw, o_depth, o_conf);
+// pscv_conv3d, kind S1C1
+int conv3d_c1_launch(const ConvCall& c) { return c1_dispatch(c, HeadOut{}); }
+
+// the call of the two fused heads: fp32 logits [B][D][H][W], no skip tensor
+static ConvCall head_call(const ConvIO& io, int dtype, int D, int H, int W, int c_in, int epi_flags, void* stream) {
+    ConvCall c{};
+    c.io = io;
+    c.dtype = dtype; c.D = D; c.H = H; c.W = W; c.c_in = c_in; c.c_out = 1; c.epi = epi_flags;
+    c.st = reinterpret_cast<hipStream_t>(stream);
+    return c;
 }
 
-int pscv_conv3d_c1_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                          const float* scale, const float* bias, const float* floor, const void* skip, int skip_cstride, int skip_coff, void* out,
-                          int out_cstride, int out_coff, int out_dtype, int B, int D, int Hh, int W, int c_in,
-                          int epi_flags, hipStream_t st) {
-    return c1_dispatch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, skip, skip_cstride, skip_coff, out, out_cstride, out_coff,
-                       out_dtype, B, D, Hh, W, c_in, epi_flags, st, nullptr, 0, nullptr, 0, nullptr, nullptr);
-}
+}  // namespace pscv
+
+PSCV_PROF_EXPORT(c1)
 
 extern "C" long pscv_prob_softargmin_workspace(int B, int D, int H, int W) {
     return (long)B * ((D + pscv::C1_P - 1) / pscv::C1_P) * 4 * H * W;     // floats: one partial set per 6-plane block at most
@@ -638,9 +635,9 @@ extern "C" int pscv_prob_softargmin(const void* in, int dtype, int in_cstride, i
     PSCV_CHECK_ARG(B > 0 && D > 0 && H > 0 && W > 0, "pscv_prob_softargmin: bad sizes");
     PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_prob_softargmin: storage dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(in_cstride % 8 == 0 && in_coff % 8 == 0 && in_coff + c_in <= in_cstride, "pscv_prob_softargmin: input channel slice must be 8-aligned");
-    const int rc = c1_dispatch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, nullptr, 0, 0, logits, 1, 0, PSCV_F32, B, D, H, W, c_in,
-                               epi_flags, reinterpret_cast<hipStream_t>(stream), depth, depth_bstride, workspace, workspace_floats, out_depth,
-                               out_conf);
+    const ConvIO io = {reinterpret_cast<const uint16_t*>(in), packed, scale, bias, floor, nullptr, logits, in_cstride, in_coff, 0, 0, 1, 0, 1, B};
+    const int rc = c1_dispatch(head_call(io, dtype, D, H, W, c_in, epi_flags, stream),
+                               HeadOut{depth, depth_bstride, workspace, workspace_floats, out_depth, out_conf, nullptr, nullptr});
     if (rc < 0) return rc;
     if (rc == 1) { set_error("pscv_prob_softargmin: this layer does not run the depth-sweep head (needs c_in = 8 and a depth axis of >= 3 six-plane blocks per chunk); use pscv_conv3d + pscv_softargmin"); return -3; }
     PSCV_CHECK_LAUNCH("pscv_prob_softargmin");
@@ -655,9 +652,9 @@ extern "C" int pscv_head_index_entropy(const void* in, int dtype, int in_cstride
     PSCV_CHECK_ARG(B > 0 && D > 0 && H > 0 && W > 0, "pscv_head_index_entropy: bad sizes");
     PSCV_CHECK_ARG(dtype == PSCV_BF16 || dtype == PSCV_F16, "pscv_head_index_entropy: storage dtype %d must be bf16 or fp16", dtype);
     PSCV_CHECK_ARG(in_cstride % 8 == 0 && in_coff % 8 == 0 && in_coff + c_in <= in_cstride, "pscv_head_index_entropy: input channel slice must be 8-aligned");
-    const int rc = c1_dispatch(in, dtype, in_cstride, in_coff, packed, scale, bias, floor, nullptr, 0, 0, logits, 1, 0, PSCV_F32, B, D, H, W, c_in,
-                               epi_flags, reinterpret_cast<hipStream_t>(stream), nullptr, 0, workspace, workspace_floats, nullptr, nullptr,
-                               out_index, out_entropy);
+    const ConvIO io = {reinterpret_cast<const uint16_t*>(in), packed, scale, bias, floor, nullptr, logits, in_cstride, in_coff, 0, 0, 1, 0, 1, B};
+    const int rc = c1_dispatch(head_call(io, dtype, D, H, W, c_in, epi_flags, stream),
+                               HeadOut{nullptr, 0, workspace, workspace_floats, nullptr, nullptr, out_index, out_entropy});
     if (rc < 0) return rc;
     if (rc == 1) { set_error("pscv_head_index_entropy: this layer does not run the depth-sweep head (needs c_in = 8 and a depth axis of >= 3 six-plane blocks per chunk); use pscv_conv3d + pscv_softargmin"); return -3; }
     PSCV_CHECK_LAUNCH("pscv_head_index_entropy");

@@ -16,22 +16,13 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): CostRegNet.conv0 = ConvBnReLU3D(32, 8) models/MVSNet/model.py:46,75
 // (block definition models/MVSNet/module.py:41-48).
-#include "pscv_common.h"
+#include "conv_common.h"
 #include <type_traits>
 
 namespace pscv {
 
-struct SweepArgs {
-    const uint16_t* in;
-    const uint16_t* wpk;     // [4 p_rel][9 taps][64 lanes][8]
-    const float* scale;
-    const float* bias;
-    const float* floor;
-    const uint16_t* skip;
-    void* out;
-    int in_cs, in_co, skip_cs, skip_co, out_cs, out_co;
-    int out_f32;
-    int B, D, Hh, W;
+struct SweepArgs : ConvIO {     // wpk: [4 p_rel][9 taps][64 lanes][8]
+    int D, Hh, W;
     int epi;
     const uint16_t* in2;     // narrow sweep, C_in = 16: channels 8..15 come from this tensor (the same tensor at in_co + 8 for a plain
     int in2_cs, in2_co;      // 16-channel input; another tensor for pscv_conv3d_cat2: torch.cat([a, b], channel) never materialised)
@@ -698,134 +689,88 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
     }
 }
 
-}  // namespace pscv
-
 template <typename H, int CIN, int PD, int COUT = 8>
-static int sweepc_launch_t(pscv::SweepArgs& a, long nblk, hipStream_t st) {
-    using namespace pscv;
+static int sweepc_launch_t(SweepArgs& a, long nblk, hipStream_t st) {
     return launch("pscv_conv3d(sweep)", conv3d_sweepc_kernel<H, CIN, PD, COUT>, dim3((unsigned)nblk), dim3(256), ScGeom<CIN>::LDS, st, a);
 }
 template <typename H, int CIN, int COUT = 8>
-static int sweepc_launch_pd(pscv::SweepArgs& a, long nblk, hipStream_t st) {
+static int sweepc_launch_pd(SweepArgs& a, long nblk, hipStream_t st) {
     // measured on MI355X over the six Vis stage shapes of BASELINE configurations 3 and 5 (scripts/kbench.py --only vis): distance 1
     // wins or ties everywhere -- deeper FIFOs cost a wave of occupancy (C_in = 16: 156 -> 182 VGPRs), and resident workgroups hide
     // more latency than registers do
-    const int pd = pscv::g_sweepc_pd > 0 ? pscv::g_sweepc_pd : (COUT == 16 ? 2 : 1);   // 16 -> 16 runs at two waves per SIMD anyway
+    const int pd = g_sweepc_pd > 0 ? g_sweepc_pd : (COUT == 16 ? 2 : 1);   // 16 -> 16 runs at two waves per SIMD anyway
     return pd == 1 ? sweepc_launch_t<H, CIN, 1, COUT>(a, nblk, st) : pd == 2 ? sweepc_launch_t<H, CIN, 2, COUT>(a, nblk, st)
                                                                              : sweepc_launch_t<H, CIN, 3, COUT>(a, nblk, st);
 }
 
-// entry used by pscv_conv3d (conv3d.hip) for kind == PSCV_CONV_S1P8 with (c_in, c_out) = (8, 8), (16, 8) or (16, 16)
-int pscv_conv3d_sweepc_launch(const void* in, int dtype, int c_in, int c_out, int in_cstride, int in_coff, const uint16_t* packed,
-                              const float* scale, const float* bias, const float* floor, const void* skip, int skip_cstride,
-                              int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype, int B, int D, int Hh, int W,
-                              int epi_flags, hipStream_t st, const void* in2, int in2_cstride, int in2_coff) {
-    using namespace pscv;
-    PSCV_CHECK_ARG((long)Hh * W * in_cstride * 2 < 0x7fffffffL, "pscv_conv3d(sweep): an input plane of %d x %d x %d channels exceeds 2 GiB", Hh, W, in_cstride);
-    PSCV_CHECK_ARG(!in2 || (c_in == 16 && (long)Hh * W * in2_cstride * 2 < 0x7fffffffL), "pscv_conv3d(sweep): a second input tensor needs c_in = 16 and planes below 2 GiB");
+// the part of the argument block that the three sweep kernels share; the tile height decides nth
+static void sweep_args(SweepArgs& a, const ConvCall& c, int th) {
+    static_cast<ConvIO&>(a) = c.io;
+    a.D = c.D; a.Hh = c.H; a.W = c.W; a.epi = c.epi;
+    a.nth = (c.H + th - 1) / th;
+    a.ntw = (c.W + 15) / 16;
+}
+
+// pscv_conv3d, kind S1P8 with (c_in, c_out) = (8, 8), (16, 8) or (16, 16), and pscv_conv3d_cat2
+int conv3d_sweepc_launch(const ConvCall& c) {
+    PSCV_CHECK_ARG((long)c.H * c.W * c.io.in_cs * 2 < 0x7fffffffL, "pscv_conv3d(sweep): an input plane of %d x %d x %d channels exceeds 2 GiB", c.H, c.W, c.io.in_cs);
+    PSCV_CHECK_ARG(!c.in2 || (c.c_in == 16 && (long)c.H * c.W * c.in2_cs * 2 < 0x7fffffffL), "pscv_conv3d(sweep): a second input tensor needs c_in = 16 and planes below 2 GiB");
     SweepArgs a;
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.in2 = in2 ? reinterpret_cast<const uint16_t*>(in2) : a.in;
-    a.in2_cs = in2 ? in2_cstride : in_cstride;
-    a.in2_co = in2 ? in2_coff : in_coff + 8;
-    a.wpk = packed; a.scale = scale; a.bias = bias; a.floor = floor;
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff;
-    a.out_cs = out_cstride; a.out_co = out_coff; a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.D = D; a.Hh = Hh; a.W = W; a.epi = epi_flags;
-    a.nth = (Hh + 7) / 8;
-    a.ntw = (W + 15) / 16;
+    sweep_args(a, c, 8);
+    a.in2 = c.in2 ? c.in2 : a.in;
+    a.in2_cs = c.in2 ? c.in2_cs : a.in_cs;
+    a.in2_co = c.in2 ? c.in2_co : a.in_co + 8;
     // one resident round of workgroups (4 per CU); each depth-chunk seam re-reads two halo planes
-    const long tiles = (long)B * a.nth * a.ntw;
-    const long slots = g_sweepc_slots > 0 ? g_sweepc_slots : (c_out == 16 ? 512 : 768);
-    const long ndc_want = tiles >= slots ? 1 : slots / tiles;
-    int dc = (int)((D + ndc_want - 1) / ndc_want);
-    dc = (dc + 1) & ~1;
-    dc = dc < 4 ? 4 : dc;
-    if (g_sweep_dc > 0) dc = g_sweep_dc & ~1;
-    dc = dc > D ? ((D + 1) & ~1) : dc;
-    a.dc = dc;
-    a.ndc = (D + dc - 1) / dc;
-    const long nblk = tiles * a.ndc;
-    a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(sweep): bad grid %ld", nblk); return -1; }
-    return with_half("pscv_conv3d(sweep)", dtype, [&](auto t) {
+    const long slots = g_sweepc_slots > 0 ? g_sweepc_slots : (c.c_out == 16 ? 512 : 768);
+    a.dc = plan_depth_chunk(c.D, (long)a.B * a.nth * a.ntw, slots, 4, true, g_sweep_dc);
+    a.ndc = (c.D + a.dc - 1) / a.dc;
+    const long nblk = finish_grid("pscv_conv3d(sweep)", a.B, a.nth, a.ntw, a.ndc, a.mg_th, a.mg_tw, a.mg_dc);
+    if (nblk < 0) return -1;
+    return with_half("pscv_conv3d(sweep)", c.dtype, [&](auto t) {
         using H = typename decltype(t)::type;
-        if (c_out == 16) return sweepc_launch_pd<H, 16, 16>(a, nblk, st);
-        return c_in == 8 ? sweepc_launch_pd<H, 8>(a, nblk, st) : sweepc_launch_pd<H, 16>(a, nblk, st);
+        if (c.c_out == 16) return sweepc_launch_pd<H, 16, 16>(a, nblk, c.st);
+        return c.c_in == 8 ? sweepc_launch_pd<H, 8>(a, nblk, c.st) : sweepc_launch_pd<H, 16>(a, nblk, c.st);
     });
 }
 
-// entry used by pscv_conv3d (conv3d.hip) for kind == PSCV_CONV_S1P8
-PSCV_PROF_EXPORT(sweep)
-
-int pscv_conv3d_sweep8_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                              const float* scale, const float* bias, const float* floor, const void* skip,
-                              int skip_cstride, int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype,
-                              int B, int D, int Hh, int W, int epi_flags, hipStream_t st) {
-    using namespace pscv;
+// pscv_conv3d, kind S1P8 with 32 -> 8
+int conv3d_sweep8_launch(const ConvCall& c) {
+    PSCV_CHECK_ARG((long)c.H * c.W * c.io.in_cs * 2 < 0x7fffffffL, "pscv_conv3d(sweep): an input plane of %d x %d x %d channels exceeds 2 GiB", c.H, c.W, c.io.in_cs);
+    const bool kdm = g_sweep_kdm != 0;          // the kd-in-rows kernel: 3-slot ring
+    const bool tall = !kdm && g_sweep_th16 && c.H >= 16;
     SweepArgs a;
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.wpk = packed; a.scale = scale; a.bias = bias; a.floor = floor;
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff;
-    a.out_cs = out_cstride; a.out_co = out_coff; a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.D = D; a.Hh = Hh; a.W = W; a.epi = epi_flags;
-    PSCV_CHECK_ARG((long)Hh * W * in_cstride * 2 < 0x7fffffffL, "pscv_conv3d(sweep): an input plane of %d x %d x %d channels exceeds 2 GiB", Hh, W, in_cstride);
-    if (g_sweep_kdm) {   // kd-in-rows kernel: 3-slot ring, three (knob 2: four) workgroups per CU in one resident round
+    sweep_args(a, c, tall ? 16 : 8);
+    const long tiles = (long)a.B * a.nth * a.ntw;
+    if (kdm) {
 #ifdef PSCV_ABLATE
         a.in2_cs = g_fuse_c0;   // ablation flags: 1 no plane fetch, 2 no stores, 4 no LDS reads / MFMAs (scripts/dev/kdm_bench.py --ablate)
 #endif
-        a.nth = (Hh + 7) / 8;
-        a.ntw = (W + 15) / 16;
-        const long tiles = (long)B * a.nth * a.ntw;
-        const long slots = g_sweep_kdm >= 2 ? 1024 : 768;
-        const long ndc_want = tiles >= slots ? 1 : slots / tiles;
-        int dc = (int)((D + ndc_want - 1) / ndc_want);
-        dc = dc < 4 ? 4 : dc;
-        if (g_sweep_dc > 0) dc = g_sweep_dc;
-        dc = dc > D ? D : dc;
-        a.dc = dc;
-        a.ndc = (D + dc - 1) / dc;
-        const long nblk = tiles * a.ndc;
-        a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
-        if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(sweep): bad grid %ld", nblk); return -1; }
-        const int pd = g_sweep_kdm_pd > 0 ? g_sweep_kdm_pd : 1;
-        return with_half("pscv_conv3d(sweep)", dtype, [&](auto t) {
-            using H = typename decltype(t)::type;
-            const dim3 grid((unsigned)nblk);
-            if (pd >= 2) return skip ? launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, true, 2>, grid, dim3(256), KM_LDS, st, a)
-                                     : launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, false, 2>, grid, dim3(256), KM_LDS, st, a);
-            return skip ? launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, true, 1>, grid, dim3(256), KM_LDS, st, a)
-                        : launch("pscv_conv3d(sweep)", conv3d_sweep8_kdm_kernel<H, false, 1>, grid, dim3(256), KM_LDS, st, a);
-        });
+        // three (knob 2: four) workgroups per CU in one resident round
+        a.dc = plan_depth_chunk(c.D, tiles, g_sweep_kdm >= 2 ? 1024 : 768, 4, false, g_sweep_dc);
+    } else {
+        // depth chunk: the whole grid should be ONE resident round of workgroups (256 CUs x 2 for 8-row tiles, x 1 for
+        // 16-row tiles): no tail round, and the fewest chunk seams (each seam re-reads 2 halo planes).  Measured at the
+        // headline size: 64 planes / 480 workgroups 90 us, 12 planes / 2560 workgroups 130 us.
+        a.dc = plan_depth_chunk(c.D, tiles, tall ? 256 : 512, 4, true, g_sweep_dc);
     }
-    const bool tall = g_sweep_th16 && Hh >= 16;
-    const int TH = tall ? 16 : 8;
-    a.nth = (Hh + TH - 1) / TH;
-    a.ntw = (W + 15) / 16;
-    // depth chunk: the whole grid should be ONE resident round of workgroups (256 CUs x 2 for 8-row tiles, x 1 for
-    // 16-row tiles): no tail round, and the fewest chunk seams (each seam re-reads 2 halo planes).  Measured at the
-    // headline size: 64 planes / 480 workgroups 90 us, 12 planes / 2560 workgroups 130 us.
-    const long tiles = (long)B * a.nth * a.ntw;
-    const long slots = tall ? 256 : 512;
-    const long ndc_want = tiles >= slots ? 1 : slots / tiles;
-    int dc = (int)((D + ndc_want - 1) / ndc_want);
-    dc = (dc + 1) & ~1;
-    dc = dc < 4 ? 4 : dc;
-    if (g_sweep_dc > 0) dc = g_sweep_dc & ~1;
-    dc = dc > D ? ((D + 1) & ~1) : dc;
-    a.dc = dc;
-    a.ndc = (D + dc - 1) / dc;
-    const long nblk = tiles * a.ndc;
-    a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(sweep): bad grid %ld", nblk); return -1; }
-    return with_half("pscv_conv3d(sweep)", dtype, [&](auto t) {
+    a.ndc = (c.D + a.dc - 1) / a.dc;
+    const long nblk = finish_grid("pscv_conv3d(sweep)", a.B, a.nth, a.ntw, a.ndc, a.mg_th, a.mg_tw, a.mg_dc);
+    if (nblk < 0) return -1;
+    const bool skip = c.io.skip != nullptr;
+    const int pd = g_sweep_kdm_pd > 0 ? g_sweep_kdm_pd : 1;
+    return with_half("pscv_conv3d(sweep)", c.dtype, [&](auto t) {
         using H = typename decltype(t)::type;
+        const char* what = "pscv_conv3d(sweep)";
         const dim3 grid((unsigned)nblk);
-        return tall ? launch("pscv_conv3d(sweep)", conv3d_sweep8_kernel<H, 16>, grid, dim3(512), SwGeom<16>::LDS, st, a)
-                    : launch("pscv_conv3d(sweep)", conv3d_sweep8_kernel<H, 8>, grid, dim3(256), SwGeom<8>::LDS, st, a);
+        if (kdm && pd >= 2) return skip ? launch(what, conv3d_sweep8_kdm_kernel<H, true, 2>, grid, dim3(256), KM_LDS, c.st, a)
+                                        : launch(what, conv3d_sweep8_kdm_kernel<H, false, 2>, grid, dim3(256), KM_LDS, c.st, a);
+        if (kdm) return skip ? launch(what, conv3d_sweep8_kdm_kernel<H, true, 1>, grid, dim3(256), KM_LDS, c.st, a)
+                             : launch(what, conv3d_sweep8_kdm_kernel<H, false, 1>, grid, dim3(256), KM_LDS, c.st, a);
+        return tall ? launch(what, conv3d_sweep8_kernel<H, 16>, grid, dim3(512), SwGeom<16>::LDS, c.st, a)
+                    : launch(what, conv3d_sweep8_kernel<H, 8>, grid, dim3(256), SwGeom<8>::LDS, c.st, a);
     });
 }
+
+}  // namespace pscv
+
+PSCV_PROF_EXPORT(sweep)

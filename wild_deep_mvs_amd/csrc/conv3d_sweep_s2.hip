@@ -16,21 +16,12 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): ConvBnReLU3D(8, 16, stride=2) models/MVSNet/model.py:49,76 (block models/MVSNet/module.py:41-48);
 // BasicBlock(8, 16, stride 2).conv1 + downsample of models/VisMVSNet/nn_utils.py:27-37, 215-226.
-#include "pscv_common.h"
+#include "conv_common.h"
 
 namespace pscv {
 
-struct S2sArgs {
-    const uint16_t* in;
-    const uint4* wpk;        // [7 steps][nt_total][64 lanes] x 8 halves: the dense S2 packing
-    const float* scale;
-    const float* bias;
-    const float* floor;
-    const uint16_t* skip;
-    void* out;
-    int in_cs, in_co, skip_cs, skip_co, out_cs, out_co;
-    int out_f32;
-    int B, Di, Hi, Wi, Do, Ho, Wo;
+struct S2sArgs : ConvIO {       // wpk: [7 steps][nt_total][64 lanes] x 8 halves, the dense S2 packing
+    int Di, Hi, Wi, Do, Ho, Wo;
     int cout, epi;
     int nth, ntw, ndc, dc;   // output tiles along h, w; depth chunks and output planes per chunk
     unsigned mg_th, mg_tw, mg_dc;
@@ -63,11 +54,12 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
     PSCV_PROF_BEGIN
 
     // ---- A fragments of the whole layer ----
+    const uint4* wpk = reinterpret_cast<const uint4*>(a.wpk);
     uint4 wf[S2S_STEPS][NT];
 #pragma unroll
     for (int s = 0; s < S2S_STEPS; ++s)
 #pragma unroll
-        for (int m = 0; m < NT; ++m) wf[s][m] = a.wpk[(s * NT + m) * 64 + lane];
+        for (int m = 0; m < NT; ++m) wf[s][m] = wpk[(s * NT + m) * 64 + lane];
 
     // ---- B operand: lane group g of step s holds tap 4 s + g (taps >= 27 carry zero weights: any staged voxel will do) ----
     int kd_s[S2S_STEPS], boff[S2S_STEPS][S2S_R];
@@ -235,53 +227,38 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
 
 template <typename H, int NT>
 static int s2s_launch(const S2sArgs& a, long nblk, hipStream_t st) {
-    if (!a.skip && !a.out_f32) hipLaunchKernelGGL((conv3d_sweep_s2_kernel<H, NT, true>), dim3((unsigned)nblk), dim3(256), S2S_NSLOT * S2S_PB, st, a);
-    else hipLaunchKernelGGL((conv3d_sweep_s2_kernel<H, NT, false>), dim3((unsigned)nblk), dim3(256), S2S_NSLOT * S2S_PB, st, a);
-    return 0;
+    const char* what = "pscv_conv3d(s2 sweep)";
+    const dim3 grid((unsigned)nblk);
+    if (!a.skip && !a.out_f32) return launch(what, conv3d_sweep_s2_kernel<H, NT, true>, grid, dim3(256), S2S_NSLOT * S2S_PB, st, a);
+    return launch(what, conv3d_sweep_s2_kernel<H, NT, false>, grid, dim3(256), S2S_NSLOT * S2S_PB, st, a);
+}
+
+// pscv_conv3d, kind S2: declines (1) the layers and sizes that stay on the brick kernel
+int conv3d_sweep_s2_launch(const ConvCall& c) {
+    const ConvIO& io = c.io;
+    const int Do = (c.D + 1) / 2, Ho = (c.H + 1) / 2, Wo = (c.W + 1) / 2;
+    if (!g_conv_s2_sweep || c.c_in != 8 || c.c_out > 32 || c.c_out % 4) return 1;
+    if (g_conv_s2_sweep != 2 && (long)io.B * Do * Ho * Wo < S2S_MIN_VOXELS) return 1;      // (2: any size -- tests)
+    // 32-bit in-plane element offsets on top of 64-bit plane bases
+    if ((long)c.H * c.W * io.in_cs * 2 >= 0x7fffffffL || (long)Ho * Wo * (io.out_cs > io.skip_cs ? io.out_cs : io.skip_cs) >= 0x7fffffffL) return 1;
+    S2sArgs a;
+    static_cast<ConvIO&>(a) = io;
+    a.Di = c.D; a.Hi = c.H; a.Wi = c.W; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
+    a.cout = c.c_out; a.epi = c.epi;
+    a.nth = (Ho + S2S_TH - 1) / S2S_TH;
+    a.ntw = (Wo + 15) / 16;
+    // depth chunks: about one resident round of workgroups (3 per CU), at least 4 output planes per sweep
+    a.dc = plan_depth_chunk(Do, (long)a.B * a.nth * a.ntw, g_s2s_slots > 0 ? g_s2s_slots : 768, 4, false, 0);
+    a.ndc = (Do + a.dc - 1) / a.dc;
+    const long nblk = finish_grid("pscv_conv3d(s2 sweep)", a.B, a.nth, a.ntw, a.ndc, a.mg_th, a.mg_tw, a.mg_dc);
+    if (nblk < 0) return -1;
+    const int nt = (c.c_out + 15) / 16;
+    return with_half("pscv_conv3d(s2 sweep)", c.dtype, [&](auto t) {
+        using H = typename decltype(t)::type;
+        return nt == 1 ? s2s_launch<H, 1>(a, nblk, c.st) : s2s_launch<H, 2>(a, nblk, c.st);
+    });
 }
 
 }  // namespace pscv
 
 PSCV_PROF_EXPORT(s2s)
-
-// returns 1 when the layer is not one this kernel takes (the caller then uses the brick kernel), 0 on a launch, < 0 on error
-int pscv_conv3d_sweep_s2_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed, const float* scale,
-                                const float* bias, const float* floor, const void* skip, int skip_cstride, int skip_coff, void* out,
-                                int out_cstride, int out_coff, int out_dtype, int B, int Di, int Hi, int Wi, int c_in, int c_out,
-                                int epi_flags, hipStream_t st) {
-    using namespace pscv;
-    const int Do = (Di + 1) / 2, Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;
-    if (!g_conv_s2_sweep || c_in != 8 || c_out > 32 || c_out % 4) return 1;
-    if (g_conv_s2_sweep != 2 && (long)B * Do * Ho * Wo < S2S_MIN_VOXELS) return 1;      // (2: any size -- tests)
-    // 32-bit in-plane element offsets on top of 64-bit plane bases
-    if ((long)Hi * Wi * in_cstride * 2 >= 0x7fffffffL || (long)Ho * Wo * (out_cstride > skip_cstride ? out_cstride : skip_cstride) >= 0x7fffffffL) return 1;
-    S2sArgs a;
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.wpk = reinterpret_cast<const uint4*>(packed);
-    a.scale = scale; a.bias = bias; a.floor = floor;
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff;
-    a.out_cs = out_cstride; a.out_co = out_coff; a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Do = Do; a.Ho = Ho; a.Wo = Wo;
-    a.cout = c_out; a.epi = epi_flags;
-    a.nth = (Ho + S2S_TH - 1) / S2S_TH;
-    a.ntw = (Wo + 15) / 16;
-    // depth chunks: about one resident round of workgroups (3 per CU), at least 4 output planes per sweep
-    const long tiles = (long)B * a.nth * a.ntw;
-    const long slots = g_s2s_slots > 0 ? g_s2s_slots : 768;
-    const long ndc_want = tiles >= slots ? 1 : slots / tiles;
-    int dc = (int)((Do + ndc_want - 1) / ndc_want);
-    dc = dc < 4 ? 4 : dc;
-    dc = dc > Do ? Do : dc;
-    a.dc = dc;
-    a.ndc = (Do + dc - 1) / dc;
-    const long nblk = tiles * a.ndc;
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(s2 sweep): bad grid %ld", nblk); return -1; }
-    a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw); a.mg_dc = fast_div_magic(a.ndc);
-    const int nt = (c_out + 15) / 16;
-    return with_half("pscv_conv3d(s2 sweep)", dtype, [&](auto t) {
-        using H = typename decltype(t)::type;
-        return nt == 1 ? s2s_launch<H, 1>(a, nblk, st) : s2s_launch<H, 2>(a, nblk, st);
-    });
-}

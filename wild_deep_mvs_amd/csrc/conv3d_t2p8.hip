@@ -10,21 +10,12 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): Sequential(ConvTranspose3d(16, 8, k3, p1, op1, s2), BatchNorm3d, ReLU) + skip add
 // models/MVSNet/model.py:67-70,81; ConvTranspose3d(16, 8) of the Vis U-Net models/VisMVSNet/nn_utils.py:232.
-#include "pscv_common.h"
+#include "conv_common.h"
 
 namespace pscv {
 
-struct Tp8Args {
-    const uint16_t* in;
-    const uint16_t* wpk;     // [9 steps][64 lanes][8]; step order: (pd,ph) = (0,0) | (0,1): th 0,1 | (1,0): td 0,1 | (1,1): td,th
-    const float* scale;
-    const float* bias;
-    const float* floor;
-    const uint16_t* skip;
-    void* out;
-    int in_cs, in_co, skip_cs, skip_co, out_cs, out_co;
-    int out_f32;
-    int B, Di, Hi, Wi;
+struct Tp8Args : ConvIO {       // wpk: [9 steps][64 lanes][8]; step order: (pd,ph) = (0,0) | (0,1): th 0,1 | (1,0): td 0,1 | (1,1): td,th
+    int Di, Hi, Wi;
     int epi;
     int ntd, nth, ntw;
     unsigned mg_td, mg_th, mg_tw;
@@ -186,28 +177,19 @@ __global__ __launch_bounds__(256) void conv3d_t2p8_kernel(const Tp8Args a) {
     PSCV_PROF_END(t2p8, blockIdx.x)
 }
 
+// pscv_conv3d, kind T2P8
+int conv3d_t2p8_launch(const ConvCall& c) {
+    Tp8Args a;
+    static_cast<ConvIO&>(a) = c.io;
+    a.Di = c.D; a.Hi = c.H; a.Wi = c.W; a.epi = c.epi;
+    a.ntd = (c.D + TP_TD - 1) / TP_TD; a.nth = (c.H + TP_TH - 1) / TP_TH; a.ntw = (c.W + 15) / 16;
+    const long nblk = finish_grid("pscv_conv3d(t2p8)", a.B, a.ntd, a.nth, a.ntw, a.mg_td, a.mg_th, a.mg_tw);
+    if (nblk < 0) return -1;
+    return with_half("pscv_conv3d(t2p8)", c.dtype, [&](auto t) {
+        return launch("pscv_conv3d(t2p8)", conv3d_t2p8_kernel<typename decltype(t)::type>, dim3((unsigned)nblk), dim3(256), 0, c.st, a);
+    });
+}
+
 }  // namespace pscv
 
 PSCV_PROF_EXPORT(t2p8)
-
-int pscv_conv3d_t2p8_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed,
-                            const float* scale, const float* bias, const float* floor, const void* skip, int skip_cstride,
-                            int skip_coff, void* out, int out_cstride, int out_coff, int out_dtype, int B, int Di, int Hi,
-                            int Wi, int epi_flags, hipStream_t st) {
-    using namespace pscv;
-    Tp8Args a;
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.wpk = packed; a.scale = scale; a.bias = bias; a.floor = floor;
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff;
-    a.out_cs = out_cstride; a.out_co = out_coff; a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.epi = epi_flags;
-    a.ntd = (Di + TP_TD - 1) / TP_TD; a.nth = (Hi + TP_TH - 1) / TP_TH; a.ntw = (Wi + 15) / 16;
-    a.mg_td = fast_div_magic(a.ntd); a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw);
-    const long nblk = (long)B * a.ntd * a.nth * a.ntw;
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_conv3d(t2p8): bad grid %ld", nblk); return -1; }
-    return with_half("pscv_conv3d(t2p8)", dtype, [&](auto t) {
-        return launch("pscv_conv3d(t2p8)", conv3d_t2p8_kernel<typename decltype(t)::type>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-    });
-}

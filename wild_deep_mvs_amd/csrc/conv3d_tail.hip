@@ -24,7 +24,7 @@
 // and `prob` of CostRegNet.forward, models/MVSNet/model.py:67-72,81-82.
 #include <type_traits>
 
-#include "pscv_common.h"
+#include "conv_common.h"
 
 namespace pscv {
 
@@ -427,8 +427,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
 
 }  // namespace pscv
 
-void pscv_softargmin_merge_launch(const float* part, const float* logits, int ndc, int B, int D, long hw, float* o_depth, float* o_conf, hipStream_t st);
-
 // Fused tail.  Returns 0 if launched, 1 if this shape is not covered (the caller runs the two layers), negative on error.
 // depth != null: the sweep also keeps softmax statistics per depth chunk and a merge launch writes the regressed depth (and the 4-plane
 // photometric confidence) -- models/MVSNet/model.py:207-215; workspace: pscv_tail_sweep_workspace(B, Di, Hi, Wi) floats.
@@ -500,7 +498,11 @@ extern "C" int pscv_tail_sweep(const void* in, int dtype, int in_cstride, int in
                     : launch("pscv_tail_sweep", conv3d_tail_kernel<H, true, true, false>, grid, dim3(256), TL_LDS, st, a);
     });
     if (rc) return rc;
-    if (fuse) pscv_softargmin_merge_launch(workspace, logits, ndc, B, D, (long)H * W, out_depth, out_conf, st);
+    if (fuse) {
+        ConvCall m{};       // what the merge reads of a call: the logits volume and the stream
+        m.io.out = logits; m.io.B = B; m.D = D; m.H = H; m.W = W; m.st = st;
+        softargmin_merge_launch(m, HeadOut{depth, depth_bstride, workspace, workspace_floats, out_depth, out_conf, nullptr, nullptr}, ndc);
+    }
     PSCV_CHECK_LAUNCH("pscv_tail_sweep");
     return 0;
 }

@@ -22,21 +22,12 @@
 //
 // Replaces (fdarmon/wild_deep_mvs): ConvBnReLU3D 32 -> 32, 32 -> 64 (stride 1), 64 -> 64 and the stride-1 ConvTranspose3d block
 // 64 -> 32 of models/CVP_MVSNet/models/net.py:50-85 at the refinement levels' sizes.
-#include "pscv_common.h"
+#include "conv_common.h"
 
 namespace pscv {
 
-struct WideArgs {
-    const uint16_t* in;
-    const uint4* wpk;        // kind S1 packing: [k-step][output tile][64 lanes] x 8 halves
-    const float* scale;
-    const float* bias;
-    const float* floor;
-    const uint16_t* skip;
-    void* out;
-    int in_cs, in_co, skip_cs, skip_co, out_cs, out_co;
-    int out_f32;
-    int B, D, Hh, W;
+struct WideArgs : ConvIO {      // wpk: kind S1 packing, [k-step][output tile][64 lanes] x 8 halves
+    int D, Hh, W;
     int epi;
     int ntd, nth, ntw;
     unsigned mg_td, mg_th, mg_tw;
@@ -143,7 +134,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
     };
     uint4 wn[2][WLD];
     // (weights through a buffer descriptor: the stage's base is the scalar offset, a thread's chunk one 32-bit register)
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(a.wpk), (short)0, NSTEPS * NT * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wpk), (short)0, NSTEPS * NT * 1024, 0x00020000);
     auto wfetch = [&](const int stage, const int buf) {
         const int cnt = wp_slen(CIN, stage) * NT * 64, base = wp_sbase(CIN, stage) * NT * 64;
 #pragma unroll
@@ -322,43 +313,34 @@ static int widep_launch(const WideArgs& a, long nblk, hipStream_t st) {
     return launch("pscv_conv3d(wide)", conv3d_widep_kernel<H, CIN, NT>, dim3((unsigned)grid), dim3(512), LDS, st, a, (int)nblk);
 }
 
-}  // namespace pscv
-
-PSCV_PROF_EXPORT(wide)
-
-// Returns 0 if launched, 1 if the layer / size is not covered (the caller runs the brick kernel), negative on error.
-int pscv_conv3d_wide_launch(const void* in, int dtype, int in_cstride, int in_coff, const uint16_t* packed, const float* scale,
-                            const float* bias, const float* floor, const void* skip, int skip_cstride, int skip_coff, void* out,
-                            int out_cstride, int out_coff, int out_dtype, int B, int D, int Hh, int W, int c_in, int c_out, int epi_flags,
-                            hipStream_t st) {
-    using namespace pscv;
+// pscv_conv3d, kind S1: declines (1) the layers and sizes that stay on the brick kernel
+int conv3d_wide_launch(const ConvCall& c) {
+    const ConvIO& io = c.io;
     if (!g_conv_wide) return 1;
-    if (!((c_in == 32 || c_in == 64) && (c_out == 32 || c_out == 64))) return 1;
+    if (!((c.c_in == 32 || c.c_in == 64) && (c.c_out == 32 || c.c_out == 64))) return 1;
     // measured at CVP's configuration 4 (scripts/dev/config_kernels.py 4): 64 -> 64 128 -> 110 us, 64 -> 32 91 -> 75 us per launch;
     // the 32-input layers (27 k-steps only) are no faster than on the brick kernel (32 -> 32 38 vs 35..43 us, 32 -> 64 62 vs 68 us):
     // they take this kernel only when it is forced ("conv_wide" = 2: tests)
-    if (c_in == 32 && g_conv_wide < 2) return 1;
-    if ((out_cstride | out_coff) & 3 || (skip && ((skip_cstride | skip_coff) & 3))) return 1;
+    if (c.c_in == 32 && g_conv_wide < 2) return 1;
+    if ((io.out_cs | io.out_co) & 3 || (io.skip && ((io.skip_cs | io.skip_co) & 3))) return 1;
     WideArgs a;
-    a.in = reinterpret_cast<const uint16_t*>(in);
-    a.wpk = reinterpret_cast<const uint4*>(packed);
-    a.scale = scale; a.bias = bias; a.floor = floor;
-    a.skip = reinterpret_cast<const uint16_t*>(skip);
-    a.out = out;
-    a.in_cs = in_cstride; a.in_co = in_coff; a.skip_cs = skip_cstride; a.skip_co = skip_coff; a.out_cs = out_cstride; a.out_co = out_coff;
-    a.out_f32 = out_dtype == PSCV_F32;
-    a.B = B; a.D = D; a.Hh = Hh; a.W = W; a.epi = epi_flags;
-    a.ntd = (D + WD_TD - 1) / WD_TD; a.nth = (Hh + WD_TH - 1) / WD_TH; a.ntw = (W + 15) / 16;
+    static_cast<ConvIO&>(a) = io;
+    a.D = c.D; a.Hh = c.H; a.W = c.W; a.epi = c.epi;
+    a.ntd = (c.D + WD_TD - 1) / WD_TD; a.nth = (c.H + WD_TH - 1) / WD_TH; a.ntw = (c.W + 15) / 16;
     a.mg_td = fast_div_magic(a.ntd); a.mg_th = fast_div_magic(a.nth); a.mg_tw = fast_div_magic(a.ntw);
-    const long nblk = (long)B * a.ntd * a.nth * a.ntw;
+    const long nblk = (long)a.B * a.ntd * a.nth * a.ntw;
     // one 8-wave workgroup per CU: volumes with fewer tiles than CUs stay on the brick kernel's small tiles (more, lighter workgroups)
     if (nblk < (g_conv_wide >= 2 ? 1 : 512) || nblk > 0x7fffffffL) return 1;      // ("conv_wide" >= 2: at any size)
-    const int nt = c_out / 16;
+    const int nt = c.c_out / 16;
     // a batch item's input volume is addressed through a 32-bit buffer descriptor
-    if ((long)D * Hh * W * in_cstride * 2 >= 0x7fffffffL) return 1;
-    return with_half("pscv_conv3d(wide)", dtype, [&](auto t) {
+    if ((long)c.D * c.H * c.W * io.in_cs * 2 >= 0x7fffffffL) return 1;
+    return with_half("pscv_conv3d(wide)", c.dtype, [&](auto t) {
         using H = typename decltype(t)::type;
-        if (c_in == 64) return nt == 4 ? widep_launch<H, 64, 4>(a, nblk, st) : widep_launch<H, 64, 2>(a, nblk, st);
-        return nt == 4 ? widep_launch<H, 32, 4>(a, nblk, st) : widep_launch<H, 32, 2>(a, nblk, st);
+        if (c.c_in == 64) return nt == 4 ? widep_launch<H, 64, 4>(a, nblk, c.st) : widep_launch<H, 64, 2>(a, nblk, c.st);
+        return nt == 4 ? widep_launch<H, 32, 4>(a, nblk, c.st) : widep_launch<H, 32, 2>(a, nblk, c.st);
     });
 }
+
+}  // namespace pscv
+
+PSCV_PROF_EXPORT(wide)
