@@ -952,6 +952,65 @@ int pscv_resample_u8_pass(const unsigned char* src, long src_pitch, int lines, i
 int pscv_depth_nearest_crop(const float* depth, int th, int tw, int oh, int ow, int y0, int x0, int ch, int cw, float min_d,
                             float max_d, float* out_depth, unsigned char* out_mask, void* stream);
 
+/*
+ * Loss reductions and depth-map scores (an addition to ABI 14: new exports only, no existing signature changes): the end of
+ * models/trainer.py:step (trainer.py:114-198) and the depth-map protocol of Trainer.test / depthmap_eval.py:104-143
+ * (csrc/depth_gt.hip).  fp32 data; a mask is uint8 / bool (valid where non-zero) or fp32 holding 0 or 1
+ * (valid where 1 for the ground-truth masks, where non-zero for the given masks).  Asynchronous on `stream`, no host wait, no float
+ * atomics: per-block partial sums in the caller's workspace, combined in a fixed order in fp64 -- equal inputs, equal bits.
+ *
+ * One call takes a table of n_terms <= PSCV_LOSS_MAX_TERMS terms as PARALLEL HOST ARRAYS (entry t describes term t; the arrays are
+ * read before the call returns, the table travels in the kernel arguments).  With l the per-pixel loss, m the mask, C = sum m,
+ * S_l = sum l m, S_u = sum (l exp(-u) + u) m:
+ *   kind                 a          u       gt        mask        interval   l                          term
+ *   PSCV_LOSS_GT_PLAIN   d [b,h,w]  -       [b,H,W]   [b,H,W]     [b]        |d - gt_down| / interval_b   S_l / C (NaN when C = 0)
+ *   PSCV_LOSS_GT_BAYES   d [b,h,w]  [b,h,w] [b,H,W]   [b,H,W]     [b]        the same                     C != 0 ? (S_u + S_l) / C : S_u + S_l
+ *   PSCV_LOSS_L_PLAIN    l [n]      -       -         [n]         -          given                        C != 0 ? S_l / C : S_l
+ *   PSCV_LOSS_L_BAYES    l [n]      [n]     -         [n]         -          given                        as GT_BAYES
+ *   dims [n_terms][5] (host, long) = (b, h, w, H, W); the L kinds use n = b h w and ignore H, W.  mask_u8[t] != 0: the mask is bytes.
+ * gt_down and the down mask are F.interpolate(mode="bilinear", align_corners=False) and `== 1` for INTEGER ratios rh = H / h,
+ * rw = W / w (anything else is an error): per axis one tap at r i + (r - 1) / 2 for an odd ratio, the two taps r i + r / 2 - 1
+ * and the next, weighing 0.5 each, for an even one; m = 1 iff every tap used is valid; gt_down = 0.5 (0.5 a + 0.5 b) +
+ * 0.5 (0.5 c + 0.5 d) in that association; taps of weight zero are not read.
+ *
+ * pscv_loss_terms: two launches (reduce over the whole table; finish).  Device outputs: loss fp32 [1] = sum_t factors[t] term_t,
+ * term fp32 [n_terms], sums fp64 [n_terms][3] = (S_l, S_u, C), norm fp32 [n_terms] = the normaliser the backward needs (1 / C;
+ * 1 where the term is un-normalised).  workspace: pscv_loss_terms_workspace(n_terms, dims) bytes, 8-byte aligned.
+ * pscv_loss_terms_bwd: one launch; grad_out fp32 [1] is read on the device; per term the gradients asked for are written
+ * (grad_a: d d or d l, grad_u; a null entry or a null array = skip), the others recomputed per pixel:
+ *   d d = g f n m sign(d - gt_down) / interval_b (x (exp(-u) + 1) for the Bayes kinds; sign(0) = 0),  d u = g f n m (1 - l exp(-u)),
+ *   d l = g f n m (x (exp(-u) + 1)).  Exactly 0 where m = 0, except that a GT_PLAIN term with C = 0 has n = 1 / 0: NaN, as torch.
+ */
+#define PSCV_LOSS_GT_PLAIN 0
+#define PSCV_LOSS_GT_BAYES 1
+#define PSCV_LOSS_L_PLAIN 2
+#define PSCV_LOSS_L_BAYES 3
+#define PSCV_LOSS_MAX_TERMS 32
+#define PSCV_METRIC_MAX_THRESH 4
+#define PSCV_METRIC_SUMS 12
+long pscv_loss_terms_workspace(int n_terms, const long* dims);
+int pscv_loss_terms(int n_terms, const int* kinds, const void* const* a, const void* const* u, const void* const* gt,
+                    const void* const* mask, const void* const* interval, const int* mask_u8, const long* dims, const float* factors,
+                    void* workspace, float* loss, float* term, double* sums, float* norm, void* stream);
+int pscv_loss_terms_bwd(int n_terms, const int* kinds, const void* const* a, const void* const* u, const void* const* gt,
+                        const void* const* mask, const void* const* interval, const int* mask_u8, const long* dims,
+                        const float* factors, const float* norm, const float* grad_out, const void* const* grad_a,
+                        const void* const* grad_u, void* stream);
+/*
+ * pscv_depth_metrics: the five metric functions of models/utils.py:138-171 (each under compute_metrics_for_each_image) in one pass.
+ * est fp32 [b,h,w] is upsampled bilinearly to (H, W) with torch's fp32 index rule -- src = (in / out) (dst + 0.5) - 0.5 clamped
+ * at 0, the neighbour clamped at the edge; any sizes, h = H is a copy --, est and gt [b,H,W] are divided by step[b] (null = 1), a
+ * pixel counts where mask [b,H,W] > 0.5 (bytes: non-zero).  thr_abs (host, n_abs <= 4) and thr_rel (host, n_rel <= 4).
+ * sums fp64 [b][PSCV_METRIC_SUMS] = (C, sum |e - g|, count |e - g| > thr_abs[0..3], sum |e - g| / g, sum (e - g)^2 / g,
+ * count max(e / g, g / e) > thr_rel[0..3]); means fp32 [b + 1][PSCV_METRIC_SUMS - 1] = per image (EPE, fraction above thr_abs[k],
+ * Rel, SqRel, 1 - fraction above thr_rel[k]) and, in row b, their mean over the batch.  An empty mask gives NaN.
+ * workspace: pscv_depth_metrics_workspace(b, H, W) bytes.  Two launches.
+ */
+long pscv_depth_metrics_workspace(int b, int H, int W);
+int pscv_depth_metrics(const float* est, const float* gt, const void* mask, int mask_u8, const float* step, int b, int h, int w, int H,
+                       int W, const float* thr_abs, int n_abs, const float* thr_rel, int n_rel, void* workspace, double* sums,
+                       float* means, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,11 +9,14 @@ One ``pscv_photo_warp`` launch warps ALL source views (the reference loops over 
 ``pscv_ssim`` launch compares them all with the reference image; backward is ``pscv_ssim_bwd`` + ``pscv_photo_warp_bwd``."""
 from __future__ import annotations
 
+import warnings
+
 import torch
 import torch.distributed as dist
 
 import torch.nn.functional as F
 
+from .. import _lib as L
 from .. import ops
 from .. import training as T
 from ..utils.ssimLoss import SSIM
@@ -43,7 +46,14 @@ def _masked_mean(values, mask):
 class Trainer(_HarnessTrainer):
     """``args`` fields used: ``architecture``, ``upsample_training``, ``occ_masking``, ``geom_clamping``, ``supervised``,
     ``num_im_train``, ``print_every``, ``dataset`` (trainer.py:26-51).  ``model`` / ``args`` may be omitted when only the loss
-    methods are used (tests, function-level callers)."""
+    methods are used (tests, function-level callers).
+
+    ``loss_engine``: "torch" (the default) runs the loss reductions of ``step`` and the scores of ``test`` as torch operations, the
+    way the reference writes them; "pscv" runs them on the engine: one autograd node for all terms of
+    a step, one launch for the scores, no host wait."""
+
+    loss_engine = "torch"
+    _warned_ratio = False
 
     def __init__(self, model=None, args=None):
         super().__init__()
@@ -80,20 +90,26 @@ class Trainer(_HarnessTrainer):
     # ---- one training / validation iteration (trainer.py:96-206) ----------------------------------------------------------------
     def step(self, sample, train):
         cuda_sample = tocuda(sample)
-        b, n, c, h, w = cuda_sample["imgs"].shape
-        vis = self.args.architecture == "vis_mvsnet"
         ref_idx = dist.get_rank() if self.args.occ_masking else 0      # occlusion masking: rank r predicts view r
         src_idx = [i for i in range(self.args.num_im_train) if i != ref_idx]
         outputs = self.forward_network(cuda_sample, ref_idx)
-        out_hw = (h // self.output_down, w // self.output_down)
-        img = _resize_views(cuda_sample["imgs"], out_hw)
+        loss = self.loss_tail(outputs, sample, cuda_sample, ref_idx, src_idx)
+        self.keep_losses({("train_loss" if train else "val_loss"): loss.detach()})
+        self.nb_iter += 1
+        return loss
 
+    def loss_tail(self, outputs, sample, cuda_sample, ref_idx, src_idx):
+        """Network outputs -> the scalar loss (trainer.py:114-198), on the engine ``loss_engine`` names."""
+        b, n, c, h, w = cuda_sample["imgs"].shape
+        vis = self.args.architecture == "vis_mvsnet"
+        out_hw = (h // self.output_down, w // self.output_down)
+        engine = self._step_loss_engine(outputs, sample)
         if self.args.supervised:
             depth_list, pairs_list = outputs["depth_est_list"], outputs["depth_pair_list"]
             gt, gt_mask = sample["depth"].cuda(), sample["mask"].cuda().float()
             gts, masks = [], []
             for d in depth_list:
-                if d is None:
+                if d is None or engine == "pscv":          # (the engine resizes the ground truth per pixel, inside its one launch)
                     gts.append(None); masks.append(None)
                     continue
                 gts.append(F.interpolate(gt, size=tuple(d.shape[1:]), mode="bilinear", align_corners=False))
@@ -101,12 +117,28 @@ class Trainer(_HarnessTrainer):
                 masks.append((F.interpolate(gt_mask, size=tuple(d.shape[1:]), mode="bilinear", align_corners=False) == 1).float())
             interval = ((cuda_sample["depth_max"] - cuda_sample["depth_min"]) / 128)[:, 0].view(b, 1, 1, 1)
         else:
+            img = _resize_views(cuda_sample["imgs"], out_hw)
             depth_list = rec_upsample(outputs["depth_est_list"], out_hw)
             pairs_list = rec_upsample(outputs["depth_pair_list"], out_hw)
             K = cuda_sample["K"].clone()
             K[:, :, :2] /= self.output_down
             proj_mat = build_proj_matrices(K, cuda_sample["R"], cuda_sample["t"])
 
+        if engine == "pscv":
+            loss = self._pscv_loss(depth_list, pairs_list, vis, n, ref_idx, src_idx,
+                                   (gt, gt_mask, interval) if self.args.supervised else (img, proj_mat))
+        else:
+            loss = self._torch_loss(depth_list, pairs_list, vis, n, ref_idx, src_idx,
+                                    (gts, masks, interval) if self.args.supervised else (img, proj_mat))
+        return loss
+
+    # ---- the loss tail (trainer.py:114-198) ---------------------------------------------------------------------------------
+    def _torch_loss(self, depth_list, pairs_list, vis, n, ref_idx, src_idx, data):
+        """The reference's loops in torch: one masked mean per scale, one ``bayesian_version_loss`` per pair."""
+        if self.args.supervised:
+            gts, masks, interval = data
+        else:
+            img, proj_mat = data
         loss = 0
         for k, d in enumerate(depth_list):
             if d is None:
@@ -131,10 +163,57 @@ class Trainer(_HarnessTrainer):
                     pair = [ref_idx, src_idx[j]]
                     ssim, mask = self.photometricloss(img[:, pair], d, proj_mat[:, pair], suffix=f"_scale{k}_pairwise{j}")
                     loss = loss + factor * bayesian_version_loss(ssim, unc, mask)
-
-        self.keep_losses({("train_loss" if train else "val_loss"): loss.detach()})
-        self.nb_iter += 1
         return loss
+
+    def _pscv_loss(self, depth_list, pairs_list, vis, n, ref_idx, src_idx, data):
+        """The same terms as one table for ``training.loss_terms``: two launches forward and one backward whatever the number of
+        terms, no host wait (supervised: GT_PLAIN per scale, GT_BAYES per pair; unsupervised: L_PLAIN / L_BAYES on the SSIM maps)."""
+        terms = []
+        if self.args.supervised:
+            gt, gt_mask, interval = data
+            interval = interval.reshape(-1)
+        else:
+            img, proj_mat = data
+        for k, d in enumerate(depth_list):
+            if d is None:
+                continue
+            factor = self.factors_loss[k] if vis else 1
+            if self.args.supervised:
+                terms.append(ops.LossTerm(L.LOSS_GT_PLAIN, factor, d, gt_mask, gt=gt, interval=interval))
+            else:
+                ssim, mask = self.loss(img, d, proj_mat, idxs=None, suffix=f"_scale{k}")
+                terms.append(ops.LossTerm(L.LOSS_L_PLAIN, factor, ssim, mask))
+        for k, pairs in enumerate(pairs_list):
+            factor = (self.factors_loss[k] if vis else 1) / (n - 1)
+            for j, (d, (unc,)) in enumerate(pairs):
+                if d is None:
+                    continue
+                d = d.squeeze(1)
+                if self.args.supervised:
+                    terms.append(ops.LossTerm(L.LOSS_GT_BAYES, factor, d, gt_mask, u=unc, gt=gt, interval=interval))
+                else:
+                    pair = [ref_idx, src_idx[j]]
+                    ssim, mask = self.photometricloss(img[:, pair], d, proj_mat[:, pair], suffix=f"_scale{k}_pairwise{j}")
+                    terms.append(ops.LossTerm(L.LOSS_L_BAYES, factor, ssim, mask, u=unc))
+        return T.loss_terms(terms)[0]
+
+    def _step_loss_engine(self, outputs, sample):
+        """"torch" or "pscv" for this step: the engine's ground-truth terms need integer ratios between the ground truth and every
+        scale; a step without them runs the torch code (warned about once)."""
+        if self.loss_engine not in ("torch", "pscv"):
+            raise ValueError(f"Trainer.loss_engine must be 'torch' or 'pscv', got {self.loss_engine!r}")
+        if self.loss_engine == "torch" or not self.args.supervised:
+            return self.loss_engine
+        H, W = sample["depth"].shape[-2:]
+        maps = [d for d in outputs["depth_est_list"] if d is not None]
+        maps += [d for pairs in outputs["depth_pair_list"] for d, _ in pairs if d is not None]
+        if all(H % d.shape[-2] == 0 and W % d.shape[-1] == 0 for d in maps):
+            return "pscv"
+        if not self._warned_ratio:
+            warnings.warn(f"Trainer.loss_engine='pscv': the ground truth ({H} x {W}) is no integer multiple of every depth map; "
+                          "such steps use the torch loss", stacklevel=3)
+            self._warned_ratio = True
+        return "torch"
 
     # ---- evaluation iteration (trainer.py:280-321) ---------------------------------------------------------------------------
     def test(self, sample):
@@ -150,15 +229,24 @@ class Trainer(_HarnessTrainer):
         with torch.no_grad():
             outputs = self.model(cuda_sample["imgs"], cuda_sample["K"], cuda_sample["R"], cuda_sample["t"],
                                  cuda_sample["depth_min"], cuda_sample["depth_max"], **extra)
-            h, w = mask.shape[-2:]
             step = ((cuda_sample["depth_max"] - cuda_sample["depth_min"]) / 128)[:, 0]
-            est = F.interpolate(outputs["depth"].unsqueeze(1), (h, w), mode="bilinear", align_corners=False).squeeze(1) / step
+            scores = self.scores(outputs["depth"], depth_gt, mask, step)
+        self.keep_losses(scores)
+        self.nb_iter += 1
+
+    def scores(self, depth, depth_gt, mask, step):
+        """EPE and the 1 px / 3 px error rates in units of the depth step, at the ground truth's size (trainer.py:304-320)."""
+        if self.loss_engine == "pscv":                 # upsampling, the division by the step and all three scores: one pass
+            m = ops.depth_metrics(depth, depth_gt, mask, step, thresholds=(1, 3))
+            return {"EPE": m["EPE"], "1pxError": m["thres"][0], "3pxError": m["thres"][1]}
+        h, w = mask.shape[-2:]
+        with torch.no_grad():
+            est = F.interpolate(depth.unsqueeze(1), (h, w), mode="bilinear", align_corners=False).squeeze(1) / step
             gt = depth_gt / step
         valid = mask > 0.5
-        self.keep_losses({"EPE": AbsDepthError_metrics(est, gt, valid).detach(),
-                          "1pxError": Thres_metrics(est, gt, valid, 1).detach(),
-                          "3pxError": Thres_metrics(est, gt, valid, 3).detach()})
-        self.nb_iter += 1
+        return {"EPE": AbsDepthError_metrics(est, gt, valid).detach(),
+                "1pxError": Thres_metrics(est, gt, valid, 1).detach(),
+                "3pxError": Thres_metrics(est, gt, valid, 3).detach()}
 
     def loss(self, imgs, d, proj_mat, idxs, suffix=""):                                   # trainer.py:53-58
         if getattr(self.args, "occ_masking", False):

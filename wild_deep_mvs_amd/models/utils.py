@@ -5,8 +5,11 @@ working when this package is installed as ``models``).
 ``homo_warp`` is the function-level name BASELINE.json's north star gives the differentiable plane-sweep warp; the reference
 itself only has ``models.MVSNet.module.homo_warping``, so the alias points there -- that one runs on the
 HIP engine.  Everything else is host-side plumbing around the engine's outputs (nested-container mapping, device moves,
-evaluation metrics) and stays in torch, written for this package (one generic container mapper instead of the reference's
-decorator pair; the decorator names are kept because ``import *`` exports them)."""
+evaluation metrics), written for this package in torch (one generic container mapper instead of the reference's decorator pair;
+the decorator names are kept because ``import *`` exports them).  The metric functions and ``bayesian_version_loss`` below are
+the torch form with the reference's signatures; the engine computes the same five metrics in one pass (``ops.depth_metrics``) and
+the loss reductions as one table (``ops.loss_terms``), which ``Trainer.loss_engine = "pscv"`` and
+``evaluation/depthmap_eval.py`` use."""
 from __future__ import annotations
 
 import numpy as np

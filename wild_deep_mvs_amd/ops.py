@@ -2439,3 +2439,160 @@ def warp_cost_bwd(ref: Optional[torch.Tensor], srcs: Sequence[torch.Tensor], cam
         _p(dtemp), B, Cc, h, w, hs, ws, D, _dt(srcs[0]), _dt(grad_out), _stream()))
     L.check(rc, "pscv_warp_cost_bwd")
     return dref, dsrcs, dtemp
+
+
+# --------------------------------------------------------------------------------------------
+# loss reductions and depth-map scores (csrc/depth_gt.hip)
+# --------------------------------------------------------------------------------------------
+@dataclass
+class LossTerm:
+    """One row of the loss table (include/pscv.h, pscv_loss_terms).  ``a`` is the depth map ``d`` [b,h,w] of the ground-truth kinds
+    (``gt`` / ``mask`` [b,H,W], ``interval`` [b]) or the given per-pixel loss ``l`` of the L kinds (``mask`` with as many
+    elements); ``u`` is the log-uncertainty of the Bayes kinds.  Masks are bool / uint8 or fp32 holding 0 or 1."""
+    kind: int
+    factor: float
+    a: torch.Tensor
+    mask: torch.Tensor
+    u: Optional[torch.Tensor] = None
+    gt: Optional[torch.Tensor] = None
+    interval: Optional[torch.Tensor] = None
+
+
+def _f32c(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype != torch.float32:
+        raise TypeError(f"pscv.{what}: fp32 expected, got {t.dtype}")
+    return t.contiguous()
+
+
+def _mask_c(m: torch.Tensor, what: str):
+    """-> (contiguous mask, 1 for bytes / 0 for fp32)."""
+    if m.dtype in (torch.bool, torch.uint8):
+        return m.contiguous(), 1
+    if m.dtype == torch.float32:
+        return m.contiguous(), 0
+    raise TypeError(f"pscv.{what}: a mask is bool, uint8 or fp32, got {m.dtype}")
+
+
+class LossTable:
+    """The parallel host arrays of a term table, with the contiguous tensors they point into kept alive.  Built once per step by
+    ``loss_terms`` and handed on to ``loss_terms_bwd``."""
+
+    def __init__(self, terms: Sequence[LossTerm]):
+        terms = list(terms)
+        n = len(terms)
+        if n < 1:
+            raise ValueError("pscv.loss_terms: no terms")
+        if n > L.LOSS_MAX_TERMS:
+            raise L.PscvError(f"pscv.loss_terms: {n} terms, at most {L.LOSS_MAX_TERMS} in one call")
+        self.n = n
+        self.a, self.u, self.gt, self.mask, self.interval = [], [], [], [], []
+        kinds, u8, dims, factors = [], [], [], []
+        for t, tm in enumerate(terms):
+            has_gt = tm.kind in (L.LOSS_GT_PLAIN, L.LOSS_GT_BAYES)
+            has_u = tm.kind in (L.LOSS_GT_BAYES, L.LOSS_L_BAYES)
+            if tm.kind not in (L.LOSS_GT_PLAIN, L.LOSS_GT_BAYES, L.LOSS_L_PLAIN, L.LOSS_L_BAYES):
+                raise ValueError(f"pscv.loss_terms: term {t}: unknown kind {tm.kind}")
+            a = _f32c(tm.a, "loss_terms")
+            mask, is_u8 = _mask_c(tm.mask, "loss_terms")
+            u = _f32c(tm.u, "loss_terms") if has_u else None
+            if has_u and u.numel() != a.numel():
+                raise ValueError(f"pscv.loss_terms: term {t}: u has {u.numel()} elements, {a.numel()} expected")
+            if has_gt:
+                if a.dim() < 3 or tm.gt is None or tm.interval is None or tm.gt.dim() < 3:
+                    raise ValueError(f"pscv.loss_terms: term {t}: a ground-truth kind takes d [b,h,w], gt [b,H,W], mask [b,H,W] and interval [b]")
+                gt, interval = _f32c(tm.gt, "loss_terms"), _f32c(tm.interval, "loss_terms")
+                b, (h, w), (H, W) = a.shape[0], a.shape[-2:], gt.shape[-2:]
+                if a.numel() != b * h * w or gt.numel() != b * H * W or mask.numel() != gt.numel() or interval.numel() != b:
+                    raise ValueError(f"pscv.loss_terms: term {t}: shapes d {tuple(a.shape)}, gt {tuple(gt.shape)}, mask {tuple(mask.shape)}, "
+                                     f"interval {tuple(interval.shape)} do not belong together")
+                dims += [b, h, w, H, W]
+            else:
+                gt = interval = None
+                if mask.numel() != a.numel():
+                    raise ValueError(f"pscv.loss_terms: term {t}: mask has {mask.numel()} elements, {a.numel()} expected")
+                dims += [a.numel(), 1, 1, 0, 0]
+            _dev(a, mask, u, gt, interval)
+            self.a.append(a); self.u.append(u); self.gt.append(gt); self.mask.append(mask); self.interval.append(interval)
+            kinds.append(int(tm.kind)); u8.append(is_u8); factors.append(float(tm.factor))
+        self.device = self.a[0].device
+        ptrs = lambda ts: (C.c_void_p * n)(*[None if x is None else x.data_ptr() for x in ts])
+        self.c_kinds, self.c_u8 = (C.c_int * n)(*kinds), (C.c_int * n)(*u8)
+        self.c_dims, self.c_factors = (C.c_long * (5 * n))(*dims), (C.c_float * n)(*factors)
+        self.c_a, self.c_u, self.c_gt, self.c_mask, self.c_interval = (ptrs(x) for x in (self.a, self.u, self.gt, self.mask, self.interval))
+        self.kinds = kinds
+
+    def head(self):
+        """The arguments every loss export starts with."""
+        return (self.n, self.c_kinds, self.c_a, self.c_u, self.c_gt, self.c_mask, self.c_interval, self.c_u8, self.c_dims, self.c_factors)
+
+
+def loss_terms(terms):
+    """terms: a sequence of ``LossTerm`` (or a ``LossTable``) -> dict(loss fp32 0-dim = sum_t factor_t term_t, term fp32 [T], sums
+    fp64 [T,3] = (S_l, S_u, C), norm fp32 [T], table).  Two launches whatever T is, no host wait (pscv_loss_terms)."""
+    tab = terms if isinstance(terms, LossTable) else LossTable(terms)
+    nbytes = L.lib().pscv_loss_terms_workspace(tab.n, tab.c_dims)
+    L.check(0 if nbytes >= 0 else -1, "pscv_loss_terms_workspace")
+    ws = _workspace(tab.device, (nbytes + 3) // 4)
+    loss = torch.empty((), dtype=torch.float32, device=tab.device)
+    term = torch.empty((tab.n,), dtype=torch.float32, device=tab.device)
+    norm = torch.empty((tab.n,), dtype=torch.float32, device=tab.device)
+    sums = torch.empty((tab.n, 3), dtype=torch.float64, device=tab.device)
+    rc = _launch("loss_terms", lambda: L.lib().pscv_loss_terms(*tab.head(), _p(ws), _p(loss), _p(term), _p(sums), _p(norm), _stream()))
+    L.check(rc, "pscv_loss_terms")
+    return dict(loss=loss, term=term, sums=sums, norm=norm, table=tab)
+
+
+def loss_terms_bwd(table: LossTable, norm: torch.Tensor, grad_out: torch.Tensor, want_a: Sequence[bool], want_u: Sequence[bool]):
+    """Gradients of ``loss_terms``' scalar, one launch (pscv_loss_terms_bwd): ``grad_out`` fp32 0-dim / [1] on the device, ``norm``
+    from the forward; ``want_a[t]`` / ``want_u[t]`` say which are written -> ([d a_t or None], [d u_t or None])."""
+    _dev(norm, grad_out)
+    n = table.n
+    if norm.dtype != torch.float32 or norm.numel() != n or grad_out.dtype != torch.float32 or grad_out.numel() != 1:
+        raise ValueError("pscv.loss_terms_bwd: norm fp32 [T] and grad_out fp32 [1] expected")
+    has_u = [k in (L.LOSS_GT_BAYES, L.LOSS_L_BAYES) for k in table.kinds]
+    ga = [torch.empty_like(table.a[t]) if want_a[t] else None for t in range(n)]
+    gu = [torch.empty_like(table.u[t]) if (want_u[t] and has_u[t]) else None for t in range(n)]
+    if all(g is None for g in ga + gu):
+        return ga, gu
+    pa = (C.c_void_p * n)(*[_p(g) for g in ga])
+    pu = (C.c_void_p * n)(*[_p(g) for g in gu])
+    rc = _launch("loss_terms_bwd", lambda: L.lib().pscv_loss_terms_bwd(*table.head(), _p(norm), _p(grad_out), pa, pu, _stream()))
+    L.check(rc, "pscv_loss_terms_bwd")
+    return ga, gu
+
+
+def depth_metrics(est: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, step: Optional[torch.Tensor] = None, thresholds=(1, 3),
+                  rel_thresholds=()):
+    """The depth-map scores of models/utils.py:138-171 in one pass (pscv_depth_metrics): ``est`` [b,h,w] is upsampled bilinearly to
+    ``gt``'s [b,H,W], both are divided by ``step`` [b], a pixel counts where ``mask`` > 0.5 (bool: True).  -> dict of device tensors:
+    EPE, Rel, SqRel (0-dim), thres [len(thresholds)] = fraction with |e - g| > t, rel_thres [len(rel_thresholds)] = fraction with
+    max(e / g, g / e) <= r -- each the mean over the batch of the per-image value --, per_image (the same keys with a leading [b])
+    and sums fp64 [b,12] = (C, sum |e - g|, 4 counts, sum |e - g| / g, sum (e - g)^2 / g, 4 counts).  No host wait."""
+    thr, rel = [float(t) for t in thresholds], [float(t) for t in rel_thresholds]
+    MT, NS = L.METRIC_MAX_THRESH, L.METRIC_SUMS
+    if len(thr) > MT or len(rel) > MT:
+        raise L.PscvError(f"pscv.depth_metrics: {len(thr)} and {len(rel)} thresholds, at most {MT} of each")
+    if est.dim() < 3 or gt.dim() < 3:
+        raise ValueError("pscv.depth_metrics: est [b,h,w] and gt [b,H,W] expected")
+    est, gt = _f32c(est, "depth_metrics"), _f32c(gt, "depth_metrics")
+    mask, is_u8 = _mask_c(mask, "depth_metrics")
+    step = None if step is None else _f32c(step, "depth_metrics")
+    _dev(est, gt, mask, step)
+    b, (h, w), (H, W) = gt.shape[0], est.shape[-2:], gt.shape[-2:]
+    if est.numel() != b * h * w or gt.numel() != b * H * W or mask.numel() != gt.numel() or (step is not None and step.numel() != b):
+        raise ValueError(f"pscv.depth_metrics: shapes est {tuple(est.shape)}, gt {tuple(gt.shape)}, mask {tuple(mask.shape)} do not belong together")
+    nbytes = L.lib().pscv_depth_metrics_workspace(b, H, W)
+    L.check(0 if nbytes >= 0 else -1, "pscv_depth_metrics_workspace")
+    ws = _workspace(est.device, (nbytes + 3) // 4)
+    sums = torch.empty((b, NS), dtype=torch.float64, device=est.device)
+    means = torch.empty((b + 1, NS - 1), dtype=torch.float32, device=est.device)
+    ta, tr = (C.c_float * MT)(*thr), (C.c_float * MT)(*rel)
+    rc = _launch("depth_metrics", lambda: L.lib().pscv_depth_metrics(_p(est), _p(gt), _p(mask), is_u8, _p(step), b, h, w, H, W, ta, len(thr),
+                                                                     tr, len(rel), _p(ws), _p(sums), _p(means), _stream()))
+    L.check(rc, "pscv_depth_metrics")
+    pick = lambda m: dict(EPE=m[..., 0], thres=m[..., 1:1 + len(thr)], Rel=m[..., 1 + MT], SqRel=m[..., 2 + MT],
+                          rel_thres=m[..., 3 + MT:3 + MT + len(rel)])
+    out = pick(means[b])
+    out["per_image"] = pick(means[:b])
+    out["sums"] = sums
+    return out

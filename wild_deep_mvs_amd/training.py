@@ -916,3 +916,50 @@ class SSIMFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         img1, img2 = ctx.saved_tensors
         return None, ops.ssim_bwd(img1, img2, grad_out.contiguous())
+
+
+class LossTermsFn(torch.autograd.Function):
+    """The whole loss table of a training step as ONE autograd node (ops.loss_terms: two launches forward, one backward, no host
+    wait, no Python branch on a device value).  ``LossTermsFn.apply(terms, *tensors)``: ``terms`` is the sequence of
+    ``ops.LossTerm`` and ``tensors`` the ones autograd may want a gradient for, in table order -- per term its ``a`` (the depth map
+    or the per-pixel loss) and, for the Bayes kinds, its ``u`` (``loss_terms`` below builds the list).  Returns the scalar loss, the
+    per-term values [T] and the sums [T,3] (the last two carry no gradient)."""
+
+    @staticmethod
+    def forward(ctx, terms, *tensors):
+        table = ops.LossTable([ops.LossTerm(t.kind, t.factor, t.a.detach(), t.mask, None if t.u is None else t.u.detach(), t.gt, t.interval)
+                               for t in terms])
+        o = ops.loss_terms(table)
+        ctx.table = table
+        ctx.save_for_backward(o["norm"])
+        ctx.mark_non_differentiable(o["term"], o["sums"])
+        return o["loss"], o["term"], o["sums"]
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_term, _grad_sums):
+        table = ctx.table
+        (norm,) = ctx.saved_tensors
+        has_u = [k in (L.LOSS_GT_BAYES, L.LOSS_L_BAYES) for k in table.kinds]
+        need = iter(ctx.needs_input_grad[1:])
+        want_a, want_u = [], []
+        for t in range(table.n):
+            want_a.append(next(need))
+            want_u.append(next(need) if has_u[t] else False)
+        ga, gu = ops.loss_terms_bwd(table, norm, grad_loss.to(torch.float32).contiguous(), want_a, want_u)
+        grads = []
+        for t in range(table.n):
+            grads.append(ga[t])
+            if has_u[t]:
+                grads.append(gu[t])
+        return (None, *grads)
+
+
+def loss_terms(terms):
+    """sum_t factor_t term_t of a sequence of ``ops.LossTerm`` with autograd -> (loss 0-dim, term [T], sums [T,3])."""
+    terms = list(terms)
+    tensors = []
+    for t in terms:
+        tensors.append(t.a)
+        if t.kind in (L.LOSS_GT_BAYES, L.LOSS_L_BAYES):
+            tensors.append(t.u)
+    return LossTermsFn.apply(terms, *tensors)
