@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""CPU model of the LDS-staged warp kernel's box phase (csrc/warp_cost_tiled.hip): for both synthetic camera rigs at the headline size, the
+"""CPU model of the LDS-staged warp kernel's box phase (the rule itself: wl_box_of / wl_arena_alloc in csrc/warp_box.h, which
+scripts/dev/warp_box_check.cpp checks on the host; this script restates it): for both synthetic camera rigs at the headline size, the
 share of (tile, plane range, source view) triples whose source box does NOT fit (-> global taps, mode DIRECT) as a function of the planes
 per range (32 = whole chunk, 16 = halves, 8 = quarters), the widest box a staging wave covers and the arena size in texels; box sizes per view.
 Reproduces the kernel's own histogram (bench.py alt_geometry: 0.43 / 0.15 on the DTU-like rig at 32 / 16 planes).  python scripts/dev/warp_box_sim.py"""

@@ -136,6 +136,42 @@ def test_conv3d_cat2_and_fused_head_reject_before_any_launch():
     assert rc == -1 and "pscv_prob_softargmin: null pointer argument" in msg, (rc, msg)
 
 
+def _warp_cost_rc(n_src=2, srcs=None, ref=64, channels=32, hs=24, ws=32, geom=None, cost=None, in_dtype=None, out_dtype=None, ref_y0=0):
+    """pscv_warp_cost_rows with fake non-null pointers (never dereferenced on the host) -> (rc, error text)."""
+    lib = L.lib()
+    geom = L.GEOM_PROJ if geom is None else geom
+    cost = L.COST_VARIANCE if cost is None else cost
+    in_dtype = L.F16 if in_dtype is None else in_dtype
+    out_dtype = in_dtype if out_dtype is None else out_dtype
+    srcs = [64] * max(n_src, 1) if srcs is None else srcs
+    arr = (C.c_void_p * len(srcs))(*srcs)
+    rc = lib.pscv_warp_cost_rows(ref, C.cast(arr, C.POINTER(C.c_void_p)), n_src, 64, 64, 8, 0, geom, cost, 1.0, 64, 1, channels, 16, 24, hs, ws, 8,
+                                 in_dtype, out_dtype, ref_y0, None)
+    return rc, lib.pscv_last_error().decode()
+
+
+@pytest.mark.parametrize("kwargs, reasons", [
+    (dict(n_src=0), ("n_src=0 outside [1,%d]" % L.MAX_SRC,)),
+    (dict(n_src=L.MAX_SRC + 1), ("n_src=%d outside [1,%d]" % (L.MAX_SRC + 1, L.MAX_SRC),)),
+    (dict(n_src=3, srcs=[64, None, 64]), ("srcs[1] is null",)),
+    (dict(channels=12), ("C=12 must be a multiple of 8",)),
+    (dict(hs=1), ("bad sizes",)),
+    (dict(hs=4096, ws=4096), ("source map 4096x4096x32 too large",)),
+    (dict(cost=L.COST_VARIANCE_PARTIAL), ("partial sums are written in fp32",)),                       # PARTIAL with a 16-bit output
+    (dict(ref=None), ("ref is required for cost mode %d" % L.COST_VARIANCE,)),
+    (dict(ref_y0=-1), ("pscv_warp_cost_rows: ref_y0=-1",)),
+    (dict(geom=7), ("unknown geometry 7",)),
+    (dict(cost=L.COST_GROUPCORR), ("cost mode %d is not available with geometry %d" % (L.COST_GROUPCORR, L.GEOM_PROJ),)),
+    (dict(geom=L.GEOM_HOMOG, cost=L.COST_SOFTMIN), ("cost mode %d is not available with geometry %d" % (L.COST_SOFTMIN, L.GEOM_HOMOG),)),
+    (dict(in_dtype=L.F32, out_dtype=L.F16), ("unsupported dtype pair in=%d out=%d" % (L.F32, L.F16), "16-bit format or fp32")),
+])
+def test_warp_cost_rejects_before_any_launch(kwargs, reasons):
+    """The argument checks of pscv_warp_cost_rows and of the kernel families behind it (LDS-staged, quad, generic: each declines what
+    it does not cover, the last one names the reason) return -1 with the entry point and the reason, before any HIP call."""
+    rc, msg = _warp_cost_rc(**kwargs)
+    assert rc == -1 and "pscv_warp_cost" in msg and all(r in msg for r in reasons), (rc, msg)
+
+
 # ---- conv3d weight packing vs a numpy emulation of the kernel ------------------------------------
 def _bf16(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(torch.bfloat16).to(torch.float32).numpy()

@@ -391,9 +391,7 @@ extern "C" int pscv_bn_stats_grouped(const void* y, int dtype, long nvox, int gr
         }
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(finish_partials_kernel, dim3((2 * C + 15) / 16, groups), dim3(256), 0, st, workspace, nb, 2 * C, sums);
-    PSCV_CHECK_LAUNCH("pscv_bn_stats(finish)");
-    return 0;
+    return launch("pscv_bn_stats(finish)", finish_partials_kernel, dim3((2 * C + 15) / 16, groups), dim3(256), 0, st, workspace, nb, 2 * C, sums);
 }
 extern "C" int pscv_bn_stats(const void* y, int dtype, long nvox, int C, float* workspace, float* sums, void* stream) {
     return pscv_bn_stats_grouped(y, dtype, nvox, 1, C, workspace, sums, stream);
@@ -435,9 +433,7 @@ extern "C" int pscv_bn_bwd_reduce_grouped(const void* dact, const void* y, int d
         }
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(finish_partials_kernel, dim3((2 * C + 15) / 16, groups), dim3(256), 0, st, workspace, nb, 2 * C, sums);
-    PSCV_CHECK_LAUNCH("pscv_bn_bwd_reduce(finish)");
-    return 0;
+    return launch("pscv_bn_bwd_reduce(finish)", finish_partials_kernel, dim3((2 * C + 15) / 16, groups), dim3(256), 0, st, workspace, nb, 2 * C, sums);
 }
 extern "C" int pscv_bn_bwd_reduce(const void* dact, const void* y, int dtype, long nvox, int C, const float* scale,
                                   const float* bias, int relu, float* workspace, float* sums, void* stream) {
@@ -509,9 +505,7 @@ extern "C" int pscv_leaky_relu_bwd_sum(const void* dout, const void* out, int dt
         }
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(finish_partials_kernel, dim3((2 * C + 15) / 16, 1), dim3(256), 0, st, workspace, nb, 2 * C, sums);
-    PSCV_CHECK_LAUNCH("pscv_leaky_relu_bwd_sum(finish)");
-    return 0;
+    return launch("pscv_leaky_relu_bwd_sum(finish)", finish_partials_kernel, dim3((2 * C + 15) / 16, 1), dim3(256), 0, st, workspace, nb, 2 * C, sums);
 }
 extern "C" int pscv_relu_bwd(const void* dout, const void* out, int dtype, long nvox, int C, void* dpre, void* stream) {
     return pscv_leaky_relu_bwd(dout, out, dtype, nvox, C, 0.0f, dpre, stream);
@@ -523,10 +517,8 @@ extern "C" int pscv_bn_finalize_grouped(const float* sums, long nvox, int groups
     using namespace pscv;
     PSCV_CHECK_ARG(sums && out && nvox > 0 && C > 0 && C <= 1024 && groups >= 1, "pscv_bn_finalize: bad arguments");
     PSCV_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "pscv_bn_finalize: running_mean and running_var go together");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3((C + 63) / 64 * 64), 0, reinterpret_cast<hipStream_t>(stream), sums, (float)nvox,
-                       gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, C, groups);
-    PSCV_CHECK_LAUNCH("pscv_bn_finalize");
-    return 0;
+    return launch("pscv_bn_finalize", bn_finalize_kernel, dim3(1), dim3((C + 63) / 64 * 64), 0, reinterpret_cast<hipStream_t>(stream), sums, (float)nvox,
+                  gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked, out, C, groups);
 }
 extern "C" int pscv_bn_finalize(const float* sums, long nvox, int C, const float* gamma, const float* beta, float eps, float momentum,
                                 float* running_mean, float* running_var, long long* num_batches_tracked, float* out, void* stream) {
@@ -537,10 +529,8 @@ extern "C" int pscv_bn_bwd_coeffs_grouped(const float* sums, const float* mean, 
                                           long nvox, int groups, int C, float* out, void* stream) {
     using namespace pscv;
     PSCV_CHECK_ARG(sums && mean && invstd && out && nvox > 0 && C > 0 && C <= 1024 && groups >= 1, "pscv_bn_bwd_coeffs: bad arguments");
-    hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(groups), dim3((C + 63) / 64 * 64), 0, reinterpret_cast<hipStream_t>(stream), sums, mean, invstd,
-                       gamma, (float)nvox, out, C, stat_stride);
-    PSCV_CHECK_LAUNCH("pscv_bn_bwd_coeffs");
-    return 0;
+    return launch("pscv_bn_bwd_coeffs", bn_bwd_coeffs_kernel, dim3(groups), dim3((C + 63) / 64 * 64), 0, reinterpret_cast<hipStream_t>(stream), sums, mean, invstd,
+                  gamma, (float)nvox, out, C, stat_stride);
 }
 extern "C" int pscv_bn_bwd_coeffs(const float* sums, const float* mean, const float* invstd, const float* gamma, long nvox, int C,
                                   float* out, void* stream) {

@@ -1,6 +1,7 @@
 // Shared pieces of the plane-sweep warp kernels (warp_cost.hip: direct gather; warp_cost_tiled.hip: LDS-staged).
 #pragma once
 #include "pscv_common.h"
+#include "warp_box.h"
 
 namespace pscv {
 
@@ -25,6 +26,30 @@ struct WarpArgs {
                          // pixel coordinates it has in the whole image); 0 for whole-image launches
     int* mode_hist;      // development aid of the LDS-staged kernel (pscv_debug_wl_mode_hist): [view][mode] counters of its per-(block, view) staging modes; null = off
 };
+
+// ---- host side: one call descriptor, the kernel families behind pscv_warp_cost_rows ----
+struct WarpCall {
+    int C, geom, cost, in_dtype, out_dtype;
+    int ppd_override;    // "warp_ppd" (0: each kernel's own planes per block)
+    hipStream_t st;
+};
+// Each family: 0 = launched, 1 = this call is not covered (the caller tries the next family, the generic kernel last), negative =
+// error (set_error called).  pscv_warp_cost_rows has made the common declines before (16-bit pairs: out = in or fp32) and has set
+// a.variant / a.mode_hist; a try fills a.ppd / a.n_dchunks (/ a.npb_batch) for its own kernel only when it launches.
+int warp_cost_lv_try(WarpArgs& a, const WarpCall& c);      // lane-owns-voxel, variance costs ("warp_tiled" = 4; warp_cost_lv.hip)
+int warp_gc_lv_try(WarpArgs& a, const WarpCall& c);        // group-wise correlation, LDS-staged (warp_gc_lv.hip)
+int warp_cost_tiled_try(WarpArgs& a, const WarpCall& c);   // quad-owns-voxel, LDS-staged (warp_cost_tiled.hip)
+int warp_cost_q2_try(WarpArgs& a, const WarpCall& c);      // quad mapping, global taps (warp_cost_quad.hip)
+extern int* g_wl_mode_hist;   // pscv_debug_wl_mode_hist (warp_cost_tiled.hip; development aid, not thread-safe)
+
+// a.ppd / a.n_dchunks for `ppd` planes per workgroup (plan_planes, warp_box.h) and `units` workgroups per depth chunk; false if the
+// grid of nblk workgroups is empty or beyond 2^31 - 1 (the caller's error).
+inline bool plan_grid(WarpArgs& a, long units, int ppd, long& nblk) {
+    a.ppd = ppd;
+    a.n_dchunks = (a.D + ppd - 1) / ppd;
+    nblk = units * a.n_dchunks;
+    return nblk > 0 && nblk <= 0x7fffffffL;
+}
 
 template <int N> struct VecF { float v[N]; };
 

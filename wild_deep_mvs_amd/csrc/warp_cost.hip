@@ -235,13 +235,6 @@ __global__ __launch_bounds__(256, 4) void warp_cost_kernel(const WarpArgs a) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-int warp_cost_q2_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st);
-int warp_cost_tiled_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st);
-// the lane-owns-voxel kernel ("warp_tiled" = 4; warp_cost_lv.hip): variance costs
-int warp_cost_lv_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st);
-// group-wise correlation, LDS-staged (warp_gc_lv.hip)
-int warp_gc_lv_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st);
-
 // Instantiated (geometry, cost) pairs: the variance / softmin statistics belong to the PROJ models (MVSNet,
 // CVP), group-wise correlation to the HOMOG model (Vis); the plain warp exists for both.
 // dynamic LDS = the per-(view, pixel) ray terms; above the 64 KiB default (> 14 HOMOG views) launch() opts in
@@ -278,13 +271,9 @@ static int launch_geom(WarpArgs& a, int geom, int cost, hipStream_t st) {
     constexpr int PPB = 256 / LPV;
     a.npb_batch = (a.h * a.w + PPB - 1) / PPB;
     const long n_pixblocks = (long)a.npb_batch * a.B;
-    int ppd = g_warp_ppd_override > 0 ? g_warp_ppd_override : 8;
     // keep >= ~4096 blocks in flight for 256 CUs when the problem allows it
-    while (ppd > 1 && n_pixblocks * ((a.D + ppd - 1) / ppd) < 4096) ppd >>= 1;
-    a.ppd = ppd;
-    a.n_dchunks = (a.D + ppd - 1) / ppd;
-    const long nblk = n_pixblocks * a.n_dchunks;
-    if (nblk <= 0 || nblk > 0x7fffffffL) {
+    long nblk;
+    if (!plan_grid(a, n_pixblocks, plan_planes(n_pixblocks, a.D, g_warp_ppd_override, 8, 1, 4096, false, 0), nblk)) {
         set_error("pscv_warp_cost: bad grid size %ld", nblk);
         return -1;
     }
@@ -335,7 +324,6 @@ extern "C" int pscv_warp_cost_rows(const void* ref, const void* const* srcs, int
     // taps are addressed with 24-bit texel indices and 32-bit byte offsets inside one source image
     PSCV_CHECK_ARG((long)hs * ws < (1L << 24) && (long)hs * ws * C * 4 < (1L << 32), "pscv_warp_cost: source map %dx%dx%d too large", hs, ws, C);
     WarpArgs a;
-    a.mode_hist = nullptr;
     a.ref_y0 = ref_y0;
     a.ref = ref;
     for (int i = 0; i < PSCV_MAX_SRC; ++i) a.src[i] = i < n_src ? srcs[i] : nullptr;
@@ -347,7 +335,8 @@ extern "C" int pscv_warp_cost_rows(const void* ref, const void* const* srcs, int
     a.n_src = n_src; a.B = B; a.h = h; a.w = w; a.hs = hs; a.ws = ws; a.D = D;
     a.depth_per_pixel = depth_per_pixel;
     a.temp = temp;
-    a.variant = 0;
+    a.variant = g_warp_tile;           // (read by the LDS-staged kernels only, like mode_hist)
+    a.mode_hist = g_wl_mode_hist;
     const long vol = (long)B * D * h * w;
     a.out_view_stride = cost == PSCV_COST_GROUPCORR ? vol * (C / 4) : vol * C;   // (PARTIAL: offset of the sum-of-squares half)
     if (geom == PSCV_GEOM_PROJ) {
@@ -362,21 +351,19 @@ extern "C" int pscv_warp_cost_rows(const void* ref, const void* const* srcs, int
         a.xlo = -0.05f * (ws - 1); a.xhi = 1.05f * (ws - 1);
         a.ylo = -0.05f * (hs - 1); a.yhi = 1.05f * (hs - 1);
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    int rc;
-    if (g_warp_tiled && g_warp_lpv_override == 0 && cost != PSCV_COST_VARIANCE_PARTIAL) {
-        rc = 1;
-        if (g_warp_tiled == 4) rc = warp_cost_lv_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
-        if (rc == 1 && g_warp_gc_lds && (g_warp_gc_lds >= 2 || !depth_per_pixel)) rc = warp_gc_lv_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
-        if (rc == 1)
-            rc = warp_cost_tiled_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
-        if (rc <= 0) return rc;
+    const WarpCall c{C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, reinterpret_cast<hipStream_t>(stream)};
+    // what every specialised kernel needs: 32 channels in a 16-bit format, the output in the same format or fp32
+    const bool special = C == 32 && (in_dtype == PSCV_F16 || in_dtype == PSCV_BF16) && (out_dtype == in_dtype || out_dtype == PSCV_F32) &&
+                         g_warp_lpv_override == 0;
+    int rc = 1;
+    if (special && g_warp_tiled && cost != PSCV_COST_VARIANCE_PARTIAL) {
+        if (g_warp_tiled == 4) rc = warp_cost_lv_try(a, c);
+        if (rc == 1 && g_warp_gc_lds && (g_warp_gc_lds >= 2 || !depth_per_pixel)) rc = warp_gc_lv_try(a, c);
+        if (rc == 1) rc = warp_cost_tiled_try(a, c);
     }
-    if (g_warp_q2 && g_warp_lpv_override == 0) {
-        rc = warp_cost_q2_try(a, C, geom, cost, in_dtype, out_dtype, g_warp_ppd_override, st);
-        if (rc <= 0) return rc;
-    }
+    if (rc == 1 && special && g_warp_q2) rc = warp_cost_q2_try(a, c);
+    if (rc <= 0) return rc;
     return with_warp_types<true>("pscv_warp_cost", in_dtype, out_dtype, [&](auto ti, auto to) {
-        return launch_channels<typename decltype(ti)::type, typename decltype(to)::type>(a, C, geom, cost, st);
+        return launch_channels<typename decltype(ti)::type, typename decltype(to)::type>(a, C, geom, cost, c.st);
     });
 }

@@ -64,17 +64,12 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     static_assert(COST == PSCV_COST_VARIANCE || COST == PSCV_COST_VARIANCE_CVP, "variance costs");
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
 
-    const int dc = blockIdx.y;
     int b, tyi, txi;
     if (!wl_tile_decode<LV_T, LV_TH>(a, b, tyi, txi)) return;
-
-    __builtin_amdgcn_s_setprio(3);                                   // box / staging phase ahead of the other blocks' sweeps
-    __builtin_amdgcn_s_setreg((1 - 1) << 11 | 23 << 6 | 1, 1);       // MODE.FP16_OVFL: saturating f32 -> f16 stores
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int x0t = txi * LV_T, y0t = tyi * LV_TH;
-    const int d0 = dc * a.ppd, d1 = min(a.D, d0 + a.ppd);
-    const float* const depth_b = a.depth + (long)b * a.depth_bstride;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const WlBlock blk = wl_block_prologue<LV_T, LV_TH>(a, b, tyi, txi);
+    const int x0t = blk.x0t, y0t = blk.y0t, d0 = blk.d0, d1 = blk.d1;
+    const float* const depth_b = blk.depth_b;
     const int n_src = a.n_src;
     int* const table = reinterpret_cast<int*>(lsm + LV_TABLE);
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lsm;   // LDS byte address of the arena
@@ -89,22 +84,14 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     const int hw = a.h * a.w;
     const int pflat = y * a.w + x;
     const float px = (float)x, py = (float)(y + a.ref_y0);
-    float rf[C];
-    {
-        const TIn* rp = reinterpret_cast<const TIn*>(a.ref) + ((long)b * hw + pflat) * C;
-#pragma unroll
-        for (int k = 0; k < C / 8; ++k) {
-            const f32x8 t = Elem<TIn>::load8(rp + 8 * k);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rf[8 * k + i] = t.v[i];
-        }
-    }
+    VecF<C> rfv = load_chan<TIn, C>(reinterpret_cast<const TIn*>(a.ref) + ((long)b * hw + pflat) * C);
+    float (&rf)[C] = rfv.v;
 
     // ---- 1. wave k: texel boxes of source view k from the 8 corner projections (see warp_cost_tiled.hip for the argument): the box of
     //         the whole chunk (lanes 0-7), of its first half (lanes 8-15) and of its second half (lanes 16-23) -- round 5: a block in
     //         which some view's whole-chunk box does not fit sweeps the two halves one after the other instead of its general path ----
     const int nplanes = d1 - d0;
-    const int hsz = nplanes >= 4 ? ((nplanes / 2 + 1) & ~1) : nplanes;        // planes of the first half (even); no split below 4 planes
+    const int hsz = wl_split_size(nplanes);                                   // planes of the first half
     if (wave < WL_MAX_SRC) {
         const int k = wave;
         const float inf = __builtin_inff();
@@ -115,44 +102,16 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
         const float dmin0 = fminf(dmin1, dmin2), dmax0 = fmaxf(dmax1, dmax2);
         const int set = min(lane >> 3, 2);
         const int corner = lane & 7;
-        const float cx = (corner & 1) ? (float)min(x0t + LV_T - 1, a.w - 1) : (float)x0t;
-        const float cy = (float)(((corner & 2) ? min(y0t + LV_TH - 1, a.h - 1) : y0t) + a.ref_y0);
         const float dlo = set == 0 ? dmin0 : set == 1 ? dmin1 : dmin2, dhi = set == 0 ? dmax0 : set == 1 ? dmax1 : dmax2;
-        const float d = (corner & 4) ? dhi : dlo;
-        int cX0 = 0, cY0 = 0, cX1 = 1, cY1 = 1, pitch = 2, mode = WL_ZERO;      // mode: WL_FAST / WL_GEN here = "if the arena has room"
+        float cx, cy;
+        wl_tile_corner<LV_T, LV_TH, PSCV_GEOM_PROJ>(a, blk, corner, cx, cy);
+        WlBox box = wl_box_none(WL_BOX_LANE, WL_ZERO);      // (no such view)
         if (k < n_src) {
-            lv_cf cam = (lv_cf)(a.cams + ((long)k * a.B + b) * PSCV_CAM_FLOATS);
-            const float ax = fmaf(cam[1], cy, cam[0] * cx) + cam[2];
-            const float ay = fmaf(cam[4], cy, cam[3] * cx) + cam[5];
-            const float az = fmaf(cam[7], cy, cam[6] * cx) + cam[8];
-            const float hx = fmaf(ax, d, cam[9]), hy = fmaf(ay, d, cam[10]), hz = fmaf(az, d, cam[11]);
-            const float inv_z = __builtin_amdgcn_rcpf(hz);
-            const float u = hx * inv_z, v = hy * inv_z;
-            const float okf = (hz > 1e-6f && fabsf(u) < 1e6f && fabsf(v) < 1e6f) ? 1.0f : 0.0f;   // also rejects NaN
-            const float umin = wl_reduce8<false>(u), umax = wl_reduce8<true>(u);               // (per 8-lane group = per plane range)
-            const float vmin = wl_reduce8<false>(v), vmax = wl_reduce8<true>(v);
-            const bool ok = wl_reduce8<false>(okf) != 0.0f;
-            const float sl = 1.0f / 32.0f;     // slack for the per-pixel evaluation's different rounding (maps <= 16384 texels)
-            const int X0 = (int)floorf(umin - sl), X1 = (int)floorf(umax + sl) + 1;
-            const int Y0 = (int)floorf(vmin - sl), Y1 = (int)floorf(vmax + sl) + 1;
-            mode = WL_DIRECT;
-            if (ok) {
-                const bool outside = X1 < 0 || Y1 < 0 || X0 > a.ws - 1 || Y0 > a.hs - 1;
-                const bool inside = X0 >= 0 && Y0 >= 0 && X1 <= a.ws - 1 && Y1 <= a.hs - 1;
-                // the staged box carries two texels of zero padding beyond each clipped border: a sample whose top-left tap
-                // lies further out is clamped onto the padding, where both its taps of that axis are zero (module.py:160-166)
-                cX0 = max(X0, -2); cX1 = min(X1, a.ws + 1); cY0 = max(Y0, -2); cY1 = min(Y1, a.hs + 1);
-                const int bw = cX1 - cX0 + 1, bh = cY1 - cY0 + 1;
-                pitch = bw;                    // (no padding of the rows: the lanes of an LDS pass read along ONE box row)
-                if (outside) mode = WL_ZERO;
-                else if (bw <= LV_BOX_W && bh <= LV_BOX_H) mode = inside ? WL_FAST : WL_GEN;
-            }
+            float u, v, okf;
+            wl_corner_uv<PSCV_GEOM_PROJ>((wl_cf)(a.cams + ((long)k * a.B + b) * PSCV_CAM_FLOATS), cx, cy, (corner & 4) ? dhi : dlo, a, u, v, okf);
+            box = wl_corner_box<false>(u, v, okf, a, WL_BOX_LANE);
         }
-        if (corner == 0 && lane < 24) {
-            int4* row = reinterpret_cast<int4*>(table + (set * WL_MAX_SRC + k) * 8);
-            row[0] = make_int4(cX0, cY0, cX1, cY1);
-            row[1] = make_int4(0, pitch, mode, 0);
-        }
+        if (corner == 0 && lane < 24) wl_record_write<LV_REC>(table, set * WL_MAX_SRC + k, box);
     }
     __syncthreads();
 
@@ -166,17 +125,13 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
         bool direct = false;
 #pragma unroll
         for (int k = 0; k < WL_MAX_SRC; ++k) {
-            const int4 r0 = *reinterpret_cast<const int4*>(table + k * 8), r1 = *reinterpret_cast<const int4*>(table + k * 8 + 4);
-            int mode = k < n_src ? __builtin_amdgcn_readfirstlane(r1.z) : WL_ZERO;
-            const int need = __builtin_amdgcn_readfirstlane(r1.y) * (__builtin_amdgcn_readfirstlane(r0.w) - __builtin_amdgcn_readfirstlane(r0.y) + 1);
-            if ((mode == WL_FAST || mode == WL_GEN) && used + need > LV_ARENA) mode = WL_DIRECT;
-            if (mode == WL_FAST || mode == WL_GEN) used += need;
-            direct = direct || mode == WL_DIRECT;
+            const WlBox r = wl_record_read<LV_REC>(table, k);
+            direct = direct || wl_arena_take(k < n_src ? r.mode : WL_ZERO, wl_box_texels(r), used, LV_ARENA) == WL_DIRECT;
         }
         if (direct) nsub = 2;
     }
     for (int sub = 0; sub < nsub; ++sub) {
-    const int tset = (nsub == 2 ? 1 + sub : 0) * WL_MAX_SRC * 8;          // this plane range's records in the table (ints)
+    const int rset = (nsub == 2 ? 1 + sub : 0) * WL_MAX_SRC;              // this plane range's records in the table
     const int s0 = d0 + (nsub == 2 && sub ? hsz : 0), s1 = nsub == 2 && !sub ? d0 + hsz : d1;
     if (sub) {
         __syncthreads();                                 // the first half's sweep is done with the arena
@@ -192,15 +147,11 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
         int used = 0;
 #pragma unroll
         for (int k = 0; k < WL_MAX_SRC; ++k) {
-            const int4 r0 = *reinterpret_cast<const int4*>(table + tset + k * 8), r1 = *reinterpret_cast<const int4*>(table + tset + k * 8 + 4);
-            const int X0 = __builtin_amdgcn_readfirstlane(r0.x), Y0 = __builtin_amdgcn_readfirstlane(r0.y);
-            const int Y1 = __builtin_amdgcn_readfirstlane(r0.w);
-            bP[k] = __builtin_amdgcn_readfirstlane(r1.y);
-            int mode = k < n_src ? __builtin_amdgcn_readfirstlane(r1.z) : WL_ZERO;
-            const int need = bP[k] * (Y1 - Y0 + 1);
-            if ((mode == WL_FAST || mode == WL_GEN) && used + need > LV_ARENA) mode = WL_DIRECT;
+            const WlBox r = wl_record_read<LV_REC>(table, rset + k);
+            const int X0 = r.X0, Y0 = r.Y0;
+            bP[k] = r.pitch;
             bBase[k] = used;
-            if (mode == WL_FAST || mode == WL_GEN) used += need;
+            const int mode = wl_arena_take(k < n_src ? r.mode : WL_ZERO, wl_box_texels(r), used, LV_ARENA);
             bMode[k] = mode;
             if (a.mode_hist && k < n_src && tid == 0) atomicAdd(a.mode_hist + k * 4 + mode, 1);
             bE0[k] = ((bBase[k] - Y0 * bP[k] - X0) << 4) + (int)lds0;      // LDS byte address of texel (x, y), chunk 0 = (y * pitch + x) * 16 + bE0
@@ -218,9 +169,8 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     // ---- 3. stage the boxes, 16-bit -> fp32, channel-chunk planar: wave k stages view k ----
     {
         const int k = wave;
-        const int4 f0 = *reinterpret_cast<const int4*>(table + tset + k * 8);
-        const int sX0 = __builtin_amdgcn_readfirstlane(f0.x), sY0 = __builtin_amdgcn_readfirstlane(f0.y);
-        const int sX1 = __builtin_amdgcn_readfirstlane(f0.z), sY1 = __builtin_amdgcn_readfirstlane(f0.w);
+        const WlBox f = wl_record_read<LV_REC>(table, rset + k);
+        const int sX0 = f.X0, sY0 = f.Y0, sX1 = f.X1, sY1 = f.Y1;
         int sP16 = bP[0] << 4, sMode = bMode[0], sBase = bBase[0];
 #pragma unroll
         for (int t = 1; t < WL_MAX_SRC; ++t)
@@ -230,41 +180,7 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
 #pragma unroll
         for (int t = 1; t < WL_MAX_SRC; ++t)
             if (k == t) srcp = a.src[t];
-        if (k < n_src && (sMode == WL_FAST || sMode == WL_GEN)) {
-            const int bw = sX1 - sX0 + 1, bh = sY1 - sY0 + 1;              // bw <= 32, bh <= 16
-            const long rstride = (long)a.ws * C;
-            // a batch = 8 rows x 16 texels (a lane = one 16-byte piece of a row: texel lane >> 2, channels 8 (lane & 3) ..), loads first
-            for (int yh = 0; yh < bh; yh += 8) {
-                for (int xh = 0; xh < bw; xh += 16) {
-                    const int cw = min(bw - xh, 16), ch = min(bh - yh, 8);
-                    const int cl = min(lane, cw * 4 - 1);
-                    const bool mine = lane < cw * 4;
-                    const int gx = sX0 + xh + (cl >> 2);
-                    const bool vx = (unsigned)gx < (unsigned)a.ws;
-                    const TIn* col = reinterpret_cast<const TIn*>(srcp) + ((long)b * a.hs * a.ws + min(max(gx, 0), a.ws - 1)) * C + (cl & 3) * 8;
-                    const int dst0 = gx * 16 + sBase + (cl & 3) * 2 * LV_PLANE;
-                    uint4 val[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const int gy = min(max(sY0 + yh + min(i, ch - 1), 0), a.hs - 1);
-                        val[i] = *reinterpret_cast<const uint4*>(col + gy * rstride);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        if (mine && i < ch) {
-                            const bool v = vx && (unsigned)(sY0 + yh + i) < (unsigned)a.hs;
-                            const uint4 u = val[i];
-                            float4 lo = make_float4(Half16<TIn>::lo(u.x), Half16<TIn>::hi(u.x), Half16<TIn>::lo(u.y), Half16<TIn>::hi(u.y));
-                            float4 hi = make_float4(Half16<TIn>::lo(u.z), Half16<TIn>::hi(u.z), Half16<TIn>::lo(u.w), Half16<TIn>::hi(u.w));
-                            if (!v) { lo = make_float4(0.0f, 0.0f, 0.0f, 0.0f); hi = lo; }
-                            const int dst = dst0 + (sY0 + yh + i) * sP16;
-                            *reinterpret_cast<float4*>(lsm + dst) = lo;
-                            *reinterpret_cast<float4*>(lsm + dst + LV_PLANE) = hi;
-                        }
-                    }
-                }
-            }
-        }
+        if (k < n_src && wl_staged(sMode)) lv_stage_box<TIn>(lsm, srcp, b, a.hs, a.ws, lane, sX0, sY0, sX1, sY1, sP16, sBase);
     }
 
     // depth-independent ray terms rot (x, y, 1) of this pixel: per slot (fast path) -- module.py:138-144
@@ -369,7 +285,7 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
                     w[jj][0] = gx * gy; w[jj][1] = fx * gy; w[jj][2] = gx * fy; w[jj][3] = fx * fy;
                     int x0 = (int)x0f, y0 = (int)y0f;
                     if (sGen[jj]) {      // top-left tap into the box (with its zero padding); the sample may lie anywhere
-                        const int4 r0 = *reinterpret_cast<const int4*>(table + tset + sView[jj] * 8);
+                        const int4 r0 = *reinterpret_cast<const int4*>(table + (rset + sView[jj]) * 8);
                         x0 = med3_i32(x0, r0.x, r0.z - 1); y0 = med3_i32(y0, r0.y, r0.w - 1);
                     }
                     aT[jj] = (unsigned)((__mul24(y0, sP[jj]) + x0) * 16 + sE0[jj]);
@@ -451,7 +367,7 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
                         const float fx = ix - x0f, fy = iy - y0f;
                         const float gx = 1.0f - fx, gy = 1.0f - fy;
                         ww[0] = gx * gy; ww[1] = fx * gy; ww[2] = gx * fy; ww[3] = fx * fy;
-                        const int4 r0 = *reinterpret_cast<const int4*>(table + tset + k * 8);
+                        const int4 r0 = *reinterpret_cast<const int4*>(table + (rset + k) * 8);
                         const int x0 = med3_i32((int)x0f, r0.x, r0.z - 1), y0 = med3_i32((int)y0f, r0.y, r0.w - 1);   // (no-op for boxes inside the image)
                         const unsigned at = (unsigned)((__mul24(y0, P) + x0) * 16 + E0 + c * LV_PLANE);
                         const unsigned ab = at + (unsigned)(P << 4);
@@ -511,21 +427,14 @@ static int lv_dispatch(const WarpArgs& a, int cost, dim3 grid, hipStream_t st) {
     return 1;
 }
 
-extern int* g_wl_mode_hist;   // warp_cost_tiled.hip (pscv_debug_wl_mode_hist)
-
-// Returns 0 if launched, 1 if this configuration is not covered (the caller tries the quad-owner kernel next), negative on error.
-int warp_cost_lv_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (a.depth_per_pixel || geom != PSCV_GEOM_PROJ) return 1;
-    if (cost != PSCV_COST_VARIANCE && cost != PSCV_COST_VARIANCE_CVP) return 1;
-    if (out_dtype != in_dtype && out_dtype != PSCV_F32) return 1;
-    if (a.n_src < 1 || a.n_src > WL_MAX_SRC) return 1;
+int warp_cost_lv_try(WarpArgs& a, const WarpCall& c) {
+    if (a.depth_per_pixel || c.geom != PSCV_GEOM_PROJ || a.n_src > WL_MAX_SRC) return 1;
+    if (c.cost != PSCV_COST_VARIANCE && c.cost != PSCV_COST_VARIANCE_CVP) return 1;
     dim3 grid;
-    const int rc = wl_plan("pscv_warp_cost(lv)", a, C, in_dtype, LV_T, LV_TH, ppd_override, 32, 64, grid);
+    const int rc = wl_plan("pscv_warp_cost(lv)", a, c, LV_T, LV_TH, 32, 64, grid);
     if (rc) return rc;
-    a.mode_hist = g_wl_mode_hist;
-    a.variant = g_warp_tile;
-    return with_warp_types<false>("pscv_warp_cost(lv)", in_dtype, out_dtype, [&](auto ti, auto to) {
-        return lv_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, cost, grid, st);
+    return with_warp_types<false>("pscv_warp_cost(lv)", c.in_dtype, c.out_dtype, [&](auto ti, auto to) {
+        return lv_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, c.cost, grid, c.st);
     });
 }
 

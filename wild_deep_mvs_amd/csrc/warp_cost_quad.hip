@@ -26,6 +26,7 @@ namespace pscv {
 
 typedef float q2_f2 __attribute__((ext_vector_type(2)));
 
+// (not wl_dpp_f / wl_dpp_i of warp_lds.h: those are v_mov_b32_dpp with bound_ctrl, another encoding, and this kernel's bits anchor the tests)
 template <int CTRL> __device__ __forceinline__ float dpp_f(float x) {
     // (old = src: every lane is written, and the compiler need not materialise a separate "old" register)
     const int xi = __builtin_bit_cast(int, x);
@@ -67,6 +68,7 @@ __device__ __forceinline__ void q2_mix8(const uint4 (&t)[4], const float (&w)[4]
     }
 }
 
+// (not wl_store8: that packs fp16 without the v_med3_f32 clamp, under the MODE.FP16_OVFL bit this kernel does not set)
 template <typename TOut> __device__ __forceinline__ void q2_store8(char* p, const float (&o)[8]) {
     if constexpr (sizeof(TOut) == 4) {
         *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
@@ -354,20 +356,13 @@ static int q2_dispatch(const WarpArgs& a, int geom, int cost, int nblk, hipStrea
     return 1;
 }
 
-// Returns 0 if launched, 1 if this configuration is not covered (the caller uses the generic kernel), < 0 on error.
-int warp_cost_q2_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (C != 32 || (in_dtype != PSCV_F16 && in_dtype != PSCV_BF16)) return 1;
-    if (out_dtype != in_dtype && out_dtype != PSCV_F32) return 1;
+int warp_cost_q2_try(WarpArgs& a, const WarpCall& c) {
     a.npb_batch = (a.h * a.w + 63) / 64;
     const long n_pixblocks = (long)a.npb_batch * a.B;
-    int ppd = ppd_override > 0 ? ((ppd_override + 1) & ~1) : 8;
-    while (ppd > 2 && n_pixblocks * ((a.D + ppd - 1) / ppd) < 4096) ppd >>= 1;
-    a.ppd = ppd;
-    a.n_dchunks = (a.D + ppd - 1) / ppd;
-    const long nblk = n_pixblocks * a.n_dchunks;
-    if (nblk <= 0 || nblk > 0x7fffffffL) { set_error("pscv_warp_cost(q2): bad grid %ld", nblk); return -1; }
-    return with_warp_types<false>("pscv_warp_cost(q2)", in_dtype, out_dtype, [&](auto ti, auto to) {
-        return q2_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, geom, cost, (int)nblk, st);
+    long nblk;
+    if (!plan_grid(a, n_pixblocks, plan_planes(n_pixblocks, a.D, c.ppd_override, 8, 2, 4096, true, 0), nblk)) { set_error("pscv_warp_cost(q2): bad grid %ld", nblk); return -1; }
+    return with_warp_types<false>("pscv_warp_cost(q2)", c.in_dtype, c.out_dtype, [&](auto ti, auto to) {
+        return q2_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, c.geom, c.cost, (int)nblk, c.st);
     });
 }
 

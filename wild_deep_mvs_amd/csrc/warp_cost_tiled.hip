@@ -51,21 +51,14 @@
 // emits that form for the blend below.  scripts/lint_isa.py keeps the form out of the library.
 namespace pscv {
 
-#ifndef WL_TILE_H
-#define WL_TILE_H 4
-#endif
-constexpr int WL_T = 8;                      // tile width in reference pixels
-constexpr int WL_TH = WL_TILE_H;             // tile height: 8 (512 threads, two workgroups per CU) or 4 (256 threads, four per CU)
+constexpr int WL_T = 8;                      // tile width in reference pixels (height WL_TH, arena WL_ARENA, largest box: warp_box.h)
 constexpr int WL_THREADS = 64 * WL_TH;       // a wave = 2 tile rows x 8 pixels; (WL_TH / 2) pixel groups x 2 plane parities
 constexpr int WL_PG = WL_TH / 2;             // pixel groups (waves per plane parity)
-constexpr int WL_ARENA = WL_TH == 8 ? 636 : 316;   // staged texels per block (all views): 80 / 40 KiB of fp32
 constexpr int WL_HI = WL_ARENA * 64;         // byte offset of the "hi" channel plane
-constexpr int WL_STAGE_ROWS = 8;             // box rows one wave stages (one load batch)
-constexpr int WL_BOX_H = WL_STAGE_ROWS * (WL_THREADS / 64 / WL_MAX_SRC);   // tallest box the staging phase covers: 8 (4-row tile) / 16
 constexpr int WL_NSETS = 7;                  // plane ranges with their own boxes: the whole chunk, its two halves (round 5), its four quarters (round 6)
-constexpr int WL_TABLE = 2 * WL_HI;          // box records (16 B: X0 | Y0, X1 | Y1, pitch | mode as 16-bit pairs), [7 plane ranges][4 views]:
-                                             // range 0 = the whole chunk, 1 / 2 = its first / second half, 3..6 = the quarters (adaptive split)
-constexpr int WL_LDS = WL_TABLE + WL_NSETS * WL_MAX_SRC * 16 + 32;
+constexpr int WL_REC = WL_BOX_QUAD.rec_bytes; // box records (warp_lds.h), [7 plane ranges][4 views]:
+constexpr int WL_TABLE = 2 * WL_HI;          // range 0 = the whole chunk, 1 / 2 = its first / second half, 3..6 = the quarters (adaptive split)
+constexpr int WL_LDS = WL_TABLE + WL_NSETS * WL_MAX_SRC * WL_REC + 32;
 static_assert(WL_LDS <= (WL_TH == 8 ? 81920 : 40960), "two / four blocks per CU");
 
 
@@ -106,20 +99,12 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
     static_assert(GEOM == PSCV_GEOM_PROJ, "PROJ geometry (three depth-independent ray terms per (view, pixel))");
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
 
-    const int dc = blockIdx.y;
     int b, tyi, txi;
     if (!wl_tile_decode<WL_T, WL_TH>(a, b, tyi, txi)) return;
-
-    // the box / staging phase of a new workgroup runs at raised priority: the (older) waves of the CU's other workgroup are in
-    // their vector-ALU-bound sweep and would otherwise win every issue slot (arbitration is priority, then age), stretching
-    // this short phase -- and with it the time the CU runs on one workgroup's waves only -- to ~25 000 cycles
-    __builtin_amdgcn_s_setprio(3);
-    __builtin_amdgcn_s_setreg((1 - 1) << 11 | 23 << 6 | 1, 1);     // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL: saturating f32 -> f16 stores
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int x0t = txi * WL_T, y0t = tyi * WL_TH;
-    const int d0 = dc * a.ppd, d1 = min(a.D, d0 + a.ppd);
-    const float* const depth_b = a.depth + (long)b * a.depth_bstride;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const WlBlock blk = wl_block_prologue<WL_T, WL_TH>(a, b, tyi, txi);
+    const int x0t = blk.x0t, y0t = blk.y0t, d0 = blk.d0, d1 = blk.d1;
+    const float* const depth_b = blk.depth_b;
     const int n_src = a.n_src;
     int* const table = reinterpret_cast<int*>(lsm + WL_TABLE);
 
@@ -170,9 +155,8 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
     // widest-baseline view still took global taps (boxes 15-18 texels wide, or no room left in the arena); 8-plane ranges fit in
     // 98 % of the cases (profiles/r06_warp_quarter_split.txt), so a half in which some view would take global taps is swept as its two quarters.
     const int nplanes = d1 - d0;
-    auto split_size = [](int m) { return m >= 4 ? ((m / 2 + 1) & ~1) : m; };     // planes of the first part (even); no split below 4 planes
-    const int hsz = split_size(nplanes);                         // first half: [0, hsz)
-    const int q0 = split_size(hsz), q2 = split_size(nplanes - hsz);   // first quarter of each half: [0, q0), [hsz, hsz + q2)
+    const int hsz = wl_split_size(nplanes);                      // first half: [0, hsz)
+    const int q0 = wl_split_size(hsz), q2 = wl_split_size(nplanes - hsz);   // first quarter of each half: [0, q0), [hsz, hsz + q2)
     if (wave < WL_MAX_SRC) {      // wave k: the boxes of source view k
         const int k = wave;
         // (depth ranges: wave reductions of the per-lane planes over the four quarters; planes need not be monotone.  Lanes beyond the
@@ -188,47 +172,17 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
         const float dmin0 = fminf(dmin1, dmin2), dmax0 = fmaxf(dmax1, dmax2);
         const int set = min(lane >> 3, WL_NSETS - 1);
         const int corner = lane & 7;
-        const float cx = (corner & 1) ? (float)min(x0t + WL_T - 1, a.w - 1) : (float)x0t;
-        const float cy = (float)(((corner & 2) ? min(y0t + WL_TH - 1, a.h - 1) : y0t) + a.ref_y0);
         const float dlo = set == 0 ? dmin0 : set == 1 ? dmin1 : set == 2 ? dmin2 : set == 3 ? qmin0 : set == 4 ? qmin1 : set == 5 ? qmin2 : qmin3;
         const float dhi = set == 0 ? dmax0 : set == 1 ? dmax1 : set == 2 ? dmax2 : set == 3 ? qmax0 : set == 4 ? qmax1 : set == 5 ? qmax2 : qmax3;
-        const float d = (corner & 4) ? dhi : dlo;
-        int cX0 = 0, cY0 = 0, cX1 = -1, cY1 = -1, pitch = 4, mode = WL_ZERO;      // mode: WL_FAST / WL_GEN here = "if the arena has room"
+        float cx, cy;
+        wl_tile_corner<WL_T, WL_TH, GEOM>(a, blk, corner, cx, cy);
+        WlBox box = wl_box_none(WL_BOX_QUAD, WL_ZERO);      // (no such view)
         if (k < n_src) {
-            typedef const __attribute__((address_space(4))) float* wl_cf;
-            wl_cf cam = (wl_cf)(a.cams + ((long)k * a.B + b) * PSCV_CAM_FLOATS);
-            const float ax = fmaf(cam[1], cy, cam[0] * cx) + cam[2];
-            const float ay = fmaf(cam[4], cy, cam[3] * cx) + cam[5];
-            const float az = fmaf(cam[7], cy, cam[6] * cx) + cam[8];
-            const float hx = fmaf(ax, d, cam[9]), hy = fmaf(ay, d, cam[10]), hz = fmaf(az, d, cam[11]);
-            const float inv_z = __builtin_amdgcn_rcpf(hz);
-            const float u = hx * inv_z, v = hy * inv_z;
-            const float okf = (hz > 1e-6f && fabsf(u) < 1e6f && fabsf(v) < 1e6f) ? 1.0f : 0.0f;   // also rejects NaN
-            // (per 8-lane group = per plane range; every lane of a group holds the group's result)
-            const float umin = wl_reduce8<false>(u), umax = wl_reduce8<true>(u);
-            const float vmin = wl_reduce8<false>(v), vmax = wl_reduce8<true>(v);
-            const bool ok = wl_reduce8<false>(okf) != 0.0f;
-            // slack of 1/32 texel: the per-pixel fp32 evaluation (different rounding, 1-ulp rcp on both sides) differs
-            // from the corners' by < 2e-6 relative, i.e. < 1/32 for maps up to 16384 texels wide (larger ones are refused)
-            const float sl = 1.0f / 32.0f;
-            const int X0 = (int)floorf(umin - sl), X1 = (int)floorf(umax + sl) + 1;
-            const int Y0 = (int)floorf(vmin - sl), Y1 = (int)floorf(vmax + sl) + 1;
-            mode = WL_DIRECT;
-            if (ok) {
-                const bool outside = X1 < 0 || Y1 < 0 || X0 > a.ws - 1 || Y0 > a.hs - 1;
-                const bool inside = X0 >= 0 && Y0 >= 0 && X1 <= a.ws - 1 && Y1 <= a.hs - 1;
-                cX0 = max(X0, 0); cX1 = min(X1, a.ws - 1); cY0 = max(Y0, 0); cY1 = min(Y1, a.hs - 1);
-                const int bw = cX1 - cX0 + 1, bh = cY1 - cY0 + 1;
-                pitch = (bw + 3) & ~3;   // a multiple of 4: the quads of a ds_read_b128 lane group stay conflict-free across rows
-                if (outside) { mode = WL_ZERO; cX0 = 0; cY0 = 0; cX1 = -1; cY1 = -1; pitch = 4; }
-                else if (bw <= 16 && bh <= WL_BOX_H) mode = inside ? WL_FAST : WL_GEN;
-                else { cX0 = 0; cY0 = 0; cX1 = -1; cY1 = -1; pitch = 4; }      // (not staged: keep the record inside 16 bits)
-            } else { cX0 = 0; cY0 = 0; cX1 = -1; cY1 = -1; pitch = 4; }
+            float u, v, okf;
+            wl_corner_uv<GEOM>((wl_cf)(a.cams + ((long)k * a.B + b) * PSCV_CAM_FLOATS), cx, cy, (corner & 4) ? dhi : dlo, a, u, v, okf);
+            box = wl_corner_box<false>(u, v, okf, a, WL_BOX_QUAD);
         }
-        if (corner == 0 && lane < 8 * WL_NSETS)
-            *reinterpret_cast<uint4*>(table + (set * WL_MAX_SRC + k) * 4) =
-                make_uint4(((unsigned)cX0 & 0xffffu) | ((unsigned)cY0 << 16), ((unsigned)cX1 & 0xffffu) | ((unsigned)cY1 << 16),
-                           (unsigned)pitch | ((unsigned)mode << 16), 0u);
+        if (corner == 0 && lane < 8 * WL_NSETS) wl_record_write<WL_REC>(table, set * WL_MAX_SRC + k, box);
     }
     __syncthreads();
 
@@ -242,20 +196,12 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
         any_gen = false;
 #pragma unroll
         for (int k = 0; k < WL_MAX_SRC; ++k) {
-            const uint4 rec = *reinterpret_cast<const uint4*>(table + (set * WL_MAX_SRC + k) * 4);
-            const int rx = __builtin_amdgcn_readfirstlane((int)rec.x), ry = __builtin_amdgcn_readfirstlane((int)rec.y);
-            const int rz = __builtin_amdgcn_readfirstlane((int)rec.z);
-            bX0[k] = (short)(rx & 0xffff); bY0[k] = rx >> 16;
-            bX1[k] = (short)(ry & 0xffff); bY1[k] = ry >> 16;
-            bPitch[k] = rz & 0xffff;
-            int mode = rz >> 16;
-            const int need = bPitch[k] * (bY1[k] - bY0[k] + 1);
-            if ((mode == WL_FAST || mode == WL_GEN) && used + need > WL_ARENA) mode = WL_DIRECT;
+            const WlBox r = wl_record_read<WL_REC>(table, set * WL_MAX_SRC + k);
+            bX0[k] = r.X0; bY0[k] = r.Y0; bX1[k] = r.X1; bY1[k] = r.Y1; bPitch[k] = r.pitch;
             bBase[k] = used;
-            if (mode == WL_FAST || mode == WL_GEN) used += need;
-            bMode[k] = mode;
-            any_gen = any_gen || mode == WL_GEN;
-            direct = direct || (k < n_src && mode == WL_DIRECT);
+            bMode[k] = wl_arena_take(r.mode, wl_box_texels(r), used, WL_ARENA);
+            any_gen = any_gen || bMode[k] == WL_GEN;
+            direct = direct || (k < n_src && bMode[k] == WL_DIRECT);
         }
         return direct;
     };
@@ -285,6 +231,8 @@ __global__ __launch_bounds__(WL_THREADS, 4) void warp_cost_lds_kernel(const Warp
         for (int k = 0; k < WL_MAX_SRC; ++k)
             if (k < n_src) atomicAdd(a.mode_hist + k * 4 + bMode[k], 1);
     }
+    // (this select chain and the one of the staging phase stay spelled out: through wl_view_select the compiler lays the blocks of this
+    //  kernel out anew; as they are, the sweep below compiles to the instructions it had before the box phase moved into warp_lds.h)
     const int sel = l;
     int mX0 = bX0[0], mY0 = bY0[0], mX1 = bX1[0], mY1 = bY1[0], mpitch = bPitch[0], mbase = bBase[0];
 #pragma unroll
@@ -530,25 +478,20 @@ static int wl_dispatch(const WarpArgs& a, int cost, dim3 grid, hipStream_t st) {
     return 1;
 }
 
-// Returns 0 if launched, 1 if this configuration is not covered by the LDS-staged kernel (the caller uses the quad /
-// generic direct kernels), negative on error.
-int* g_wl_mode_hist = nullptr;   // set by pscv_debug_wl_mode_hist (development aid, not thread-safe; shared with warp_cost_lv.hip)
+int* g_wl_mode_hist = nullptr;   // set by pscv_debug_wl_mode_hist (development aid, not thread-safe)
 
-int warp_cost_tiled_try(WarpArgs& a, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (a.depth_per_pixel || geom != PSCV_GEOM_PROJ) return 1;
-    if (out_dtype != in_dtype && out_dtype != PSCV_F32) return 1;
-    if (a.n_src < 1 || a.n_src > WL_MAX_SRC) return 1;
+int warp_cost_tiled_try(WarpArgs& a, const WarpCall& c) {
+    if (a.depth_per_pixel || c.geom != PSCV_GEOM_PROJ || a.n_src > WL_MAX_SRC) return 1;
     // planes per block: amortises the box + staging phases (13 % of a 32-plane workgroup's lifetime).  Round 6: 48 planes where the
     // depth axis has room for two such chunks -- the adaptive split (halves, quarters) takes care of the blocks whose 48-plane boxes do
     // not fit: 3-view step 0.900 -> 0.884 / 0.912 -> 0.899 ms on the probe rig, 0.987 -> 0.977 / 0.970 -> 0.970 on the DTU-like rig
     // (free-running per-view graphs, alternating; 64 planes: no better, 24: worse)
     dim3 grid;
-    const int rc = wl_plan("pscv_warp_cost(lds)", a, C, in_dtype, WL_T, WL_TH, ppd_override, a.D >= 96 ? 48 : 32, 64, grid);
+    // (known oddity, ADVICE.md: on small maps 48 halves to 24, 12, 6, 3 -- below the floor of 4 that 32 would stop at)
+    const int rc = wl_plan("pscv_warp_cost(lds)", a, c, WL_T, WL_TH, a.D >= 96 ? 48 : 32, 64, grid);
     if (rc) return rc;
-    a.variant = g_warp_tile;
-    a.mode_hist = g_wl_mode_hist;
-    return with_warp_types<false>("pscv_warp_cost(lds)", in_dtype, out_dtype, [&](auto ti, auto to) {
-        return wl_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, cost, grid, st);
+    return with_warp_types<false>("pscv_warp_cost(lds)", c.in_dtype, c.out_dtype, [&](auto ti, auto to) {
+        return wl_dispatch<typename decltype(ti)::type, typename decltype(to)::type>(a, c.cost, grid, c.st);
     });
 }
 

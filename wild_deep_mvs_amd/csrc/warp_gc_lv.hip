@@ -35,19 +35,14 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     static_assert(sizeof(TOut) == 2 && sizeof(TIn) == 2, "16-bit storage");
     extern __shared__ __attribute__((aligned(16))) unsigned char lsm[];
 
-    const int dc = blockIdx.y;
     int b, tyi, txi;
     if (!wl_tile_decode<LV_T, LV_TH>(a, b, tyi, txi)) return;
-
-    __builtin_amdgcn_s_setprio(3);
-    __builtin_amdgcn_s_setreg((1 - 1) << 11 | 23 << 6 | 1, 1);       // MODE.FP16_OVFL: saturating f32 -> f16 stores
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int x0t = txi * LV_T, y0t = tyi * LV_TH;
-    const int d0 = dc * a.ppd, d1 = min(a.D, d0 + a.ppd);
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const WlBlock blk = wl_block_prologue<LV_T, LV_TH>(a, b, tyi, txi);
+    const int x0t = blk.x0t, y0t = blk.y0t, d0 = blk.d0, d1 = blk.d1;
+    const float* const depth_b = blk.depth_b;
     const int nd = d1 - d0;
     const int hw = a.h * a.w;
-    const float* const depth_b = a.depth + (long)b * a.depth_bstride;
     const int n_src = a.n_src;
     int* const table = reinterpret_cast<int*>(lsm + LV_TABLE);
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lsm;
@@ -79,61 +74,23 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
         }
     }
 
-    float rf[C];
-    {
-        const TIn* rp = reinterpret_cast<const TIn*>(a.ref) + ((long)b * hw + pflat) * C;
-#pragma unroll
-        for (int k = 0; k < C / 8; ++k) {
-            const f32x8 t = Elem<TIn>::load8(rp + 8 * k);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rf[8 * k + i] = t.v[i];
-        }
-    }
+    const VecF<C> rfv = load_chan<TIn, C>(reinterpret_cast<const TIn*>(a.ref) + ((long)b * hw + pflat) * C);
+    const float (&rf)[C] = rfv.v;
 
     // ---- 1. wave k: texel box of source view k from the 8 corner projections (tile corners x depth extremes) ----
     if (wave < WL_MAX_SRC) {
         const int k = wave;
         const float dmin = wl_wave_reduce<false>(dlo), dmax = wl_wave_reduce<true>(dhi);
         const int corner = lane & 7;
-        const float cx = ((corner & 1) ? (float)min(x0t + LV_T - 1, a.w - 1) : (float)x0t) + 0.5f;
-        const float cy = (float)(((corner & 2) ? min(y0t + LV_TH - 1, a.h - 1) : y0t) + a.ref_y0) + 0.5f;
-        const float d = (corner & 4) ? dmax : dmin;
-        int cX0 = 0, cY0 = 0, cX1 = 1, cY1 = 1, pitch = 2, mode = WL_ZERO;
+        float cx, cy;
+        wl_tile_corner<LV_T, LV_TH, PSCV_GEOM_HOMOG>(a, blk, corner, cx, cy);
+        WlBox box = wl_box_none(WL_BOX_GC, WL_ZERO);      // (no such view)
         if (k < n_src) {
-            lv_cf cam = (lv_cf)(a.cams + ((long)k * a.B + b) * PSCV_CAM_FLOATS);
-            const float ax = fmaf(cam[1], cy, cam[0] * cx) + cam[2];
-            const float ay = fmaf(cam[4], cy, cam[3] * cx) + cam[5];
-            const float az = fmaf(cam[7], cy, cam[6] * cx) + cam[8];
-            const float bx = fmaf(cam[10], cy, cam[9] * cx) + cam[11];
-            const float by = fmaf(cam[13], cy, cam[12] * cx) + cam[14];
-            const float bz = fmaf(cam[16], cy, cam[15] * cx) + cam[17];
-            const float inv_d = __builtin_amdgcn_rcpf(d + 1e-9f);
-            const float hx = fmaf(-bx, inv_d, ax), hy = fmaf(-by, inv_d, ay), hz = fmaf(-bz, inv_d, az);
-            const float inv_z = __builtin_amdgcn_rcpf(hz);
-            const float u = hx * inv_z * a.sx, v = hy * inv_z * a.sy;
-            const float okf = (d > 1e-6f && hz > 1e-6f && fabsf(u) < 1e6f && fabsf(v) < 1e6f) ? 1.0f : 0.0f;   // also rejects NaN
-            const float umin = wl_reduce8<false>(u), umax = wl_reduce8<true>(u);
-            const float vmin = wl_reduce8<false>(v), vmax = wl_reduce8<true>(v);
-            const bool ok = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wl_reduce8<false>(okf))) != 0;
-            const float sl = 1.0f / 32.0f;
-            const int X0 = __builtin_amdgcn_readfirstlane((int)floorf(umin - sl)), X1 = __builtin_amdgcn_readfirstlane((int)floorf(umax + sl)) + 1;
-            const int Y0 = __builtin_amdgcn_readfirstlane((int)floorf(vmin - sl)), Y1 = __builtin_amdgcn_readfirstlane((int)floorf(vmax + sl)) + 1;
-            mode = WL_DIRECT;
-            if (ok) {
-                const bool outside = X1 < 0 || Y1 < 0 || X0 > a.ws - 1 || Y0 > a.hs - 1;
-                const bool inside = X0 >= 0 && Y0 >= 0 && X1 <= a.ws - 1 && Y1 <= a.hs - 1;
-                cX0 = max(X0, -2); cX1 = min(X1, a.ws + 1); cY0 = max(Y0, -2); cY1 = min(Y1, a.hs + 1);
-                const int bw = cX1 - cX0 + 1, bh = cY1 - cY0 + 1;
-                pitch = bw;
-                if (outside) mode = WL_ZERO;
-                else if (bw <= LV_BOX_W && bh <= LV_BOX_H) mode = inside ? WL_FAST : WL_GEN;
-            }
+            float u, v, okf;
+            wl_corner_uv<PSCV_GEOM_HOMOG>((wl_cf)(a.cams + ((long)k * a.B + b) * PSCV_CAM_FLOATS), cx, cy, (corner & 4) ? dmax : dmin, a, u, v, okf);
+            box = wl_corner_box<true>(u, v, okf, a, WL_BOX_GC);
         }
-        if (lane == 0) {
-            int4* row = reinterpret_cast<int4*>(table + k * 8);
-            row[0] = make_int4(cX0, cY0, cX1, cY1);
-            row[1] = make_int4(0, pitch, mode, 0);
-        }
+        if (lane == 0) wl_record_write<LV_REC>(table, k, box);
     }
     __syncthreads();
 
@@ -143,16 +100,11 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
         int used = 0;
 #pragma unroll
         for (int k = 0; k < WL_MAX_SRC; ++k) {
-            const int4 r0 = *reinterpret_cast<const int4*>(table + k * 8), r1 = *reinterpret_cast<const int4*>(table + k * 8 + 4);
-            const int X0 = __builtin_amdgcn_readfirstlane(r0.x), Y0 = __builtin_amdgcn_readfirstlane(r0.y);
-            const int Y1 = __builtin_amdgcn_readfirstlane(r0.w);
-            bP[k] = __builtin_amdgcn_readfirstlane(r1.y);
-            int mode = k < n_src ? __builtin_amdgcn_readfirstlane(r1.z) : WL_ZERO;
-            const int need = bP[k] * (Y1 - Y0 + 1);
-            if ((mode == WL_FAST || mode == WL_GEN) && used + need > LV_ARENA) mode = WL_DIRECT;
-            if (a.variant == 7 && (mode == WL_FAST || mode == WL_GEN)) mode = WL_DIRECT;     // ("warp_tile" = 7: nothing staged, a test aid)
+            const WlBox r = wl_record_read<LV_REC>(table, k);
+            const int X0 = r.X0, Y0 = r.Y0;
+            bP[k] = r.pitch;
             bBase[k] = used;
-            if (mode == WL_FAST || mode == WL_GEN) used += need;
+            const int mode = wl_arena_take(k < n_src ? r.mode : WL_ZERO, wl_box_texels(r), used, LV_ARENA, a.variant == 7);     // ("warp_tile" = 7: nothing staged, a test aid)
             bMode[k] = mode;
             if (a.mode_hist && k < n_src && tid == 0) atomicAdd(a.mode_hist + k * 4 + mode, 1);
             bE0[k] = ((bBase[k] - Y0 * bP[k] - X0) << 4) + (int)lds0;
@@ -162,16 +114,15 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     // ---- 3. wave k stages view k ----
     {
         const int k = wave;
-        const int4 f0 = *reinterpret_cast<const int4*>(table + k * 8);
-        const int sX0 = __builtin_amdgcn_readfirstlane(f0.x), sY0 = __builtin_amdgcn_readfirstlane(f0.y);
-        const int sX1 = __builtin_amdgcn_readfirstlane(f0.z), sY1 = __builtin_amdgcn_readfirstlane(f0.w);
+        const WlBox f = wl_record_read<LV_REC>(table, k);
+        const int sX0 = f.X0, sY0 = f.Y0, sX1 = f.X1, sY1 = f.Y1;
         int sP16 = bP[0] << 4, sMode = bMode[0], sBase = bBase[0];
         const void* srcp = a.src[0];
 #pragma unroll
         for (int t = 1; t < WL_MAX_SRC; ++t)
             if (k == t) { sP16 = bP[t] << 4; sMode = bMode[t]; sBase = bBase[t]; srcp = a.src[t]; }
         sBase = (sBase << 4) - sY0 * sP16 - (sX0 << 4);
-        if (k < n_src && (sMode == WL_FAST || sMode == WL_GEN)) lv_stage_box<TIn>(lsm, srcp, b, a.hs, a.ws, lane, sX0, sY0, sX1, sY1, sP16, sBase);
+        if (k < n_src && wl_staged(sMode)) lv_stage_box<TIn>(lsm, srcp, b, a.hs, a.ws, lane, sX0, sY0, sX1, sY1, sP16, sBase);
     }
 
     // ray terms A p and Bm p of this pixel, per view                                        homography.py:63-69
@@ -281,16 +232,12 @@ __global__ __launch_bounds__(LV_THREADS) __attribute__((amdgpu_waves_per_eu(LV_O
     }
 }
 
-extern int* g_wl_mode_hist;   // warp_cost_tiled.hip (pscv_debug_wl_mode_hist)
-
-// Returns 0 if launched (one launch per group of four source views), 1 if this configuration is not covered (the caller uses the quad
-// kernel), negative on error.
-int warp_gc_lv_try(WarpArgs& a0, int C, int geom, int cost, int in_dtype, int out_dtype, int ppd_override, hipStream_t st) {
-    if (geom != PSCV_GEOM_HOMOG || cost != PSCV_COST_GROUPCORR || out_dtype != in_dtype) return 1;
-    if (a0.n_src < 1 || a0.n_src > PSCV_MAX_SRC) return 1;
+// One launch per group of four source views.
+int warp_gc_lv_try(WarpArgs& a0, const WarpCall& c) {
+    if (c.geom != PSCV_GEOM_HOMOG || c.cost != PSCV_COST_GROUPCORR || c.out_dtype != c.in_dtype) return 1;
     if (a0.ws < 21 || a0.hs < 21) return 1;     // (below 21 texels the grid clamp reaches inside the image's tap range)
     dim3 grid;
-    const int plan = wl_plan("pscv_warp_cost(gc)", a0, C, in_dtype, LV_T, LV_TH, ppd_override, 32, a0.depth_per_pixel ? 32 : 64, grid);
+    const int plan = wl_plan("pscv_warp_cost(gc)", a0, c, LV_T, LV_TH, 32, a0.depth_per_pixel ? 32 : 64, grid);
     if (plan) return plan;
     for (int v0 = 0; v0 < a0.n_src; v0 += WL_MAX_SRC) {
         WarpArgs a = a0;
@@ -298,11 +245,9 @@ int warp_gc_lv_try(WarpArgs& a0, int C, int geom, int cost, int in_dtype, int ou
         for (int i = 0; i < PSCV_MAX_SRC; ++i) a.src[i] = (i < a.n_src) ? a0.src[v0 + i] : nullptr;
         a.cams = a0.cams + (long)v0 * a0.B * PSCV_CAM_FLOATS;
         a.out = reinterpret_cast<char*>(a0.out) + (unsigned long)v0 * a0.out_view_stride * 2;
-        a.mode_hist = g_wl_mode_hist ? g_wl_mode_hist + 0 : nullptr;
-        a.variant = g_warp_tile;
-        const int rc = with_half("pscv_warp_cost(gc)", in_dtype, [&](auto t) {
+        const int rc = with_half("pscv_warp_cost(gc)", c.in_dtype, [&](auto t) {
             using T = typename decltype(t)::type;
-            return launch("pscv_warp_cost(gc)", warp_gc_lv_kernel<T, T>, grid, dim3(LV_THREADS), LV_LDS, st, a);
+            return launch("pscv_warp_cost(gc)", warp_gc_lv_kernel<T, T>, grid, dim3(LV_THREADS), LV_LDS, c.st, a);
         });
         if (rc) return rc;
     }

@@ -8,18 +8,14 @@ namespace pscv {
 
 constexpr int LV_T = 8, LV_TH = 4;           // tile of reference pixels
 constexpr int LV_THREADS = 256;              // 4 waves; a wave trip = 32 pixels x 2 planes
-#ifndef LV_OCC
-#define LV_OCC 3                             // blocks per CU (= waves per SIMD): 3 -> 52 KiB arena, 168 registers; 4 -> 39.5 KiB, 128
-#endif
-constexpr int LV_ARENA = LV_OCC == 3 ? 416 : 316;   // staged texels per block (all views), fp32
 constexpr int LV_PLANE = LV_ARENA * 16;      // bytes of one channel-chunk plane
 constexpr int LV_TABLE = 8 * LV_PLANE;       // per-view box records written by wave 0
-constexpr int LV_LDS = LV_TABLE + 3 * WL_MAX_SRC * 32 + 32;   // box records: [3 plane ranges (whole chunk, first half, second half)][4 views] x 32 B
-constexpr int LV_BOX_W = 32, LV_BOX_H = 16;  // largest box the staging phase covers (one wave per view, batches of 8 rows x 16 texels)
+constexpr int LV_REC = WL_BOX_LANE.rec_bytes; // box records (warp_lds.h): [3 plane ranges (whole chunk, first half, second half)][4 views]
+constexpr int LV_LDS = LV_TABLE + 3 * WL_MAX_SRC * LV_REC + 32;      // (LV_OCC, LV_ARENA, LV_BOX_W x LV_BOX_H: warp_box.h)
 static_assert(LV_OCC * LV_LDS <= 160 * 1024, "LV_OCC blocks per CU");
 static_assert(7 * LV_PLANE + 16 < 65536, "chunk planes within the immediate offset of ds_read");
 
-typedef const __attribute__((address_space(4))) float* lv_cf;   // camera blocks through the scalar cache
+typedef wl_cf lv_cf;                                             // camera blocks through the scalar cache
 typedef const __attribute__((address_space(3))) wl_f4* lv_lp;   // a tap in LDS, by absolute byte address
 
 // (address + constant in one expression: the constant lands in the instruction's offset field)
