@@ -30,6 +30,9 @@ struct WarpBwdArgs {
 };
 
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
+// maximum that KEEPS a NaN (IEEE 754-2019 maximum: v_maximum3_f32 on gfx950, one instruction per two values like the v_max3_f32 of
+// fmaxf, which drops a NaN): the magnitude bounds of the tiled kernel must turn non-finite when any value under them is
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 
 template <typename TIn, typename TG, int C, int LPV, int GEOM, int COST>
 __global__ __launch_bounds__(256) void warp_bwd_kernel(const WarpBwdArgs A) {
@@ -252,7 +255,8 @@ __global__ __launch_bounds__(256) void warp_bwd_kernel(const WarpBwdArgs A) {
 //   3. flushes the patch with global float atomics in texel-major order: consecutive lanes hit consecutive addresses, so a
 //      wave instruction is two full 128-byte lines instead of 64 scattered words, and each texel of the box is touched
 //      once per workgroup instead of once per tap.
-// Taps that fall outside the (capacity-clipped) box take the direct global atomic, so any geometry stays correct.
+// Taps that fall outside the (capacity-clipped) box take the direct global atomic, so any geometry stays correct; so do all taps of a
+// lane whose magnitude bound is not finite (fixed point has no NaN or inf: tests/test_gpu_warp_bwd.py, part E).
 // The statistic of the forward (variance: sum; soft-min: numerator / weights) and the upstream gradient of the four planes
 // live in registers across the view loop.
 constexpr int BT_TW = 16, BT_TH = 8, BT_PLN = 4;
@@ -353,7 +357,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
     float invZ[BT_PLN], gcs[BT_PLN];
     float fmaxabs = 0.0f;    // largest |feature value| this lane holds or sampled: |warped - mean| <= 2 fmaxabs
 #pragma unroll
-    for (int j = 0; j < CPL; ++j) fmaxabs = fmaxf(fmaxabs, fabsf(rf.v[j]));
+    for (int j = 0; j < CPL; ++j) fmaxabs = max_keep_nan(fmaxabs, fabsf(rf.v[j]));
     if (VAR || COST == PSCV_COST_SOFTMIN) {
 #pragma unroll
         for (int i = 0; i < BT_PLN; ++i) {
@@ -364,7 +368,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
                 for (int v = 0; v < (BT_ABL(4) ? 0 : a.n_src); ++v) {
                     const VecF<CPL> wv = sample(v, dval[i], taps, x0, y0);
 #pragma unroll
-                    for (int j = 0; j < CPL; ++j) { s1.v[j] += wv.v[j]; fmaxabs = fmaxf(fmaxabs, fabsf(wv.v[j])); }
+                    for (int j = 0; j < CPL; ++j) { s1.v[j] += wv.v[j]; fmaxabs = max_keep_nan(fmaxabs, fabsf(wv.v[j])); }
                 }
                 G[i] = load_chan<TG, CPL>(gp + vox[i] * C + choff);
 #pragma unroll
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
                         const float t = rf.v[j] - wv.v[j];
                         diff.v[j] = t * t;
                         part += diff.v[j];
-                        fmaxabs = fmaxf(fmaxabs, fabsf(wv.v[j]));
+                        fmaxabs = max_keep_nan(fmaxabs, fabsf(wv.v[j]));
                     }
                     const float e = __expf(-a.temp * lane_sum(part));
                     Z += e;
@@ -440,7 +444,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
 #pragma unroll
             for (int i = 0; i < BT_PLN; ++i)
 #pragma unroll
-                for (int j = 0; j < CPL; ++j) gmax = fmaxf(gmax, fabsf(G[i].v[j]));
+                for (int j = 0; j < CPL; ++j) gmax = max_keep_nan(gmax, fabsf(G[i].v[j]));
             bnd = gmax * 2.0f * fmaxabs;
         } else if (COST == PSCV_COST_SOFTMIN) {
             // the soft-min coefficient has no useful closed-form bound (it mixes G, the weights and the channel sums):
@@ -453,7 +457,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
                 VecF<CPL> gw;
                 softmin_gw(i, wv, gw, false);
 #pragma unroll
-                for (int j = 0; j < CPL; ++j) bnd = fmaxf(bnd, fabsf(gw.v[j]));
+                for (int j = 0; j < CPL; ++j) bnd = max_keep_nan(bnd, fabsf(gw.v[j]));
             }
         } else if constexpr (COST == PSCV_COST_GROUPCORR) {
 #pragma unroll
@@ -462,7 +466,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     G[i].v[j] = dok[i] ? G8.v[choff / 4 + j / 4] : 0.0f;
-                    bnd = fmaxf(bnd, fabsf(G[i].v[j]) * fabsf(rf.v[j]));
+                    bnd = max_keep_nan(bnd, fabsf(G[i].v[j]) * fabsf(rf.v[j]));
                 }
             }
         } else {
@@ -472,12 +476,18 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     G[i].v[j] = dok[i] ? G[i].v[j] : 0.0f;
-                    bnd = fmaxf(bnd, fabsf(G[i].v[j]));
+                    bnd = max_keep_nan(bnd, fabsf(G[i].v[j]));
                 }
             }
         }
-        bnd = fminf(bnd, 3.0e38f);   // (an inf / NaN upstream gradient must not poison the scale; it reaches the output through the taps)
-        int bbits = active ? (int)__float_as_uint(bnd) : 0;
+        // A lane whose bound is not finite (an inf / NaN upstream gradient or feature value under it: the maxima above keep a NaN) has
+        // no fixed-point form -- __float2int_rn turns a NaN into 0 and an inf into a saturated integer, and the scale of an inf bound
+        // would flush every finite value of the workgroup to 0.  Such a lane stays out of the workgroup's bound, and its taps of this view
+        // are shifted out of every box (`xout`): they take the direct global atomics, which carry NaN and inf to the output like the
+        // direct kernel does.  The shift only enters the in-box comparison that every tap makes anyway.
+        const bool finite_bnd = bnd <= 3.0e38f;
+        const int xout = finite_bnd ? 0 : (1 << 28);
+        int bbits = (active && finite_bnd) ? (int)__float_as_uint(bnd) : 0;
         // exact bounding box of the texels this workgroup's samples of view v touch
         int mnx = INT_MAX, mny = INT_MAX, mxx = INT_MIN, mxy = INT_MIN;
 #pragma unroll
@@ -567,6 +577,7 @@ __global__ __launch_bounds__(256) void warp_bwd_tile_kernel(const WarpBwdArgs A)
                 gw = G[i];
             }
             if (dok[i] && (ALL || mine)) {
+                x0 += xout;
                 put(x0, y0, taps.o00, taps.w00, gw);
                 put(x0 + 1, y0, taps.o01, taps.w01, gw);
                 put(x0, y0 + 1, taps.o10, taps.w10, gw);
@@ -734,7 +745,8 @@ extern "C" int pscv_warp_cost_bwd(const void* ref, const void* const* srcs, int 
     PSCV_CHECK_ARG(n_src >= 1 && n_src <= PSCV_MAX_SRC, "pscv_warp_cost_bwd: n_src=%d outside [1,%d]", n_src, PSCV_MAX_SRC);
     PSCV_CHECK_ARG(srcs && cams && depth && grad_out && dsrcs, "pscv_warp_cost_bwd: null pointer argument");
     PSCV_CHECK_ARG(cost == PSCV_COST_WARP_ONLY || ref, "pscv_warp_cost_bwd: ref is required for cost mode %d", cost);
-    PSCV_CHECK_ARG(B > 0 && h > 0 && w > 0 && hs > 1 && ws > 1 && D > 0, "pscv_warp_cost_bwd: bad sizes");
+    PSCV_CHECK_ARG(B > 0 && h > 0 && w > 0 && hs > 1 && ws > 1 && D > 0,
+                   "pscv_warp_cost_bwd: bad sizes B=%d h=%d w=%d hs=%d ws=%d D=%d (all positive; hs and ws at least 2)", B, h, w, hs, ws, D);
     PSCV_CHECK_ARG((long)hs * ws < (1L << 24) && (long)hs * ws * C * 4 < (1L << 32), "pscv_warp_cost_bwd: source map %dx%dx%d too large", hs, ws, C);
     WarpBwdArgs A;
     WarpArgs& a = A.w;
