@@ -1011,6 +1011,39 @@ int pscv_depth_metrics(const float* est, const float* gt, const void* mask, int 
                        int W, const float* thr_abs, int n_abs, const float* thr_rel, int n_rel, void* workspace, double* sums,
                        float* means, void* stream);
 
+/*
+ * Training-view augmentation (an addition to ABI 14: new exports only, no existing signature changes): the reference's
+ * MVSDataset.data_augmentation (data/MVSDataset.py:124-150, BlendedMVS in train mode) -- torchvision's ColorJitter on the PIL image
+ * (ImageEnhance.Brightness / Contrast = Image.blend with a degenerate image), then a 3 x 3 directional blur of the fp32 image
+ * (csrc/image_augment.hip).  imgs: V <= PSCV_AUG_MAX_VIEWS views of one size, interleaved uint8
+ * [V][H][W][3] on the device.  The per-view records are PARALLEL HOST ARRAYS read before the call returns:
+ *   ops     int   [V][2]  the two steps in their order, each PSCV_AUG_NONE / _BRIGHTNESS / _CONTRAST; none may be listed twice
+ *   factors float [V][2]  the blend factor of each step (ignored for NONE); finite
+ *   weights float [V][9]  the blur's 3 x 3 correlation kernel, row-major; finite; a centre of 1 among zeros is "no blur"
+ * Per byte and step: t = (float)deg + a * (float)((int)v - (int)deg), product and sum each rounded to fp32; for 0 <= a <= 1 the byte
+ * is t truncated, otherwise 0 where t <= 0, 255 where t >= 255, else t truncated.  deg = 0 for brightness; for contrast
+ * deg = (2 S + H W) / (2 H W) in integers, S the sum over the WHOLE image, as it stands when the step runs, of
+ * (19595 R + 38470 G + 7471 B + 0x8000) >> 16.  Per pixel of the window and channel: the taps of non-zero weight, in row-major
+ * order, acc = w lut[byte] for the first and acc = acc + w lut[byte] after it (each product and sum rounded to fp32), neighbours
+ * outside the IMAGE (not the window) by BORDER_REFLECT_101 (-1 reads 1, n reads n - 2, a length of 1 reads 0).
+ *
+ * pscv_augment_workspace: bytes of the workspace (8-byte aligned) for V views; < 0 on error.
+ * pscv_augment_grey_sums: S of every view that has a contrast step, into the workspace (cleared on the stream first; integer
+ *   atomics, so equal inputs give equal sums).  No launch and no workspace needed when no view has one.
+ * pscv_augment_apply: out fp32 [V][3][ch][cw] = the window of ch rows from y0 and cw columns from x0; lut device fp32 [256], the
+ *   caller's float(v) / 255.0f; workspace as pscv_augment_grey_sums left it on the same stream (may be null without contrast).
+ * Asynchronous on `stream`, no host wait.
+ */
+#define PSCV_AUG_NONE 0
+#define PSCV_AUG_BRIGHTNESS 1
+#define PSCV_AUG_CONTRAST 2
+#define PSCV_AUG_MAX_VIEWS 16
+long pscv_augment_workspace(int V);
+int pscv_augment_grey_sums(const unsigned char* imgs, int V, int H, int W, const int* ops, const float* factors, void* workspace,
+                           void* stream);
+int pscv_augment_apply(const unsigned char* imgs, int V, int H, int W, const int* ops, const float* factors, const float* weights,
+                       const void* workspace, int x0, int y0, int cw, int ch, const float* lut, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,7 +62,7 @@ CONSTANTS = ("ABI_VERSION", "F32", "BF16", "F16", "GEOM_PROJ", "GEOM_HOMOG", "CO
              "COST_GROUPCORR", "COST_WARP_ONLY", "COST_VARIANCE_PARTIAL", "CONV_S1", "CONV_S2", "CONV_T2", "CONV_S1P8", "CONV_S1C1",
              "CONV_T2P8", "EPI_RELU_PRE", "EPI_RELU_POST", "MAX_SRC", "CAM_FLOATS", "GEO_MAX_SRC", "GEO_CAM_FLOATS", "FUSE_MAX_VIEWS",
              "PM_MAX_SRC", "PM_MAX_RADIUS", "PM_MAX_TOPK", "LOSS_GT_PLAIN", "LOSS_GT_BAYES", "LOSS_L_PLAIN", "LOSS_L_BAYES",
-             "LOSS_MAX_TERMS", "METRIC_MAX_THRESH", "METRIC_SUMS")
+             "LOSS_MAX_TERMS", "METRIC_MAX_THRESH", "METRIC_SUMS", "AUG_NONE", "AUG_BRIGHTNESS", "AUG_CONTRAST", "AUG_MAX_VIEWS")
 _missing = [n for n in CONSTANTS if n not in _CONSTS]
 if _missing:
     raise ImportError(f"include/pscv.h does not define PSCV_{_missing[0]} as an integer")

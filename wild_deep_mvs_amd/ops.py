@@ -1128,6 +1128,89 @@ def depth_nearest_crop(depth: torch.Tensor, size, crop=None, min_d: float = 0.0,
 
 
 # --------------------------------------------------------------------------------------------
+# training-view augmentation (data/MVSDataset.py:124-150: ColorJitter's brightness and contrast on the PIL image, motion_blur)
+# --------------------------------------------------------------------------------------------
+AUG_OPS = {"brightness": L.AUG_BRIGHTNESS, "contrast": L.AUG_CONTRAST}
+AUG_NO_BLUR = (0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def _augment_record(what, v, rec):
+    """One view's record -> ([op, op], [factor, factor], [9 weights]).  ``rec`` is None (nothing happens to the view), a pair
+    (steps, kernel) or an object whose ``record()`` returns one: steps = up to two (name, factor) in the order they run, names
+    "brightness" / "contrast"; kernel = 3 x 3 numbers or None (no blur)."""
+    steps, kernel = ((), None) if rec is None else (rec.record() if hasattr(rec, "record") else rec)
+    steps = list(steps)
+    if len(steps) > 2:
+        raise ValueError(f"{what}: view {v}: {len(steps)} colour steps, at most two")
+    ops_v, fac_v = [L.AUG_NONE, L.AUG_NONE], [1.0, 1.0]
+    for s, (name, factor) in enumerate(steps):
+        if name not in AUG_OPS:
+            raise ValueError(f"{what}: view {v}: step '{name}' must be one of {tuple(AUG_OPS)}")
+        if AUG_OPS[name] in ops_v:
+            raise ValueError(f"{what}: view {v}: '{name}' listed twice")
+        factor = float(np.float32(factor))
+        if not math.isfinite(factor):
+            raise ValueError(f"{what}: view {v}: the factor of '{name}' is not finite")
+        ops_v[s], fac_v[s] = AUG_OPS[name], factor
+    w = np.asarray(AUG_NO_BLUR if kernel is None else kernel, dtype=np.float32).reshape(-1)
+    if w.size != 9 or not np.isfinite(w).all():
+        raise ValueError(f"{what}: view {v}: the blur kernel must be 3 x 3 finite numbers")
+    return ops_v, fac_v, w.tolist()
+
+
+def augment_views(imgs_u8: torch.Tensor, params, crop=None) -> torch.Tensor:
+    """The reference's ``data_augmentation`` of V views of one size on the GPU: per view up to two
+    colour steps -- PIL's ``ImageEnhance.Brightness`` / ``Contrast``, byte for byte -- and a 3 x 3 blur of the fp32 image under
+    BORDER_REFLECT_101.  imgs_u8 uint8 [V,H,W,3] on the GPU, contiguous; ``params`` one record per view (see ``_augment_record``;
+    ``data.views.ViewAugmentation`` is one); ``crop`` = (x0, y0, w, h): only that window is computed, while contrast's mean and
+    the blur's borders stay those of the whole image.  -> fp32 [V,3,h,w].
+    Two launches on the current stream (pscv_augment_grey_sums, skipped when no view has a contrast step; pscv_augment_apply), no
+    host wait."""
+    what = "pscv.augment_views"
+    if not isinstance(imgs_u8, torch.Tensor):
+        raise ValueError(f"{what}: a uint8 [V,H,W,3] tensor expected, got {type(imgs_u8).__name__}")
+    if imgs_u8.dtype != torch.uint8:
+        raise ValueError(f"{what}: uint8 images expected, got {imgs_u8.dtype}")
+    if imgs_u8.dim() != 4 or imgs_u8.shape[3] != 3 or min(imgs_u8.shape[:3]) < 1:
+        raise ValueError(f"{what}: [V,H,W,3] expected, got {tuple(imgs_u8.shape)}")
+    if not imgs_u8.is_contiguous():
+        raise ValueError(f"{what}: the images must be contiguous")
+    V, H, W = (int(v) for v in imgs_u8.shape[:3])
+    if V > L.AUG_MAX_VIEWS:
+        raise ValueError(f"{what}: {V} views, at most {L.AUG_MAX_VIEWS} in one call")
+    params = list(params)
+    if len(params) != V:
+        raise ValueError(f"{what}: {len(params)} records for {V} views")
+    x0, y0, cw, ch = (0, 0, W, H) if crop is None else (int(v) for v in crop)
+    if x0 < 0 or y0 < 0 or cw < 1 or ch < 1 or x0 + cw > W or y0 + ch > H:
+        raise ValueError(f"{what}: crop {(x0, y0, cw, ch)} outside the {W} x {H} image")
+    if not imgs_u8.is_cuda:
+        raise ValueError(f"{what}: the images must be on the GPU (there is no CPU path)")
+    ops_l, fac_l, w_l = [], [], []
+    for v, rec in enumerate(params):
+        o, f, w = _augment_record(what, v, rec)
+        ops_l += o
+        fac_l += f
+        w_l += w
+    c_ops, c_fac, c_w = (C.c_int * (2 * V))(*ops_l), (C.c_float * (2 * V))(*fac_l), (C.c_float * (9 * V))(*w_l)
+    dev = imgs_u8.device
+    out = torch.empty((V, 3, ch, cw), dtype=torch.float32, device=dev)
+    ws = None
+    if L.AUG_CONTRAST in ops_l:
+        nbytes = L.lib().pscv_augment_workspace(V)
+        L.check(0 if nbytes >= 0 else -1, "pscv_augment_workspace")
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+        rc = _launch("augment_grey_sums", lambda: L.lib().pscv_augment_grey_sums(_p(imgs_u8), V, H, W, c_ops, c_fac, _p(ws), _stream()),
+                     cost=lambda: (float(V * H * W * 3), 0.0))
+        L.check(rc, "pscv_augment_grey_sums")
+    rc = _launch("augment_apply", lambda: L.lib().pscv_augment_apply(_p(imgs_u8), V, H, W, c_ops, c_fac, c_w, _p(ws), x0, y0, cw, ch,
+                                                                    _p(_unit_table(dev)), _p(out), _stream()),
+                 cost=lambda: (float(V * ch * cw * 15), 0.0))
+    L.check(rc, "pscv_augment_apply")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # PatchMatch multi-view stereo (the COLMAP baseline: utils/colmap_utils.py:depthmap_colmap)
 # --------------------------------------------------------------------------------------------
 PM_DELTA0, PM_THETA0_DEG = 0.25, 30.0      # candidate 9: inverse-depth fraction and normal angle, halved every iteration
