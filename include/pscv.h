@@ -514,6 +514,30 @@ int pscv_view_covisibility(const float* const* depth, const int* hw, int n_views
                            float max_depth_error, int* counts, void* workspace, long workspace_bytes, void* stream);
 
 /*
+ * Normal maps from depth maps (an addition to ABI 14: new exports only, no existing signature changes): the normals of a network
+ * reconstruction, for the normal test of pscv_colmap_fuse_pass_normals and for meshing (INTEGRATION.md section 2n,
+ * csrc/depth_normals.hip).  Per valid pixel (0 < d finite) a linear least-squares fit of the inverse depth over the
+ * (2 radius + 1)^2 window, taps gated by |d_q - d_p| <= rel_gate d_p, all fp64 from the fp32 inputs in a fixed order; a pixel with
+ * fewer than min_support taps, collinear taps or a fit that does not face the camera gets the ray towards the camera instead.
+ *   depth, hw   host arrays: n_views device pointers to fp32 [h_v, w_v] (0 = invalid) and the (h_v, w_v) pairs
+ *   cams        device fp32 [n_views][PSCV_GEO_CAM_FLOATS]; K at each map's size
+ *   1 <= n_views <= PSCV_FUSE_MAX_VIEWS, 1 <= radius <= 4, rel_gate > 0 finite, 3 <= min_support <= (2 radius + 1)^2
+ *   normal      host array of n_views device pointers, fp32 [h_v, w_v, 3]: unit normals in the camera frame (n^T K^-1 p < 0),
+ *               0 at invalid pixels -- the layout pscv_colmap_fuse_pass_normals reads
+ *   support     host array of n_views device pointers, int32 [h_v, w_v], or NULL: the tap count, negated where the pixel fell
+ *               back to the ray, 0 at invalid pixels
+ * One launch for all views on `stream`, no workspace, no host synchronisation, bit-reproducible.
+ *
+ * pscv_point_world_normals: out[k] = R_v^T n_v[pixel[k]], v = view[k] (fp64 sums rounded to fp32, the world normal of the fusion's
+ * normal test) for n_points fused points; view, pixel device int32 [n_points] (pixel = y w_v + x), out device fp32 [n_points][3].
+ * An index outside its range reads nothing and gives (0, 0, 0).  normal, hw, n_views, cams as above.
+ */
+int pscv_depth_normals(const float* const* depth, const int* hw, int n_views, const float* cams, int radius, double rel_gate,
+                       int min_support, float* const* normal, int* const* support, void* stream);
+int pscv_point_world_normals(const int* view, const int* pixel, long n_points, const float* const* normal, const int* hw,
+                             int n_views, const float* cams, float* out, void* stream);
+
+/*
  * Scene set-up from a COLMAP sparse model (an addition to ABI 14: new exports only, no existing signature changes): what
  * utils/colmap_utils.py:compute_src_imgs and compute_min_max_depth_yao compute for every YFCC scene (INTEGRATION.md section 2i,
  * csrc/scene_setup.hip).  All arrays are device memory; all calls are asynchronous on `stream`, need no workspace and are

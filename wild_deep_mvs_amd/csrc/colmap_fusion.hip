@@ -80,14 +80,6 @@ __device__ __forceinline__ uint32_t cf_fkey(float f) {           // IEEE total o
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float cf_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-// world normal R^T n of the camera-frame normal at n[0..2], each component rounded to fp32
-__device__ __forceinline__ void cf_world_normal(const float* c, const float* n, float& wx, float& wy, float& wz) {
-    const float* R = c + CAM_R;
-    const double nx = (double)n[0], ny = (double)n[1], nz = (double)n[2];
-    wx = (float)((double)R[0] * nx + (double)R[3] * ny + (double)R[6] * nz);
-    wy = (float)((double)R[1] * nx + (double)R[4] * ny + (double)R[7] * nz);
-    wz = (float)((double)R[2] * nx + (double)R[5] * ny + (double)R[8] * nz);
-}
 
 template <int W, bool PHASE_B, bool NORMALS>
 __global__ __launch_bounds__(CF_WAVE) void colmap_fuse_kernel(const typename CfArgsOf<NORMALS>::type a) {

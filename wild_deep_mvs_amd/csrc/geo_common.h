@@ -60,6 +60,14 @@ __device__ __forceinline__ void cf_project(const float* c, double X, double Y, d
 }
 __device__ __forceinline__ bool cf_depth_ok(float d) { return d > 0.0f && d <= 3.402823466e38f; }   // (false for NaN, inf)
 constexpr double CF_PIX_LIMIT = 1073741824.0;   // 2^30: a projection further out is no pixel of any view
+// world normal R^T n of the camera-frame normal at n[0..2], each component rounded to fp32 (the fusion's normal test; depth_normals.hip)
+__device__ __forceinline__ void cf_world_normal(const float* c, const float* n, float& wx, float& wy, float& wz) {
+    const float* R = c + CAM_R;
+    const double nx = (double)n[0], ny = (double)n[1], nz = (double)n[2];
+    wx = (float)((double)R[0] * nx + (double)R[3] * ny + (double)R[6] * nz);
+    wy = (float)((double)R[1] * nx + (double)R[4] * ny + (double)R[7] * nz);
+    wz = (float)((double)R[2] * nx + (double)R[5] * ny + (double)R[8] * nz);
+}
 
 // ---- one-workgroup exclusive scan ------------------------------------------------------------------------------------------
 // (internal linkage: every translation unit keeps its own copy in its own code object)

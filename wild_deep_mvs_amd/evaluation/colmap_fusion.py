@@ -9,7 +9,10 @@ line, COLMAP's defaults for the rest -- and has not been compared with the binar
 ``colmap_fusion(dataloader, args)`` keeps the reference's interface and writes the file its metrics step reads,
 ``<data_path>/Points/<model>_<nviews>/<model>_<nviews><scene>.ply``, in COLMAP's fused PLY layout.
 
-Network path (``args.colmap`` false): constant normals, the normal test off (``max_normal_error 180`` in the reference).
+Network path (``args.colmap`` false): constant normals, the normal test off (``max_normal_error 180`` in the reference).  With
+``args.fusion_normals = "depth"`` the normal maps come from the masked depth maps themselves (``ops.depth_normals``, INTEGRATION.md
+section 2n) and the normal test runs at ``args.fusion_max_normal_error`` (default 180 degrees: every pair passes, the points are
+the default run's and carry real normals).
 COLMAP baseline (``args.colmap``): the geometric normal maps that ``depthmap_colmap`` wrote under
 ``IntRes/colmap_dense/<scene>/stereo/normal_maps`` go into ``pscv_colmap_fuse_pass_normals`` with ``MAX_NORMAL_ERROR`` = 10
 degrees; until that folder exists the call raises ``NotImplementedError`` and touches no file.
@@ -27,7 +30,7 @@ from ..utils.colmap_array import read_array
 from ..utils.colmap_model import overlap_from_counts, overlap_from_covisibility, shared_point_counts
 from ..utils.point_cloud import write_colmap_point_cloud
 from .filtering import depth_folder_name
-from .fusibile import get_mask
+from .fusibile import depth_normal_options, get_mask, normal_source
 
 CHECK_NUM_IMAGES = 50          # COLMAP's StereoFusionOptions defaults
 MAX_TRAVERSAL_DEPTH = 100
@@ -113,6 +116,7 @@ def view_normals(normal_dir, filename, shape):
 
 
 def colmap_fusion(dataloader, args):
+    depth_normals = normal_source(args) == "depth"
     use_normals = bool(getattr(args, "colmap", False))
     normal_dir = Path(args.data_path) / "IntRes" / "colmap_dense" / str(args.scene) / "stereo" / "normal_maps"
     if use_normals and not normal_dir.is_dir():
@@ -149,6 +153,9 @@ def colmap_fusion(dataloader, args):
         depths = [torch.from_numpy(d).cuda() for d in depths]          # uploaded once: the overlap pass and the fusion share them
         overlap, source = scene_overlap(args, names, depths, cams)
         print(f"COLMAP fusion of {len(views)} views, overlap from {source}")
+        if depth_normals:                                              # from the maps the fusion reads, after upsample and mask
+            extra = dict(normals=ops.depth_normals(depths, cams, **depth_normal_options(args)),
+                         max_normal_error=getattr(args, "fusion_max_normal_error", 180.0))
         xyz, normal, rgb, _ = ops.colmap_fuse(depths, [torch.from_numpy(c).cuda() for c in colors],
                                               cams, overlap, max_depth_error=args.fusion_depth_threshold,
                                               max_reproj_error=args.fusion_max_reproj_error, min_num_pixels=args.fusion_num_consistent,

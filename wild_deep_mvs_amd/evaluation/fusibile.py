@@ -9,6 +9,11 @@ has not been compared with the binary's output).
 ``run(dataloader, args)`` keeps the reference's interface and writes the file its metrics step reads,
 ``<data_path>/Points/<model>_<nviews>/<model>_<nviews><scene>.ply``; ``fuse_depth_maps`` is the step as a function from tensors to a
 point cloud.
+
+With ``args.fusion_normals = "depth"`` every point also carries the world normal of the pixel that emitted it, estimated from
+its view's masked depth map (``ops.depth_normals``, ``ops.point_world_normals``), and the file has
+COLMAP's fused layout (``x y z nx ny nz red green blue``), which ``evaluation/metrics.py`` reads by property name like the plain
+one.  Points, colours and their order are those of the default run.
 """
 from __future__ import annotations
 
@@ -20,22 +25,27 @@ import torch
 from PIL import Image
 
 from .. import ops
-from ..utils.point_cloud import write_point_cloud
+from ..utils.point_cloud import write_colmap_point_cloud, write_point_cloud
 from .filtering import depth_folder_name
 
 DEPTH_MIN, DEPTH_MAX = 0.001, 100000.0       # fusibile.py:165-166
 
 
 def fuse_depth_maps(depths: Sequence, images: Sequence, K, R, t, *, disp_thresh: float = 0.01, num_consistent: int = 3,
-                    depth_min: float = DEPTH_MIN, depth_max: float = DEPTH_MAX, device="cuda"):
+                    depth_min: float = DEPTH_MIN, depth_max: float = DEPTH_MAX, device="cuda", normal_options=None):
     """depths N x [h_v,w_v] (masked pixels 0), images N x uint8 [h_v,w_v,3], K,R [N,3,3], t [N,3,1] (intrinsics at each depth
-    map's resolution; tensors or numpy arrays) -> (xyz fp32 [M,3], rgb uint8 [M,3], view int32 [M]) on ``device``."""
+    map's resolution; tensors or numpy arrays) -> (xyz fp32 [M,3], rgb uint8 [M,3], view int32 [M]) on ``device``.  With
+    ``normal_options`` (a dict of ``ops.depth_normals`` keywords, possibly empty) a fourth result, normal fp32 [M,3]: the world
+    normal of each point's emitting pixel from its view's depth map; the first three are the same either way."""
     tens = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)
     cams = ops.geo_filter_cams(tens(K), tens(R), tens(t)).to(device)
     d = [tens(x).to(device=device, dtype=torch.float32) for x in depths]
     c = [tens(x).to(device=device, dtype=torch.uint8) for x in images]
-    return ops.fuse_depth_maps(d, c, cams, disp_thresh=disp_thresh, num_consistent=num_consistent, depth_min=depth_min,
-                               depth_max=depth_max)
+    kw = dict(disp_thresh=disp_thresh, num_consistent=num_consistent, depth_min=depth_min, depth_max=depth_max)
+    if normal_options is None:
+        return ops.fuse_depth_maps(d, c, cams, **kw)
+    xyz, rgb, view, pixel = ops.fuse_depth_maps(d, c, cams, want_pixel=True, **kw)
+    return xyz, rgb, view, ops.point_world_normals(view, pixel, ops.depth_normals(d, cams, **normal_options), cams)
 
 
 def get_mask(args, filename, prob, geo_mask=None):
@@ -48,6 +58,27 @@ def get_mask(args, filename, prob, geo_mask=None):
                                / f"{filename}_out.npz")["geo_mask"]
         invalid = invalid | ~geo_mask
     return invalid
+
+
+NORMAL_SOURCES = ("constant", "depth")
+
+
+def normal_source(args):
+    """``args.fusion_normals`` (absent = "constant"), checked: "depth" estimates the network path's normal maps from its depth maps
+    and does not go with ``args.colmap``, whose PatchMatch brings its own."""
+    mode = getattr(args, "fusion_normals", "constant")
+    if mode not in NORMAL_SOURCES:
+        raise ValueError(f"fusion_normals must be one of {NORMAL_SOURCES}, got {mode!r}")
+    if mode == "depth" and getattr(args, "colmap", False):
+        raise ValueError("fusion_normals 'depth' is for the network path: under args.colmap the fusion reads PatchMatch's own normal maps")
+    return mode
+
+
+def depth_normal_options(args):
+    """The keyword arguments of ``ops.depth_normals`` from ``args.fusion_normal_radius``, ``fusion_normal_gate`` and
+    ``fusion_normal_support`` (each absent = the default of ``ops.depth_normals``)."""
+    names = (("radius", "fusion_normal_radius"), ("rel_gate", "fusion_normal_gate"), ("min_support", "fusion_normal_support"))
+    return {kw: getattr(args, name) for kw, name in names if getattr(args, name, None) is not None}
 
 
 def view_colors(img: torch.Tensor, downscale: int) -> np.ndarray:
@@ -81,6 +112,7 @@ def masked_view(args, batch, depth_folder):
 
 
 def run(dataloader, args):
+    with_normals = normal_source(args) == "depth"
     folder_name = depth_folder_name(args)
     out_path = Path(args.data_path) / "Points" / folder_name
     outfile = out_path / f"{folder_name}{args.scene}.ply"
@@ -91,9 +123,13 @@ def run(dataloader, args):
     views = [masked_view(args, batch, depth_folder) for batch in dataloader]
     depths, colors, K, R, t = zip(*views)
     with torch.no_grad():
-        xyz, rgb, _ = fuse_depth_maps(depths, colors, torch.stack(K), torch.stack(R), torch.stack(t),
-                                      disp_thresh=args.fusion_depth_threshold, num_consistent=args.fusion_num_consistent)
+        xyz, rgb, _, *normal = fuse_depth_maps(depths, colors, torch.stack(K), torch.stack(R), torch.stack(t),
+                                               disp_thresh=args.fusion_depth_threshold, num_consistent=args.fusion_num_consistent,
+                                               normal_options=depth_normal_options(args) if with_normals else None)
     out_path.mkdir(parents=True, exist_ok=True)
-    write_point_cloud(outfile, xyz.cpu().numpy(), rgb.cpu().numpy())
+    if with_normals:
+        write_colmap_point_cloud(outfile, xyz, normal[0], rgb)
+    else:
+        write_point_cloud(outfile, xyz.cpu().numpy(), rgb.cpu().numpy())
     print(f"Fused {xyz.shape[0]} points from {len(views)} views -> {outfile}")
     return args

@@ -826,6 +826,93 @@ def view_covisibility(depths: Sequence[torch.Tensor], cams: torch.Tensor, *, str
 
 
 # --------------------------------------------------------------------------------------------
+# normal maps from depth maps (the normals of a network reconstruction)
+# --------------------------------------------------------------------------------------------
+DEPTH_NORMALS_MAX_RADIUS = 4
+
+
+def depth_normals(depths: Sequence[torch.Tensor], cams: torch.Tensor, *, radius: int = 2, rel_gate: float = 0.05,
+                  min_support: int = 6, want_support: bool = False):
+    """Normal maps from depth maps: depths V x fp32 [h_v,w_v] (0 = invalid), cams [V,30]
+    (``geo_filter_cams``; intrinsics at each map's size), on the GPU, any V -> V x fp32 [h_v,w_v,3] on the GPU: unit normals in
+    the camera frame of their view facing the camera (n^T K^-1 p < 0), 0 at invalid pixels -- what ``colmap_fuse(normals=...)``
+    takes.  Per valid pixel a least-squares fit of the inverse depth over the (2 ``radius`` + 1)^2 window (``radius`` 1..4), over
+    the taps within ``rel_gate`` (relative) of the centre's depth; with fewer than ``min_support`` taps (3..window), collinear
+    taps or a fit that faces away, the pixel gets the ray towards the camera.  ``want_support`` appends V x int32 [h_v,w_v]: the
+    tap count, negated where the pixel fell back, 0 where invalid.  One pscv_depth_normals launch per 64 views on the current
+    stream, no host synchronisation, bit-reproducible."""
+    what = "pscv.depth_normals"
+    r = int(radius)
+    if not 1 <= r <= DEPTH_NORMALS_MAX_RADIUS:
+        raise ValueError(f"{what}: radius must lie in [1, {DEPTH_NORMALS_MAX_RADIUS}], got {radius}")
+    tau = float(rel_gate)
+    if not (tau > 0.0 and math.isfinite(tau)):                    # (false for NaN)
+        raise ValueError(f"{what}: rel_gate must be positive and finite, got {rel_gate}")
+    window = (2 * r + 1) ** 2
+    if not 3 <= int(min_support) <= window:
+        raise ValueError(f"{what}: min_support must lie in [3, {window}] (the window of radius {r}), got {min_support}")
+    cams = cams.to(torch.float32).contiguous()
+    _dev(cams)
+    depths, _, _ = _maps([d.to(torch.float32).contiguous() for d in depths], what)
+    n = len(depths)
+    _check_cams(cams, n if n else None, what)
+    dev = cams.device
+    if any(d.device != dev for d in depths):
+        raise ValueError(f"{what}: depth maps and cams must be on the same device")
+    normals = [torch.empty(tuple(d.shape) + (3,), dtype=torch.float32, device=dev) for d in depths]
+    supports = [torch.empty(d.shape, dtype=torch.int32, device=dev) for d in depths] if want_support else None
+    for first in range(0, n, L.FUSE_MAX_VIEWS):
+        part = slice(first, min(first + L.FUSE_MAX_VIEWS, n))
+        _, dptr, hw = _maps(depths[part], what)
+        k = part.stop - first
+        pixels = sum(int(d.numel()) for d in depths[part])
+        rc = _launch("depth_normals", lambda: L.lib().pscv_depth_normals(
+            dptr, hw, k, _p(cams[first:]), r, tau, int(min_support), _used_ptrs(normals[part]),
+            None if supports is None else _used_ptrs(supports[part]), _stream()),
+            # per pixel: 4 B read, 12 (+ 4) B written; per tap ~12 fp64 operations
+            cost=lambda: (float(pixels * (20 if want_support else 16)), 12.0 * window * pixels))
+        L.check(rc, "pscv_depth_normals")
+    return (normals, supports) if want_support else normals
+
+
+def point_world_normals(view: torch.Tensor, pixel: torch.Tensor, normals: Sequence[torch.Tensor], cams: torch.Tensor) -> torch.Tensor:
+    """World normals of fused points: view, pixel int32 [M] (the emitting view and pixel y w_v + x of each point, what
+    ``fuse_depth_maps(want_pixel=True)`` and ``colmap_fuse(want_pixel=True)`` return), normals V x fp32 [h_v,w_v,3] (camera
+    frame, ``depth_normals``), cams [V,30], on the GPU, 1 <= V <= 64 -> fp32 [M,3] on the GPU, ``R_v^T n`` by the rule of the
+    fusion's normal test (fp64 sums rounded to fp32).  An index outside its range gives (0,0,0).  One launch, no host
+    synchronisation."""
+    what = "pscv.point_world_normals"
+    normals = list(normals)
+    n = len(normals)
+    if not 1 <= n <= L.FUSE_MAX_VIEWS:
+        raise ValueError(f"{what}: 1..{L.FUSE_MAX_VIEWS} normal maps expected (PSCV_FUSE_MAX_VIEWS), got {n}")
+    for v, nm in enumerate(normals):
+        if not torch.is_tensor(nm) or nm.dtype != torch.float32 or nm.dim() != 3 or nm.shape[2] != 3:
+            raise ValueError(f"{what}: normal map {v} must be fp32 [h,w,3], got {getattr(nm, 'dtype', type(nm))} "
+                             f"{tuple(getattr(nm, 'shape', ()))}")
+    for name, idx in (("view", view), ("pixel", pixel)):
+        if not torch.is_tensor(idx) or idx.dtype != torch.int32 or idx.dim() != 1:
+            raise ValueError(f"{what}: {name} must be int32 [M], got {getattr(idx, 'dtype', type(idx))} {tuple(getattr(idx, 'shape', ()))}")
+    if view.shape != pixel.shape:
+        raise ValueError(f"{what}: view and pixel must have one entry per point, got {tuple(view.shape)} and {tuple(pixel.shape)}")
+    cams = cams.to(torch.float32).contiguous()
+    view, pixel = view.contiguous(), pixel.contiguous()
+    _dev(cams, view, pixel, *normals)
+    _check_cams(cams, n, what)
+    dev = cams.device
+    if any(t.device != dev for t in [view, pixel] + normals):
+        raise ValueError(f"{what}: indices, normal maps and cams must be on the same device")
+    m = int(view.shape[0])
+    out = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    hw = (C.c_int * (2 * n))(*[s for nm in normals for s in nm.shape[:2]])
+    rc = _launch("point_world_normals", lambda: L.lib().pscv_point_world_normals(
+        _p(view), _p(pixel), m, _used_ptrs(normals), hw, n, _p(cams), _p(out), _stream()),
+        cost=lambda: (float(m * (8 + 12 + 12)), 15.0 * m))
+    L.check(rc, "pscv_point_world_normals")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # scene set-up from a COLMAP sparse model (utils/colmap_utils.py: compute_src_imgs, compute_min_max_depth_yao)
 # --------------------------------------------------------------------------------------------
 def _sparse_inputs(what, xyz, R, t, **index_arrays):
