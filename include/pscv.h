@@ -538,6 +538,49 @@ int pscv_point_world_normals(const int* view, const int* pixel, long n_points, c
                              int n_views, const float* cams, float* out, void* stream);
 
 /*
+ * TSDF fusion and marching tetrahedra (an addition to ABI 14: new exports only, no existing signature changes): depth maps into a
+ * dense truncated-signed-distance volume and the volume into an indexed triangle mesh (INTEGRATION.md section 2o,
+ * csrc/tsdf_fusion.hip).  Grid: lattice point (i, j, k) at (o0 + i voxel, o1 + j voxel, o2 + k voxel), linear index
+ * (k ny + j) nx + i, nx ny nz < 2^31.  State, device arrays [nz][ny][nx], zero at the start: tsdf_sum fp32, weight int32, rgb_sum
+ * fp32 [..][3], cweight int32.  All arithmetic is fp64 in a fixed order: every result is bit-reproducible.  Asynchronous on `stream`.
+ *
+ * pscv_tsdf_integrate: adds 1 <= n_views <= PSCV_FUSE_MAX_VIEWS views to the state, in view order.  Per voxel X and view:
+ * (x, y, z) = K (R X + t), z > 0; pixel (floor(x / z + 0.5), floor(y / z + 0.5)) inside the view; its depth d valid (0 < d finite);
+ * sd = d - z >= -trunc: tsdf_sum += min(1, sd / trunc), weight += 1, and where sd <= trunc also rgb_sum += the pixel's bytes,
+ * cweight += 1.  tsdf_sum is rounded to fp32 once per call.
+ *   depth, color, hw   host arrays: n_views device pointers to fp32 [h_v, w_v] and rgba8 [h_v, w_v] (red in the low byte), and the
+ *                      (h_v, w_v) pairs;  cams device fp32 [n_views][PSCV_GEO_CAM_FLOATS]
+ *   dmax               device fp32 [n_views]: the largest valid depth of each view (0 for a view without one); the kernel skips
+ *                      (tile, view) pairs it proves untouched, which changes no result while dmax is not too small
+ *   origin, voxel > 0, trunc > 0 finite
+ *
+ * pscv_tsdf_mark: f(p) = tsdf_sum / weight, p observed iff weight >= min_weight (>= 1), negative iff f(p) < 0.  Edge (p, d), d =
+ * 1..7 (bit 0 = x, 1 = y, 2 = z), joins p and p + bits(d); it carries a vertex iff both ends are observed and exactly one is
+ * negative.  info device int32 [nz][ny][nx]: bits 0-6 the edge mask of p (bit d-1), bit 8 observed, bit 9 negative, bits 16-23 the
+ * number of vertices, bits 24-31 the number of faces of the cell at p (six tetrahedra (0, a, a|b, 7) over the axis orders).
+ *
+ * pscv_tsdf_emit_vertices / pscv_tsdf_emit_faces: vincl, fincl device int32 [nx ny nz] are the INCLUSIVE prefix sums of the two
+ * counts of info in linear order; n_vertices, n_faces their totals.  Vertices are numbered by (linear index, d): position
+ * X(p) + t (X(q) - X(p)) with t = f(p) / (f(p) - f(q)) rounded to fp32 -> xyz [n_vertices][3]; colour interpolated the same way
+ * between the ends' mean colours (an end with cweight 0 leaves the other's; neither: 0) -> rgb uint8 [n_vertices][3].  Faces:
+ * int32 [n_faces][3], by cell, tetrahedron 0..5, oriented towards the positive side, smallest vertex index first, a quad as
+ * (q0,q1,q2), (q0,q2,q3).  A total of 0 launches nothing.
+ *
+ * pscv_tsdf_case_table: the 6 x 16 orientation table of the face kernel, host memory unsigned [96]: entry [T][negative corner
+ * positions] = vertex count in bits 0-2, vertex k's edge in bits 3 + 6 k .. 8 + 6 k as corner | edge type << 3.
+ */
+int pscv_tsdf_integrate(const float* const* depth, const unsigned int* const* color, const int* hw, int n_views, const float* cams,
+                        const float* dmax, double o0, double o1, double o2, double voxel, double trunc, int nx, int ny, int nz,
+                        float* tsdf_sum, int* weight, float* rgb_sum, int* cweight, void* stream);
+int pscv_tsdf_mark(const float* tsdf_sum, const int* weight, int nx, int ny, int nz, int min_weight, int* info, void* stream);
+int pscv_tsdf_emit_vertices(const float* tsdf_sum, const int* weight, const float* rgb_sum, const int* cweight, const int* info,
+                            const int* vincl, int nx, int ny, int nz, double o0, double o1, double o2, double voxel, float* xyz,
+                            unsigned char* rgb, long n_vertices, void* stream);
+int pscv_tsdf_emit_faces(const int* info, const int* vincl, const int* fincl, int nx, int ny, int nz, int* faces, long n_faces,
+                         void* stream);
+int pscv_tsdf_case_table(unsigned int* table);
+
+/*
  * Scene set-up from a COLMAP sparse model (an addition to ABI 14: new exports only, no existing signature changes): what
  * utils/colmap_utils.py:compute_src_imgs and compute_min_max_depth_yao compute for every YFCC scene (INTEGRATION.md section 2i,
  * csrc/scene_setup.hip).  All arrays are device memory; all calls are asynchronous on `stream`, need no workspace and are

@@ -913,6 +913,180 @@ def point_world_normals(view: torch.Tensor, pixel: torch.Tensor, normals: Sequen
 
 
 # --------------------------------------------------------------------------------------------
+# TSDF fusion of depth maps and marching-tetrahedra meshing
+# --------------------------------------------------------------------------------------------
+TSDF_MAX_VOXELS = 2 ** 31 - 1
+TSDF_MAX_VIEWS = (2 ** 24 - 1) // 255          # 65793: rgb_sum holds integers in fp32, exact while 255 cweight < 2^24
+
+
+@dataclass
+class TsdfVolume:
+    """The state of a TSDF grid of ``dims`` = (nx, ny, nz) on one GPU: tsdf_sum fp32, weight int32, cweight int32 [nz,ny,nx] and
+    rgb_sum fp32 [nz,ny,nx,3]; ``views`` counts the views integrated so far (host side)."""
+    dims: tuple
+    tsdf_sum: torch.Tensor
+    weight: torch.Tensor
+    rgb_sum: torch.Tensor
+    cweight: torch.Tensor
+    views: int = 0
+
+    def arrays(self):
+        return self.tsdf_sum, self.weight, self.rgb_sum, self.cweight
+
+
+def _tsdf_dims(dims, what):
+    try:
+        nx, ny, nz = (int(v) for v in dims)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: dims must be three integers (nx, ny, nz), got {dims!r}")
+    if min(nx, ny, nz) < 1 or nx * ny * nz > TSDF_MAX_VOXELS:
+        raise ValueError(f"{what}: dims {nx} x {ny} x {nz} must be positive with nx ny nz < 2^31")
+    return nx, ny, nz
+
+
+def _tsdf_grid(origin, voxel, what):
+    try:
+        o = tuple(float(v) for v in origin)
+    except (TypeError, ValueError):
+        o = ()
+    if len(o) != 3 or not all(math.isfinite(v) for v in o):
+        raise ValueError(f"{what}: origin must be three finite numbers, got {origin!r}")
+    s = float(voxel)
+    if not (s > 0.0 and math.isfinite(s)):
+        raise ValueError(f"{what}: voxel must be positive and finite, got {voxel}")
+    return o, s
+
+
+def _tsdf_state(state, what):
+    if not isinstance(state, TsdfVolume):
+        raise ValueError(f"{what}: state must be the TsdfVolume of ops.tsdf_volume, got {type(state).__name__}")
+    nx, ny, nz = _tsdf_dims(state.dims, what)
+    want = ((torch.float32, (nz, ny, nx)), (torch.int32, (nz, ny, nx)), (torch.float32, (nz, ny, nx, 3)), (torch.int32, (nz, ny, nx)))
+    for name, t, (dt, shape) in zip(("tsdf_sum", "weight", "rgb_sum", "cweight"), state.arrays(), want):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: state.{name} must be {dt} {shape}, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return nx, ny, nz
+
+
+def tsdf_volume(dims, device="cuda") -> TsdfVolume:
+    """The zeroed state of a TSDF grid of ``dims`` = (nx, ny, nz), nx ny nz < 2^31, on ``device`` (24 bytes per voxel)."""
+    nx, ny, nz = _tsdf_dims(dims, "pscv.tsdf_volume")
+    z = lambda dt, *more: torch.zeros((nz, ny, nx) + more, dtype=dt, device=device)
+    return TsdfVolume((nx, ny, nz), z(torch.float32), z(torch.int32), z(torch.float32, 3), z(torch.int32))
+
+
+def _max_valid_depth(depths):
+    """fp32 [V] on the device: the largest valid (0 < d finite) depth of each map, 0 for a map without one (plumbing: no host read)."""
+    def amax(d):
+        ok = (d > 0) & (d <= torch.finfo(torch.float32).max)
+        return torch.where(ok, d, torch.zeros_like(d)).flatten(-2).amax(dim=-1)
+    if all(d.shape == depths[0].shape for d in depths):
+        return amax(torch.stack(depths)).contiguous()
+    return torch.stack([amax(d) for d in depths]).contiguous()
+
+
+def tsdf_integrate(state: TsdfVolume, depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, *,
+                   origin, voxel: float, trunc: float) -> TsdfVolume:
+    """Integrates depth maps into the TSDF ``state`` in place: depths V x fp32 [h_v,w_v] (0 = invalid),
+    colors V x uint8 [h_v,w_v,3] (or packed int32 [h_v,w_v], ``pack_rgba8``), cams [V,30] (``geo_filter_cams``), on the GPU of the
+    state, any V >= 1.  Lattice point (i,j,k) sits at ``origin`` + (i,j,k) ``voxel``; per voxel and view the signed distance along
+    the view's z axis, sd = d - z at the pixel the voxel's centre rounds to, is kept when sd >= -``trunc`` and adds min(1, sd /
+    trunc) to tsdf_sum and 1 to weight; where also sd <= trunc the pixel's colour joins rgb_sum / cweight.  One
+    pscv_tsdf_integrate launch per 64 views in view order on the current stream, no host synchronisation, bit-reproducible."""
+    what = "pscv.tsdf_integrate"
+    nx, ny, nz = _tsdf_state(state, what)
+    o, s = _tsdf_grid(origin, voxel, what)
+    tr = float(trunc)
+    if not (tr > 0.0 and math.isfinite(tr)):
+        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
+    depths, colors = list(depths), list(colors)
+    n = len(depths)
+    if n < 1 or len(colors) != n:
+        raise ValueError(f"{what}: at least one depth map and as many colour images expected, got {n} and {len(colors)}")
+    if state.views + n > TSDF_MAX_VIEWS:
+        raise ValueError(f"{what}: {state.views} + {n} views exceed the {TSDF_MAX_VIEWS} a volume can hold (its fp32 colour sums stay "
+                         f"exact only while 255 cweight < 2^24)")
+    if not torch.is_tensor(cams):
+        raise ValueError(f"{what}: cams must be a tensor [V,{L.GEO_CAM_FLOATS}]")
+    _check_cams(cams, n, what)
+    packed = []
+    for v, (d, c) in enumerate(zip(depths, colors)):
+        if not torch.is_tensor(d) or d.dtype != torch.float32 or d.dim() != 2:
+            raise ValueError(f"{what}: depth map {v} must be fp32 [h,w], got {getattr(d, 'dtype', type(d))} {tuple(getattr(d, 'shape', ()))}")
+        if torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
+            packed.append(c)
+        elif torch.is_tensor(c) and c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
+            packed.append(None)
+        else:
+            raise ValueError(f"{what}: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
+    cams = cams.contiguous()
+    depths = [d.contiguous() for d in depths]
+    _dev(cams, *depths, *state.arrays())
+    dev = state.tsdf_sum.device
+    for c in colors:
+        _dev(c.contiguous())
+    if any(t.device != dev for t in [cams] + depths + colors + list(state.arrays())):
+        raise ValueError(f"{what}: state, depth maps, colours and cams must be on the same device")
+    packed = [pack_rgba8(c) if p is None else p.contiguous() for c, p in zip(colors, packed)]
+    for first in range(0, n, L.FUSE_MAX_VIEWS):
+        part = slice(first, min(first + L.FUSE_MAX_VIEWS, n))
+        _, dptr, hw = _maps(depths[part], what)
+        k = part.stop - first
+        dmax = _max_valid_depth(depths[part])
+        cam_part = cams[part]
+        rc = _launch("tsdf_integrate", lambda: L.lib().pscv_tsdf_integrate(
+            dptr, _used_ptrs(packed[part]), hw, k, _p(cam_part), _p(dmax), o[0], o[1], o[2], s, tr, nx, ny, nz,
+            _p(state.tsdf_sum), _p(state.weight), _p(state.rgb_sum), _p(state.cweight), _stream()),
+            # the state read and written once (2 x 24 B per voxel); per voxel and view ~60 fp64 operations and three divisions
+            cost=lambda: (48.0 * nx * ny * nz, 100.0 * nx * ny * nz * k))
+        L.check(rc, "pscv_tsdf_integrate")
+        state.views += k
+    return state
+
+
+def tsdf_extract(state: TsdfVolume, *, origin, voxel: float, min_weight: int = 1):
+    """Marching tetrahedra over the TSDF ``state`` -> (xyz fp32 [V,3], rgb uint8 [V,3], faces int32
+    [F,3]) on the GPU: the zero crossing of f = tsdf_sum / weight over the voxels with weight >= ``min_weight`` (>= 1), one vertex
+    per sign-changing lattice edge (ordered by voxel, then edge type), faces oriented towards the positive (free-space) side,
+    ordered by cell and tetrahedron.  Mark, two prefix sums (torch), one host read of their last entries (the totals), two emits; bit-reproducible."""
+    what = "pscv.tsdf_extract"
+    nx, ny, nz = _tsdf_state(state, what)
+    o, s = _tsdf_grid(origin, voxel, what)
+    if isinstance(min_weight, bool) or int(min_weight) != min_weight or int(min_weight) < 1:
+        raise ValueError(f"{what}: min_weight must be an integer >= 1, got {min_weight!r}")
+    _dev(*state.arrays())
+    dev = state.tsdf_sum.device
+    nvox = nx * ny * nz
+    info = torch.empty(nvox, dtype=torch.int32, device=dev)
+    st = _stream()
+    rc = _launch("tsdf_mark", lambda: L.lib().pscv_tsdf_mark(_p(state.tsdf_sum), _p(state.weight), nx, ny, nz, int(min_weight),
+                                                             _p(info), st), cost=lambda: (12.0 * nvox, 2.0 * nvox))
+    L.check(rc, "pscv_tsdf_mark")
+    counts = info.view(torch.uint8).view(nvox, 4)[:, 2:]              # (little-endian: byte 2 = vertices, byte 3 = faces)
+    if 12 * nvox >= 2 ** 31:       # a voxel has at most 7 vertices and 12 faces: only a grid this large can overflow the int32 sums
+        totals = counts.sum(dim=0, dtype=torch.int64).tolist()
+        if max(totals) >= 2 ** 31:
+            raise L.PscvError(f"{what}: {totals[0]} vertices and {totals[1]} faces do not fit int32 indices")
+    vincl = torch.cumsum(counts[:, 0], dim=0, dtype=torch.int32)
+    fincl = torch.cumsum(counts[:, 1], dim=0, dtype=torch.int32)
+    n_vert, n_face = (int(v) for v in torch.stack((vincl[-1], fincl[-1])).tolist())   # the totals: the one host read
+    xyz = torch.empty((n_vert, 3), dtype=torch.float32, device=dev)
+    rgb = torch.empty((n_vert, 3), dtype=torch.uint8, device=dev)
+    faces = torch.empty((n_face, 3), dtype=torch.int32, device=dev)
+    if n_vert == 0:
+        return xyz, rgb, faces
+    rc = _launch("tsdf_emit_vertices", lambda: L.lib().pscv_tsdf_emit_vertices(
+        _p(state.tsdf_sum), _p(state.weight), _p(state.rgb_sum), _p(state.cweight), _p(info), _p(vincl), nx, ny, nz, o[0], o[1], o[2],
+        s, _p(xyz), _p(rgb), n_vert, st), cost=lambda: (8.0 * nvox + 60.0 * n_vert, 40.0 * n_vert))
+    L.check(rc, "pscv_tsdf_emit_vertices")
+    if n_face:
+        rc = _launch("tsdf_emit_faces", lambda: L.lib().pscv_tsdf_emit_faces(_p(info), _p(vincl), _p(fincl), nx, ny, nz, _p(faces),
+                                                                             n_face, st), cost=lambda: (8.0 * nvox + 12.0 * n_face, 0.0))
+        L.check(rc, "pscv_tsdf_emit_faces")
+    return xyz, rgb, faces
+
+
+# --------------------------------------------------------------------------------------------
 # scene set-up from a COLMAP sparse model (utils/colmap_utils.py: compute_src_imgs, compute_min_max_depth_yao)
 # --------------------------------------------------------------------------------------------
 def _sparse_inputs(what, xyz, R, t, **index_arrays):

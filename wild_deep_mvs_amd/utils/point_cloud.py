@@ -100,3 +100,86 @@ def read_ply(path) -> np.ndarray:
             raise ValueError(f"{path}: coordinates {', '.join(wide)} are float64; the metrics run on float32 points and will not "
                              f"round them silently")
         return np.fromfile(fh, dtype=props, count=n)
+
+
+# ---- triangle meshes (evaluation/tsdf_fusion.py) ----------------------------------------------------------------------------------
+_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def mesh_ply_header(n_vertices: int, n_faces: int) -> bytes:
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n_vertices}"]
+    lines += [f"property float32 {c}" for c in "xyz"] + [f"property uint8 {c}" for c in ("red", "green", "blue")]
+    lines += [f"element face {n_faces}", "property list uchar int vertex_indices"]
+    return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
+
+
+def write_mesh(path, xyz, rgb, faces) -> None:
+    """xyz [V,3] (cast to float32), rgb [V,3] uint8, faces [F,3] integer indices into the vertices -> binary little-endian PLY at
+    ``path`` with ``element face`` / ``property list uchar int vertex_indices`` (numpy arrays or tensors)."""
+    xyz = np.asarray(getattr(xyz, "cpu", lambda: xyz)(), dtype=np.float32).reshape(-1, 3)
+    rgb = np.asarray(getattr(rgb, "cpu", lambda: rgb)())
+    faces = np.asarray(getattr(faces, "cpu", lambda: faces)())
+    if rgb.dtype != np.uint8 or rgb.shape != xyz.shape:
+        raise ValueError(f"write_mesh: rgb must be uint8 {xyz.shape}, got {rgb.dtype} {rgb.shape}")
+    if faces.dtype.kind not in "iu" or faces.ndim != 2 or faces.shape[1] != 3:
+        raise ValueError(f"write_mesh: faces must be integer [F,3], got {faces.dtype} {faces.shape}")
+    if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= xyz.shape[0]):
+        raise ValueError(f"write_mesh: face indices must lie in [0, {xyz.shape[0]})")
+    vdata = np.empty(xyz.shape[0], dtype=_VERTEX)
+    for k, c in enumerate("xyz"):
+        vdata[c] = xyz[:, k]
+    for k, c in enumerate(("red", "green", "blue")):
+        vdata[c] = rgb[:, k]
+    fdata = np.empty(faces.shape[0], dtype=_FACE)
+    fdata["n"] = 3
+    fdata["v"] = faces
+    tmp = f"{path}.part"
+    with open(tmp, "wb") as fh:
+        fh.write(mesh_ply_header(xyz.shape[0], faces.shape[0]))
+        fh.write(vdata.tobytes())
+        fh.write(fdata.tobytes())
+    os.replace(tmp, path)
+
+
+def read_mesh(path):
+    """(xyz float32 [V,3], rgb uint8 [V,3], faces int32 [F,3]) of a binary little-endian PLY triangle mesh as ``write_mesh`` writes
+    it: vertex properties by name (x, y, z float32 and red, green, blue uint8 must be among them), faces as a uchar-counted list of
+    int / uint indices, every face a triangle."""
+    with open(path, "rb") as fh:
+        if b"ply" not in fh.readline():
+            raise ValueError(f"{path}: not a PLY file")
+        fmt = fh.readline().split()[1].decode()
+        if fmt != "binary_little_endian":
+            raise ValueError(f"{path}: PLY format {fmt!r} is not binary_little_endian")
+        counts, props, index_type, element, line = {}, [], None, None, b""
+        while b"end_header" not in line:
+            line = fh.readline()
+            if line == b"":
+                raise ValueError(f"{path}: truncated PLY header")
+            tok = line.split()
+            if tok[:1] == [b"element"]:
+                element = tok[1].decode()
+                counts[element] = int(tok[2])
+            elif tok[:1] == [b"property"]:
+                if element == "vertex":
+                    if tok[1] not in PLY_DTYPES:
+                        raise ValueError(f"{path}: unsupported PLY property type {tok[1].decode()!r}")
+                    props.append((tok[2].decode(), "<" + PLY_DTYPES[tok[1]]))
+                elif element == "face":
+                    if tok[1] != b"list" or PLY_DTYPES.get(tok[2]) != "u1" or PLY_DTYPES.get(tok[3]) not in ("i4", "u4"):
+                        raise ValueError(f"{path}: faces must be `property list uchar int vertex_indices`")
+                    index_type = "<" + PLY_DTYPES[tok[3]]
+        if "vertex" not in counts or "face" not in counts or index_type is None or list(counts) != ["vertex", "face"]:
+            raise ValueError(f"{path}: a mesh needs `element vertex` followed by `element face`")
+        vdata = np.fromfile(fh, dtype=props, count=counts["vertex"])
+        fdata = np.fromfile(fh, dtype=np.dtype([("n", "u1"), ("v", index_type, (3,))]), count=counts["face"])
+    if vdata.shape[0] != counts["vertex"] or fdata.shape[0] != counts["face"]:
+        raise ValueError(f"{path}: truncated PLY data")
+    if fdata.size and (fdata["n"] != 3).any():
+        raise ValueError(f"{path}: every face must be a triangle")
+    for c in ("x", "y", "z"):
+        if vdata.dtype[c] != np.dtype("<f4"):
+            raise ValueError(f"{path}: coordinate {c} must be float32")
+    xyz = np.stack([vdata[c] for c in "xyz"], axis=-1).astype(np.float32).reshape(-1, 3)
+    rgb = np.stack([vdata[c] for c in ("red", "green", "blue")], axis=-1).astype(np.uint8).reshape(-1, 3)
+    return xyz, rgb, fdata["v"].astype(np.int32).reshape(-1, 3)
