@@ -33,7 +33,7 @@ extern "C" {
 /* storage dtypes */
 #define PSCV_F32 0
 #define PSCV_BF16 1
-#define PSCV_F16 2 /* IEEE half, stores saturate at +-65504 */
+#define PSCV_F16 2 /* IEEE half, stores saturate at +-65504; a NaN is stored as NaN */
 
 /* sampling geometry of the warp */
 #define PSCV_GEOM_PROJ 0  /* q = rot*(x,y,1)*d + trans, integer pixel centres, sample at index (u,v):

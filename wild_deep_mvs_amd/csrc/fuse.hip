@@ -67,8 +67,9 @@ __global__ __launch_bounds__(256) void fuse_finish_kernel(const float* __restric
 // Backward of the fusion (training): with fused = sum_v w_v I_v / W, W = sum_v w_v, w_v = exp(-u_v) and G the
 // gradient of the fused volume,
 //     d I_v = G w_v / W            d u_v = -w_v / W * sum_{d,c} G (I_v - fused)
-// One lane per pixel walks the depth axis (coalesced 16-byte accesses across the wave), recomputes `fused` from the pair
-// volumes and keeps the per-view sums in registers: every volume is read once, every d I_v written once.
+// One lane per pixel walks the depth axis (coalesced 16-byte accesses across the wave), recomputes `fused` (relative to the view of
+// largest weight, see the kernel) from the pair volumes and keeps the per-view sums in registers: every volume is read once, every
+// d I_v written once.
 struct FuseBwdArgs {
     const void* interm[PSCV_MAX_SRC];
     const float* uncert[PSCV_MAX_SRC];
@@ -91,31 +92,41 @@ __global__ __launch_bounds__(256) void fuse_pairs_bwd_kernel(const FuseBwdArgs a
     p = active ? p : npix - 1;
     const int b = (int)(p / a.hw);
     const int pf = (int)(p - (long)b * a.hw);
+    // d u_v cancels: sum G I_v against sum G fused.  Where one view carries nearly all the weight, fused IS that view up to fp32
+    // rounding, and the difference of the two sums was rounding noise of sum |G I| (seven decades above the value for uncertainties
+    // 16 apart; nonzero even for a single view).  So everything is taken relative to the PIVOT view p of largest weight:
+    //     fused - I_p = delta = sum_v s_v (I_v - I_p)          I_v - fused = (I_v - I_p) - delta          s_v = w_v / W
+    // whose terms are differences of stored values (exact or one rounding) and the pivot's own term is exactly 0; for v != p,
+    // s_v <= 1/2 bounds what (I_v - I_p) and delta can cancel of each other.  s_v by a true division: exactly 1 for a single view,
+    // whose d uncert is then exactly 0.
     float w[PSCV_MAX_SRC], acc[PSCV_MAX_SRC];
     float wsum = 0.f;
+    int piv = 0;
     for (int v = 0; v < a.n_src; ++v) { w[v] = expf(-a.uncert[v][p]); wsum += w[v]; acc[v] = 0.f; }
-    const float inv = 1.0f / wsum;
+    for (int v = 1; v < a.n_src; ++v) piv = w[v] > w[piv] ? v : piv;
+    for (int v = 0; v < a.n_src; ++v) w[v] /= wsum;
     const int per = (a.D + FB_NS - 1) / FB_NS;
     const int d0 = sl * per, d1 = min(a.D, d0 + per);
     for (int d = d0; d < d1; ++d) {
         const long vox = ((long)b * a.D + d) * a.hw + pf;
         const f32x8 G = Elem<H>::load8(reinterpret_cast<const H*>(a.g) + vox * 8);
-        float fused[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const f32x8 xp = Elem<H>::load8(reinterpret_cast<const H*>(a.interm[piv]) + vox * 8);
+        float delta[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int v = 0; v < a.n_src; ++v) {
             const f32x8 x = Elem<H>::load8(reinterpret_cast<const H*>(a.interm[v]) + vox * 8);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) fused[j] = fmaf(x.v[j], w[v], fused[j]);
+            for (int j = 0; j < 8; ++j) delta[j] = fmaf(x.v[j] - xp.v[j], w[v], delta[j]);
         }
         float gf = 0.f;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) gf = fmaf(G.v[j], fused[j] * inv, gf);
+        for (int j = 0; j < 8; ++j) gf = fmaf(G.v[j], delta[j], gf);
         for (int v = 0; v < a.n_src; ++v) {
             const f32x8 x = Elem<H>::load8(reinterpret_cast<const H*>(a.interm[v]) + vox * 8);   // (L1/L2 hit: read just above)
             float gi = 0.f;
             f32x8 o;
-            const float s = w[v] * inv;
+            const float s = w[v];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { gi = fmaf(G.v[j], x.v[j], gi); o.v[j] = G.v[j] * s; }
+            for (int j = 0; j < 8; ++j) { gi = fmaf(G.v[j], x.v[j] - xp.v[j], gi); o.v[j] = G.v[j] * s; }
             acc[v] += gi - gf;
             if (active) Elem<H>::store8(reinterpret_cast<H*>(a.dinterm[v]) + vox * 8, o);
         }
@@ -127,7 +138,7 @@ __global__ __launch_bounds__(256) void fuse_pairs_bwd_kernel(const FuseBwdArgs a
             float t = sh[v][0][px];
 #pragma unroll
             for (int i = 1; i < FB_NS; ++i) t += sh[v][i][px];
-            a.duncert[v][p] = -w[v] * inv * t;
+            a.duncert[v][p] = -w[v] * t;
         }
     }
 }

@@ -210,17 +210,28 @@ __host__ __device__ __forceinline__ uint16_t f32_to_f16_bits(float f) {
 typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float f16lo(uint32_t x) { return (float)__builtin_bit_cast(h2_t, x)[0]; }
 __device__ __forceinline__ float f16hi(uint32_t x) { return (float)__builtin_bit_cast(h2_t, x)[1]; }
+// Saturating at +-65504, and a NaN stays NaN.  (The first form clamped with v_med3 before the conversion: v_med3 returns a non-NaN
+// operand, so a NaN activation was stored as -65504 and passed every isfinite check behind it -- the fp16 twin of what relu_floor
+// below fixes.  Selecting the NaN back with v_cmp + v_cndmask per element cost the fp16 forward 1.3 %.)  So: convert first -- the
+// hardware convert gives +-inf exactly for what the clamp would saturate (|x| >= 65520, true inf included) and keeps NaN -- then
+// step the halves that hold +-inf (magnitude bits 0x7c00) down to 0x7bff = 65504 with integer ops on the packed word: `inf` is 1 in
+// such a half and 0 in every other (a saturating 1 - e per half, e = 0 only there), and h - inf does not borrow between the halves.
+// Four ops per pair: v_cvt_pk_f16_f32, v_bitop3, v_pk_sub_u16 clamp, v_sub.
+typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
     h2_t v;
-    v[0] = (_Float16)__builtin_amdgcn_fmed3f(lo, -65504.0f, 65504.0f);
-    v[1] = (_Float16)__builtin_amdgcn_fmed3f(hi, -65504.0f, 65504.0f);
-    return __builtin_bit_cast(uint32_t, v);
+    v[0] = (_Float16)lo;
+    v[1] = (_Float16)hi;
+    const uint32_t h = __builtin_bit_cast(uint32_t, v);
+    const u16x2_t e = __builtin_bit_cast(u16x2_t, (h & 0x7fff7fffu) ^ 0x7c007c00u);
+    const u16x2_t inf = __builtin_elementwise_sub_sat((u16x2_t){1, 1}, e);
+    return h - __builtin_bit_cast(uint32_t, inf);
 }
 
-// Saturating fp32 -> fp16 stores without the two v_med3 clamps per pair: with MODE.FP16_OVFL set (once per wave, at kernel entry)
+// Saturating fp32 -> fp16 stores without the fix-up ops of pack_f16x2: with MODE.FP16_OVFL set (once per wave, at kernel entry)
 // the hardware conversion clamps an overflowing result to +-65504 itself.  Kernels that call fp16_ovfl_mode() may pack with
 // pack_f16x2_ovfl(); everything else keeps pack_f16x2().
-// Exception: the mode clamps OVERFLOWING FINITE results only -- a true +-inf input stays +-inf (pack_f16x2's med3 clamp stores
+// Exception: the mode clamps OVERFLOWING FINITE results only -- a true +-inf input stays +-inf (pack_f16x2 stores
 // +-65504 for it).  On the engine's own path no stored tensor can hold inf (every 16-bit store saturates), so the difference is
 // reachable only through caller-supplied feature maps that already contain inf; tests/test_gpu_warp_cost.py pins that behaviour.
 // The conversions carry no dependency on MODE, so nothing may be scheduled across the s_setreg: sched_barrier right behind it.

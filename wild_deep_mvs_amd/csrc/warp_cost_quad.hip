@@ -68,7 +68,7 @@ __device__ __forceinline__ void q2_mix8(const uint4 (&t)[4], const float (&w)[4]
     }
 }
 
-// (not wl_store8: that packs fp16 without the v_med3_f32 clamp, under the MODE.FP16_OVFL bit this kernel does not set)
+// (not wl_store8: that packs fp16 without pack_f16x2's saturation, under the MODE.FP16_OVFL bit this kernel does not set)
 template <typename TOut> __device__ __forceinline__ void q2_store8(char* p, const float (&o)[8]) {
     if constexpr (sizeof(TOut) == 4) {
         *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);

@@ -41,7 +41,7 @@ template <bool MAX> __device__ __forceinline__ float wl_wave_reduce(float x) {
 
 // fp16 stores saturate at +-65504 like every other kernel of the engine (pscv_common.h), but through the MODE.FP16_OVFL bit the
 // kernel sets at its start ("an overflowed FP16 result is clamped to +-MAX_FP16 ... preserving true INF"): the per-element
-// v_med3_f32 clamp of pack_f16x2 costs 8 vector-ALU instructions per voxel here, 5 % of the sweep
+// saturation of pack_f16x2 (then a v_med3_f32 per element) cost 8 vector-ALU instructions per voxel here, 5 % of the sweep
 template <typename TOut> __device__ __forceinline__ uint32_t wl_pack2(float lo, float hi) {
     if constexpr (Half16<TOut>::dtype == PSCV_F16) {
         h2_t v;
