@@ -8,7 +8,13 @@
 //   * Plane-pair packing: C_out = 8 fills only half of the 16 MFMA rows, so rows 0-7 compute output plane d
 //     and rows 8-15 output plane d+1.  An input plane p feeds plane d with kernel slice kd = p-d+1 and plane
 //     d+1 with kd = p-d, so 4 input planes x 9 (kh,kw) taps = 36 MFMAs produce TWO output planes
-//     (18 per plane instead of 27), and all 64 lanes end with a useful 8-byte store.
+//     (18 per plane instead of 27).  Store side: one buffer descriptor per plane pair (base = output plane d, range = the one
+//     or two planes of the pair this chunk owns) and per-lane 32-bit offsets made once per sweep -- rows / columns beyond the
+//     volume carry an out-of-range offset and the hardware drops their stores: no 64-bit arithmetic, no bounds branch per pair.
+//     16-bit outputs whose voxels are 16-byte addressable leave as ONE 16-byte store per lane: the two 16-lane rows (g, g ^ 1)
+//     hold channels 0-3 / 4-7 of the same voxels for the wave's two pixel rows and swap halves (v_permlane16_swap), so that
+//     even g stores the whole voxel of pixel row 0 and odd g that of pixel row 1.  Other 16-bit slices keep 8-byte stores and
+//     fp32 outputs their float4 stores, through the same descriptor.
 //   * All 36 A fragments (144 VGPRs) stay in registers for the whole sweep: no weight traffic in the loop.
 //   * LDS voxels are 64 B (32 ch x 16 bit) with the XOR swizzle chunk ^= ((voxel >> 2) & 1) << 1, which makes
 //     every ds_read_b128 B-fragment read conflict-free for any tap offset (brute-forced over the gfx950
@@ -28,12 +34,15 @@ struct SweepArgs : ConvIO {     // wpk: [4 p_rel][9 taps][64 lanes][8]
     int in2_cs, in2_co;      // 16-channel input; another tensor for pscv_conv3d_cat2: torch.cat([a, b], channel) never materialised)
     int nth, ntw, ndc, dc;   // tiles along h, w; depth chunks and planes per chunk (even)
     unsigned mg_th, mg_tw, mg_dc;
+    int st16;                // 32 -> 8 plane-pair kernel: 16-bit output voxels are 16-byte addressable (one 16-byte store per voxel)
 };
 
 PSCV_PROF_BUFFER(sweep)
 constexpr int SW_BW = 18;
 constexpr int SW_VB = 64;                  // bytes per voxel (32 ch x 2 B)
 constexpr int SW_NSLOT = 6;
+typedef unsigned sw_u32x4 __attribute__((ext_vector_type(4)));   // payloads of the raw buffer stores
+typedef unsigned sw_u32x2 __attribute__((ext_vector_type(2)));
 // Tile height TH (rows) is a template parameter: TH = 8 -> 256 threads, 70 KiB ring, two workgroups per CU;
 // TH = 16 -> 512 threads, 123 KiB ring, one workgroup per CU but 18/16 instead of 10/8 halo rows per tile.
 template <int TH> struct SwGeom {
@@ -50,7 +59,9 @@ __device__ __forceinline__ int sw_lds_off(int v, int chunk) {   // v = in-plane 
     return v * SW_VB + ((chunk ^ (((v >> 2) & 1) << 1)) << 4);
 }
 
-template <typename H, int SW_TH>
+// HOT: the epilogue of MVSNet's conv0 at compile time -- BN + ReLU, no residual, 16-bit output in 16-byte voxels; every other
+// combination reads its flags from the argument block (wave-uniform branches).
+template <typename H, int SW_TH, bool HOT>
 __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const SweepArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     using G = SwGeom<SW_TH>;
@@ -134,6 +145,38 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
         bi[k] = a.bias ? a.bias[c0 + k] : 0.0f;
         fl[k] = a.floor ? a.floor[c0 + k] : 0.0f;
     }
+    const bool out_f32 = !HOT && a.out_f32, has_skip = !HOT && a.skip != nullptr, st16 = HOT || a.st16;
+    const bool relu_pre = HOT || (a.epi & PSCV_EPI_RELU_PRE), relu_post = !HOT && (a.epi & PSCV_EPI_RELU_POST);
+
+    // ---- store descriptors: the mirror of `fetch` ----
+    // The descriptor of a plane pair starts at output plane d of this batch item and covers plane d, and plane d + 1 if this chunk
+    // owns it; a lane's byte offset (made once, here) is its voxel inside plane d plus one plane for the lanes of plane d + 1
+    // (g >> 1).  Rows beyond Hh and columns beyond W carry an out-of-range constant, plane d + 1 beyond dend lies beyond the
+    // range: the hardware drops those stores (and returns zeros for the residual, which then goes nowhere).
+    constexpr unsigned OOR = 0x7ffffff0u;
+    const unsigned oes = out_f32 ? 4u : 2u;
+    const long oplane_b = (long)a.Hh * a.W * a.out_cs * oes, splane_b = (long)a.Hh * a.W * a.skip_cs * 2;
+    const char* outb = reinterpret_cast<const char*>(a.out) + (long)b * a.D * oplane_b + a.out_co * oes;
+    const char* skb = reinterpret_cast<const char*>(a.skip) + (long)b * a.D * splane_b + a.skip_co * 2;
+    unsigned ooff[R], soff[R], ooff16;
+    {
+        const int ow = w0 + n;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int oh = h0 + row0 + r;
+            const bool ok = oh < a.Hh && ow < a.W;
+            const unsigned pix = (unsigned)(oh * a.W + ow);
+            ooff[r] = ok ? (unsigned)(g >> 1) * (unsigned)oplane_b + (pix * (unsigned)a.out_cs + (unsigned)c0) * oes : OOR;
+            soff[r] = ok && has_skip ? (unsigned)(g >> 1) * (unsigned)splane_b + (pix * (unsigned)a.skip_cs + (unsigned)c0) * 2u : OOR;
+        }
+        // 16-byte stores: even g owns the whole voxel (channels 0..7) of pixel row 0, odd g that of pixel row 1
+        const int oh = h0 + row0 + (g & 1);
+        ooff16 = oh < a.Hh && ow < a.W ? (unsigned)(g >> 1) * (unsigned)oplane_b + (unsigned)(oh * a.W + ow) * (unsigned)a.out_cs * 2u : OOR;
+    }
+    auto pair_rsrc = [&](const char* base, long plane_b, int co_b, int d) {                   // wave-uniform
+        const int np = min(2, dend - d);
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base + d * plane_b), (short)0, (int)(np * plane_b - co_b), 0x00020000);
+    };
 
     // ---- prologue: planes dbeg-1 .. dbeg+2 into ring slots 0..3 ----
     {
@@ -177,35 +220,45 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
         }
 
         PSCV_STAMP(2)
-        // epilogue: rows g*4.. of D = channels c0.. of plane d + (g >> 1)
-        const int od = d + (g >> 1);
+        // epilogue: rows g*4.. of D = channels c0.. of plane d + (g >> 1); every lane runs it, the descriptor decides what lands
+        const __amdgpu_buffer_rsrc_t ors = pair_rsrc(outb, oplane_b, (int)(a.out_co * oes), d);
+        uint2 sv[R];
+        if (has_skip) {
+            const __amdgpu_buffer_rsrc_t srs = pair_rsrc(skb, splane_b, a.skip_co * 2, d);
+#pragma unroll
+            for (int r = 0; r < R; ++r) sv[r] = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(srs, (int)soff[r], 0, 0));
+        }
+        uint2 pk[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int oh = h0 + row0 + r, ow = w0 + n;
-            if (od < dend && oh < a.Hh && ow < a.W) {
-                const long vox = (((long)b * a.D + od) * a.Hh + oh) * a.W + ow;
-                float y[4];
+            float y[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    y[k] = fmaf(acc[r][k], sc[k], bi[k]);
-                    if (a.epi & PSCV_EPI_RELU_PRE) y[k] = relu_floor(y[k], fl[k]);
-                }
-                if (a.skip) {
-                    const uint2 sv = *reinterpret_cast<const uint2*>(a.skip + vox * a.skip_cs + a.skip_co + c0);
-                    y[0] += Half16<H>::lo(sv.x); y[1] += Half16<H>::hi(sv.x);
-                    y[2] += Half16<H>::lo(sv.y); y[3] += Half16<H>::hi(sv.y);
-                }
-                if (a.epi & PSCV_EPI_RELU_POST) {
+            for (int k = 0; k < 4; ++k) {
+                y[k] = fmaf(acc[r][k], sc[k], bi[k]);
+                if (relu_pre) y[k] = relu_floor(y[k], fl[k]);
+            }
+            if (has_skip) {
+                y[0] += Half16<H>::lo(sv[r].x); y[1] += Half16<H>::hi(sv[r].x);
+                y[2] += Half16<H>::lo(sv[r].y); y[3] += Half16<H>::hi(sv[r].y);
+            }
+            if (relu_post) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], 0.0f);
-                }
-                if (a.out_f32) {
-                    *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + vox * a.out_cs + a.out_co + c0) =
-                        make_float4(y[0], y[1], y[2], y[3]);
-                } else {
-                    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + vox * a.out_cs + a.out_co + c0) =
-                        make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
-                }
+                for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], 0.0f);
+            }
+            if (out_f32)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sw_u32x4, make_float4(y[0], y[1], y[2], y[3])), ors, (int)ooff[r], 0, 0);
+            else
+                pk[r] = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
+        }
+        if (!out_f32) {
+            if (st16) {
+                // odd rows of pk[0] <-> even rows of pk[1]: even g = [own row 0 | partner's row 0], odd g = [partner's row 1 | own row 1]
+                const auto rx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
+                const auto ry = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
+                __builtin_amdgcn_raw_buffer_store_b128(sw_u32x4{rx[0], ry[0], rx[1], ry[1]}, ors, (int)ooff16, 0, 0);
+            } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) __builtin_amdgcn_raw_buffer_store_b64(sw_u32x2{pk[r].x, pk[r].y}, ors, (int)ooff[r], 0, 0);
             }
         }
 
@@ -709,6 +762,7 @@ static void sweep_args(SweepArgs& a, const ConvCall& c, int th) {
     a.D = c.D; a.Hh = c.H; a.W = c.W; a.epi = c.epi;
     a.nth = (c.H + th - 1) / th;
     a.ntw = (c.W + 15) / 16;
+    a.st16 = 0;
 }
 
 // pscv_conv3d, kind S1P8 with (c_in, c_out) = (8, 8), (16, 8) or (16, 16), and pscv_conv3d_cat2
@@ -741,6 +795,14 @@ int conv3d_sweep8_launch(const ConvCall& c) {
     SweepArgs a;
     sweep_args(a, c, tall ? 16 : 8);
     const long tiles = (long)a.B * a.nth * a.ntw;
+    if (!kdm) {
+        // the plane-pair kernel stores (and reads the residual) through one descriptor per plane pair with 32-bit lane offsets
+        PSCV_CHECK_ARG(2L * c.H * c.W * c.io.out_cs * (c.io.out_f32 ? 4 : 2) < 0x7ffffff0L,
+                       "pscv_conv3d(sweep): two output planes of %d x %d x %d channels exceed 2 GiB", c.H, c.W, c.io.out_cs);
+        PSCV_CHECK_ARG(!c.io.skip || 2L * c.H * c.W * c.io.skip_cs * 2 < 0x7ffffff0L,
+                       "pscv_conv3d(sweep): two residual planes of %d x %d x %d channels exceed 2 GiB", c.H, c.W, c.io.skip_cs);
+        a.st16 = !c.io.out_f32 && c.io.out_cs % 8 == 0 && c.io.out_co % 8 == 0 && (reinterpret_cast<uintptr_t>(c.io.out) & 15) == 0;
+    }
     if (kdm) {
 #ifdef PSCV_ABLATE
         a.in2_cs = g_fuse_c0;   // ablation flags: 1 no plane fetch, 2 no stores, 4 no LDS reads / MFMAs (scripts/dev/kdm_bench.py --ablate)
@@ -766,8 +828,11 @@ int conv3d_sweep8_launch(const ConvCall& c) {
                                         : launch(what, conv3d_sweep8_kdm_kernel<H, false, 2>, grid, dim3(256), KM_LDS, c.st, a);
         if (kdm) return skip ? launch(what, conv3d_sweep8_kdm_kernel<H, true, 1>, grid, dim3(256), KM_LDS, c.st, a)
                              : launch(what, conv3d_sweep8_kdm_kernel<H, false, 1>, grid, dim3(256), KM_LDS, c.st, a);
-        return tall ? launch(what, conv3d_sweep8_kernel<H, 16>, grid, dim3(512), SwGeom<16>::LDS, c.st, a)
-                    : launch(what, conv3d_sweep8_kernel<H, 8>, grid, dim3(256), SwGeom<8>::LDS, c.st, a);
+        if (tall) return launch(what, conv3d_sweep8_kernel<H, 16, false>, grid, dim3(512), SwGeom<16>::LDS, c.st, a);
+        // MVSNet's conv0 (BN + ReLU, no residual, plain 16-bit output): its epilogue flags are compile-time constants
+        const bool hot = a.st16 && !skip && (c.epi & (PSCV_EPI_RELU_PRE | PSCV_EPI_RELU_POST)) == PSCV_EPI_RELU_PRE;
+        return hot ? launch(what, conv3d_sweep8_kernel<H, 8, true>, grid, dim3(256), SwGeom<8>::LDS, c.st, a)
+                   : launch(what, conv3d_sweep8_kernel<H, 8, false>, grid, dim3(256), SwGeom<8>::LDS, c.st, a);
     });
 }
 
