@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Phase timing of the regulariser's conv kernels with a -DPSCV_PROFILE build of libpscv (cycle stamps per workgroup).
 Build:  bash scripts/dev/ab_build.sh prof "conv3d.hip conv3d_c1.hip conv3d_t2p8.hip" -DPSCV_PROFILE
-Run:    PSCV_LIB=$PWD/scripts/dev/libpscv_prof.so python scripts/dev/phase_prof.py [layer ...]"""
+Run:    PSCV_LIB=$PWD/scripts/dev/libpscv_prof.so python scripts/dev/phase_prof.py [--bf16] [layer ...]"""
 import ctypes
 import os
 import sys
@@ -16,7 +16,8 @@ L.LIB_PATH = os.environ["PSCV_LIB"]
 from wild_deep_mvs_amd import ops  # noqa: E402
 
 dev = "cuda"
-dt = torch.float16
+dt = torch.bfloat16 if "--bf16" in sys.argv else torch.float16
+LAYER_ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 D, h, w = 192, 128, 160
 g = torch.Generator().manual_seed(0)
 # name, c_in, c_out, kind, input scale, transposed, skip?, getter tag
@@ -32,9 +33,9 @@ LAYERS = {
     "cvp64": (64, 64, 0, (4, 512, 640), False, False, "wide"),
     "cvp16": (16, 16, 0, (8, 1024, 1280), False, False, "conv"),   # CVP conv0a at the finest level (brick kernel, 4x4x16 tiles)   # CVP refinement 64 -> 64 at 4 x 512 x 640 (4x4x16 tiles, all 4 N-tiles)
 }
-NAMES = ["loads issued", "loads landed", "LDS write+sync", "MFMA loop", "epilogue", "drain"]
+NAMES = ["loads issued", "loads landed", "LDS write+sync", "MFMA loop", "epilogue", "drain", "prologue"]   # (prologue: the brick kernel only)
 lib = L.lib()
-for name in sys.argv[1:] or list(LAYERS):
+for name in LAYER_ARGS or list(LAYERS):
     ci, co, kind, s, tr, sk, tag = LAYERS[name]
     shp = s if isinstance(s, tuple) else (D // s, h // s, w // s)
     x = (torch.randn(1, *shp, ci, generator=g) * 0.5).to(dt).to(dev)
@@ -71,15 +72,15 @@ for name in sys.argv[1:] or list(LAYERS):
         base_of[keep] = r[keep, 6].min()
     r, xcc, base_of = r[valid], xcc[valid], base_of[valid]
     nblk = len(r)
-    ph = r[:, :6]
+    ph = np.concatenate([r[:, :6], r[:, 10:11]], axis=1)     # phase 6 is kept in word 10 (pscv_common.h)
     t0, t1 = r[:, 6] - base_of, r[:, 7] - base_of
     span = t1.max()
     key = ((xcc * 8 + ((r[:, 8] >> 13) & 7)) * 2 + ((r[:, 8] >> 12) & 1)) * 16 + ((r[:, 8] >> 8) & 0xf)
     ncu = len(np.unique(key))
-    print(f"{name} ({ci}->{co}, kind {layer.kind}): {us:.1f} us  {nblk} workgroups profiled on {ncu} CUs / {len(np.unique(xcc))} XCDs, "
+    print(f"{name} ({ci}->{co}, kind {layer.kind}, {str(dt)[6:]}): {us:.1f} us  {nblk} workgroups profiled on {ncu} CUs / {len(np.unique(xcc))} XCDs, "
           f"launch span {span} ticks ({span / us:.0f} ticks/us if the span were the whole kernel)")
     tot = ph.sum(1)
-    print("   mean ticks per workgroup (wave 0): total %7.0f | " % tot.mean() + "  ".join(f"{NAMES[i]} {ph[:, i].mean():6.0f}" for i in range(6)))
+    print("   mean ticks per workgroup (wave 0): total %7.0f | " % tot.mean() + "  ".join(f"{NAMES[i]} {ph[:, i].mean():6.0f}" for i in range(7)))
     print(f"   resident workgroups per CU (sum lifetimes / span / CUs): {(t1 - t0).sum() / span / ncu:.2f};  workgroup start times "
           f"p10 {np.percentile(t0, 10):.0f}  p50 {np.percentile(t0, 50):.0f}  p90 {np.percentile(t0, 90):.0f}  max {t0.max()};  end p50 "
           f"{np.percentile(t1, 50):.0f} max {t1.max()}")

@@ -105,7 +105,15 @@ __device__ __noinline__ void epi_ragged(float y0, float y1, float y2, float y3, 
     }
 }
 
-template <typename H, int CIN, int NT, int KIND, int TD, int TH>
+typedef unsigned cv_u32x2 __attribute__((ext_vector_type(2)));   // payload of the raw buffer stores
+
+// HOT: the store side of the layers the U-Nets run -- 16-bit output, c_out a multiple of 16, output and skip slice of a batch item
+// below 2 GiB and 8-byte aligned (chosen on the host, launch_conv).  Output and skip tensor are addressed through one buffer
+// descriptor each, made once per workgroup from the batch item's base: a lane's 32-bit byte offset inside a row is made once (lanes
+// beyond the volume carry an out-of-range offset: the hardware drops their stores and zero-fills their loads), the wave-uniform row
+// offset is the instruction's scalar offset, and the epilogue has no flag, bounds or channel-count branch.  Every other call runs the
+// general instance: flat 64-bit addresses, run-time flags, epi_ragged.  The arithmetic of the two is the same, operation by operation.
+template <typename H, int CIN, int NT, int KIND, int TD, int TH, bool HOT>
 __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
     using BR = Brick<KIND, TD, TH>;
     constexpr int BD = BR::BD, BH = BR::BH, BW = BR::BW;
@@ -119,6 +127,15 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     PSCV_PROF_BEGIN
+
+    // The argument block in ONE burst of scalar loads.  Left to itself the compiler fetches each field where it is first used, behind
+    // the branches of the tile decode and the fetch lambdas: some fifteen dependent s_load / s_waitcnt round trips, 2.7 K of a
+    // workgroup's 10-14 K cycles before its first weight load went out (scripts/dev/phase_prof.py, slot "prologue").  Naming the
+    // fields as scalar inputs of an empty asm makes them live here, all at once.
+    asm volatile("" ::"s"(a.in), "s"(a.wpk), "s"(a.scale), "s"(a.bias), "s"(a.floor), "s"(a.skip), "s"(a.out), "s"(a.epi), "s"(a.in_cs),
+                 "s"(a.in_co), "s"(a.skip_cs), "s"(a.skip_co), "s"(a.out_cs), "s"(a.out_co), "s"(a.Di), "s"(a.Hi), "s"(a.Wi), "s"(a.Do),
+                 "s"(a.Ho), "s"(a.Wo), "s"(a.cout), "s"(a.ntd), "s"(a.nth), "s"(a.ntw), "s"(a.mg_td), "s"(a.mg_th), "s"(a.mg_tw),
+                 "s"(a.nt_total));
 
     // ---- which tile (XCD-aware bijective remap: each XCD gets a contiguous run of tiles) ----
     int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -180,24 +197,49 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
     constexpr int XS = KIND == PSCV_CONV_T2 ? 2 : 1;
     const int ox0 = XS * (t0w + n);                                 // lane's output x (pw = 0)
     const int cg = nt0 * 16 + g * 4;                                // lane's first channel in N-tile 0
-    const unsigned lane_out = (unsigned)(ox0 * a.out_cs + cg), lane_skip = (unsigned)(ox0 * a.skip_cs + cg);
+    // Row offsets (RowT): elements from the tensor's start in the general instance, bytes from the descriptor's base (the batch
+    // item's first voxel, channel offset included) in the HOT one, where they fit 32 bits.
+    using RowT = std::conditional_t<HOT, unsigned, long>;
+    constexpr int EB = HOT ? 2 : 1;
+    constexpr unsigned OOR = 0x80000000u;   // beyond any HOT descriptor's range (< 0x7fff0000 bytes), and OOR + row + tile offset does not wrap 32 bits
     const bool lane_ok = t0w + n < (KIND == PSCV_CONV_T2 ? a.Wi : a.Wo);
-    const long plane_out = (long)a.Ho * a.Wo * a.out_cs, plane_skip = (long)a.Ho * a.Wo * a.skip_cs;
-    const int row_out = a.Wo * a.out_cs, row_skip = a.Wo * a.skip_cs;
+    const unsigned lane_out = HOT && !lane_ok ? OOR : (unsigned)(ox0 * a.out_cs + cg) * EB;
+    const unsigned lane_skip = HOT && !lane_ok ? OOR : (unsigned)(ox0 * a.skip_cs + cg) * EB;
+    const RowT plane_out = (RowT)((long)a.Ho * a.Wo * a.out_cs * EB), plane_skip = (RowT)((long)a.Ho * a.Wo * a.skip_cs * EB);
+    using StrideT = std::conditional_t<HOT, unsigned, int>;
+    const StrideT row_out = (StrideT)(a.Wo * a.out_cs * EB), row_skip = (StrideT)(a.Wo * a.skip_cs * EB);
     const int bDo = b * a.Do;
-    const bool cout4 = (a.cout & 3) == 0;
-    auto out_row = [&](int od, int oh) -> long { return (long)(bDo + od) * plane_out + (long)oh * row_out + a.out_co; };
-    auto skip_row = [&](int od, int oh) -> long { return (long)(bDo + od) * plane_skip + (long)oh * row_skip + a.skip_co; };
-    auto skip_fetch = [&](long srow, int pw, int m) -> uint2 {           // srow: wave-uniform row inside the volume
+    const bool cout4 = HOT || (a.cout & 3) == 0;
+    __amdgpu_buffer_rsrc_t ors, srs;
+    if constexpr (HOT) {
+        const long item_out = (long)a.Do * a.Ho * a.Wo * a.out_cs, item_skip = (long)a.Do * a.Ho * a.Wo * a.skip_cs;   // elements
+        ors = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint16_t*>(a.out) + (long)b * item_out + a.out_co, (short)0,
+                                                (int)((item_out - a.out_co) * 2), 0x00020000);
+        srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.skip) + (a.skip ? (long)b * item_skip + a.skip_co : 0), (short)0,
+                                                a.skip ? (int)((item_skip - a.skip_co) * 2) : 0, 0x00020000);
+    }
+    auto out_row = [&](int od, int oh) -> RowT {
+        if constexpr (HOT) return (unsigned)od * plane_out + (unsigned)oh * row_out;
+        else return (long)(bDo + od) * plane_out + (long)oh * row_out + a.out_co;
+    };
+    auto skip_row = [&](int od, int oh) -> RowT {
+        if constexpr (HOT) return (unsigned)od * plane_skip + (unsigned)oh * row_skip;
+        else return (long)(bDo + od) * plane_skip + (long)oh * row_skip + a.skip_co;
+    };
+    auto skip_fetch = [&](RowT srow, int pw, int m) -> uint2 {           // srow: wave-uniform row inside the volume
         uint2 sv = make_uint2(0u, 0u);
-        if (a.skip && cout4) {
+        if constexpr (HOT) {
+            if (a.skip)
+                sv = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(srs, (int)(lane_skip + (unsigned)(m * 32)),
+                                                                                    (int)(srow + (unsigned)(pw * a.skip_cs * 2)), 0));
+        } else if (a.skip && cout4) {
             if (lane_ok && cg + m * 16 < a.cout)
                 sv = *reinterpret_cast<const uint2*>(a.skip + srow + (lane_skip + (unsigned)(pw * a.skip_cs + m * 16)));
         }
         return sv;
     };
     // class split: rows of the wave's outputs relative to the tile origin (od = 2 t0d + pd, oh = 2 (t0h + i) + ph)
-    const long cs_orow0 = CSPLIT ? out_row(2 * t0d, 2 * t0h) : 0, cs_srow0 = CSPLIT ? skip_row(2 * t0d, 2 * t0h) : 0;
+    const RowT cs_orow0 = CSPLIT ? out_row(2 * t0d, 2 * t0h) : 0, cs_srow0 = CSPLIT ? skip_row(2 * t0d, 2 * t0h) : 0;
     auto cls_fetch = [&](auto pcc, auto woffc, auto soffc) {
         constexpr int pc = decltype(pcc)::value, WOFF = decltype(woffc)::value, SOFF = decltype(soffc)::value;
         constexpr int nsteps = t2_nsteps(pc, CIN), sbase = t2_stepbase(pc, CIN);
@@ -212,7 +254,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
             const bool in_ok = id < a.Di && ih < a.Hi;     // wave-uniform
 #pragma unroll
             for (int m = 0; m < NT; ++m)
-                skc[SOFF + i][m] = in_ok ? skip_fetch(cs_srow0 + (pd ? plane_skip : 0) + (2 * i + ph) * row_skip, pw, m) : make_uint2(0u, 0u);
+                skc[SOFF + i][m] = in_ok ? skip_fetch(cs_srow0 + (pd ? plane_skip : (RowT)0) + (2 * i + ph) * row_skip, pw, m) : make_uint2(0u, 0u);
         }
     };
     if constexpr (CSPLIT) {
@@ -231,7 +273,17 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
             skk[m] = (od < a.Do && oh < a.Ho) ? skip_fetch(skip_row(od, oh), 0, m) : make_uint2(0u, 0u);
         }
     }
-    PSCV_STAMP(5)   // (profile builds: slot 5 = weight / skip fetches issued + the final drain)
+    // per-channel epilogue constants of this block's NT output tiles: requested here, ahead of the brick, and written to LDS with it
+    // (requested behind the brick, their round trip stood between the last brick write and the barrier)
+    float e_sc = 1.0f, e_bi = 0.0f, e_fl = (a.epi & PSCV_EPI_RELU_PRE) ? 0.0f : -__builtin_inff();
+    if (tid < NT * 16) {
+        const int c = nt0 * 16 + tid;
+        const bool cv = c < a.cout;
+        if (a.scale && cv) e_sc = a.scale[c];
+        if (a.bias && cv) e_bi = a.bias[c];
+        if ((a.epi & PSCV_EPI_RELU_PRE) && a.floor && cv) e_fl = a.floor[c];
+    }
+    PSCV_STAMP(6)   // (profile builds: slot 6 = tile decode, weight / skip fetches issued; slot 5 is the final drain alone)
 
     // ---- stage the input brick into LDS (zero fill outside the volume = the conv's padding) ----
     // A thread owns the same in-plane positions (row, column, 16-byte channel chunk) in EVERY plane of the brick: their
@@ -283,17 +335,15 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
                         *reinterpret_cast<uint4*>(smem + (p0 + pp) * (BH * BW * VS) + lds_off[sl]) = val[pp][sl];
         }
     }
-    // per-channel epilogue constants of this block's NT output tiles -> LDS (one global read per block)
+    // per-channel epilogue constants -> LDS (one global read per block)
     constexpr int REGION0 = conv_region0(KIND, CIN, NT, TD, TH);   // brick, later reused by the k-split reduction
     float* epi_sc = reinterpret_cast<float*>(smem + REGION0);
     float* epi_bi = epi_sc + NT * 16;
     float* epi_fl = epi_bi + NT * 16;
     if (tid < NT * 16) {
-        const int c = nt0 * 16 + tid;
-        const bool cv = c < a.cout;
-        epi_sc[tid] = (a.scale && cv) ? a.scale[c] : 1.0f;
-        epi_bi[tid] = (a.bias && cv) ? a.bias[c] : 0.0f;
-        epi_fl[tid] = (a.epi & PSCV_EPI_RELU_PRE) ? ((a.floor && cv) ? a.floor[c] : 0.0f) : -__builtin_inff();
+        epi_sc[tid] = e_sc;
+        epi_bi[tid] = e_bi;
+        epi_fl[tid] = e_fl;
     }
     __syncthreads();
     PSCV_STAMP(2)
@@ -313,15 +363,44 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
     // 32-bit offset.  The ReLU switches are folded into clamp constants (epi_fl holds -inf without RELU_PRE, lo_post is -inf
     // without RELU_POST) and a missing skip tensor adds +0, so the common case -- a channel count that is a multiple of 4 --
     // is straight-line code: the epilogue is inlined up to 32 times per kernel and its branches used to dominate the code size.
+    // The HOT instance reads the lane's 12 constants per N-tile into registers once per contraction (epi_consts, called behind the
+    // MFMA loop so that they are not live across it) and not once per row -- up to two N-tiles: the 48 registers of four cost the
+    // large tiles a workgroup per CU, and the class split keeps its reads per row too (its first class's epilogue runs with the second
+    // class's weights and skip values live: 132 instead of 120 VGPRs at 32 -> 16, a workgroup per CU).  Every caller hands it the
+    // skip values.
     const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
-    auto epilogue_row = [&](const f32x4 (&acc)[NT], long orow, long srow, int pw, const uint2* pre) {
+    constexpr bool CREG = HOT && NT < 4 && !CSPLIT;
+    float4 hsc[CREG ? NT : 1], hbi[CREG ? NT : 1], hfl[CREG ? NT : 1];
+    auto epi_consts = [&]() {
+        if constexpr (CREG) {
+#pragma unroll
+            for (int m = 0; m < NT; ++m) {
+                hsc[m] = *reinterpret_cast<const float4*>(epi_sc + m * 16 + g * 4);
+                hbi[m] = *reinterpret_cast<const float4*>(epi_bi + m * 16 + g * 4);
+                hfl[m] = *reinterpret_cast<const float4*>(epi_fl + m * 16 + g * 4);
+            }
+        }
+    };
+    auto epilogue_row = [&](const f32x4 (&acc)[NT], RowT orow, RowT srow, int pw, const uint2* pre) {
 #pragma unroll
         for (int m = 0; m < NT; ++m) {
-            const float4 sc = *reinterpret_cast<const float4*>(epi_sc + m * 16 + g * 4);
-            const float4 bi = *reinterpret_cast<const float4*>(epi_bi + m * 16 + g * 4);
-            const float4 fl = *reinterpret_cast<const float4*>(epi_fl + m * 16 + g * 4);
+            float4 sc, bi, fl;
+            if constexpr (CREG) { sc = hsc[m]; bi = hbi[m]; fl = hfl[m]; }
+            else {
+                sc = *reinterpret_cast<const float4*>(epi_sc + m * 16 + g * 4);
+                bi = *reinterpret_cast<const float4*>(epi_bi + m * 16 + g * 4);
+                fl = *reinterpret_cast<const float4*>(epi_fl + m * 16 + g * 4);
+            }
             float y[4] = {relu_floor(fmaf(acc[m][0], sc.x, bi.x), fl.x), relu_floor(fmaf(acc[m][1], sc.y, bi.y), fl.y),
                           relu_floor(fmaf(acc[m][2], sc.z, bi.z), fl.z), relu_floor(fmaf(acc[m][3], sc.w, bi.w), fl.w)};
+            if constexpr (HOT) {
+                const uint2 sv = pre[m];
+                y[0] = relu_floor(y[0] + Half16<H>::lo(sv.x), lo_post); y[1] = relu_floor(y[1] + Half16<H>::hi(sv.x), lo_post);
+                y[2] = relu_floor(y[2] + Half16<H>::lo(sv.y), lo_post); y[3] = relu_floor(y[3] + Half16<H>::hi(sv.y), lo_post);
+                __builtin_amdgcn_raw_buffer_store_b64(cv_u32x2{Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3])}, ors,
+                                                      (int)(lane_out + (unsigned)(m * 32)), (int)(orow + (unsigned)(pw * a.out_cs * 2)), 0);
+                continue;
+            }
             const unsigned lo = lane_out + (unsigned)(pw * a.out_cs + m * 16), ls = lane_skip + (unsigned)(pw * a.skip_cs + m * 16);
             if (lane_ok && cg + m * 16 < a.cout) {
                 if (cout4) {
@@ -379,6 +458,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
             }
         }
         PSCV_STAMP(3)
+        epi_consts();
         // partial sums -> LDS (over the brick, which every wave has finished reading), summed in wave order 0..3
         __syncthreads();
         f32x4* red = reinterpret_cast<f32x4*>(smem);       // [source wave][M-tile][N-tile][lane]
@@ -421,12 +501,13 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
                 }
             }
             PSCV_STAMP(3)
+            epi_consts();
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int id = t0d + i / TH, ih = t0h + i % TH;
                 if (id < a.Di && ih < a.Hi)
-                    epilogue_row(acc[i], cs_orow0 + (pd ? plane_out : 0) + (2 * i + ph) * row_out,
-                                 cs_srow0 + (pd ? plane_skip : 0) + (2 * i + ph) * row_skip, pw, skc[SOFF + i]);
+                    epilogue_row(acc[i], cs_orow0 + (pd ? plane_out : (RowT)0) + (2 * i + ph) * row_out,
+                                 cs_srow0 + (pd ? plane_skip : (RowT)0) + (2 * i + ph) * row_skip, pw, skc[SOFF + i]);
             }
             PSCV_STAMP(4)
         };
@@ -473,6 +554,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
             }
         }
         PSCV_STAMP(3)
+        epi_consts();
 #pragma unroll
         for (int i = 0; i < MB; ++i) {
             const int mt = wave * MB + i;
@@ -519,6 +601,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
                 }
             }
             PSCV_STAMP(3)
+            epi_consts();
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
                 const int mt = wave * MB + i;
@@ -542,7 +625,15 @@ static int launch_conv(ConvArgs& a, int n_split, hipStream_t st) {
     a.ntd = ceil_div(rd, TD); a.nth = ceil_div(rh, TH); a.ntw = ceil_div(rw, 16);
     const long nblk = finish_grid("pscv_conv3d", a.B, a.ntd, a.nth, a.ntw, a.mg_td, a.mg_th, a.mg_tw);
     if (nblk < 0) return -1;
-    return launch("pscv_conv3d", conv3d_kernel<H, CIN, NT, KIND, TD, TH>, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
+    // the descriptor instance: 32-bit byte offsets inside a batch item's output / skip slice, 8-byte loads and stores
+    // (not for the 4 x 4 x 16 tile of 32 -> 64: 264 instead of 248 registers would cost it the second workgroup per CU)
+    constexpr bool HOT_FITS = !(KIND == PSCV_CONV_S1 && CIN == 32 && NT == 4 && TD == 4 && TH == 4);
+    const long vox = (long)a.Do * a.Ho * a.Wo;
+    const bool hot = HOT_FITS && !a.out_f32 && a.cout % 16 == 0 && vox * a.out_cs * 2 < 0x7fff0000L && (reinterpret_cast<uintptr_t>(a.out) & 7) == 0 &&
+                     (!a.skip || (vox * a.skip_cs * 2 < 0x7fff0000L && (reinterpret_cast<uintptr_t>(a.skip) & 7) == 0));
+    if constexpr (HOT_FITS)
+        if (hot) return launch("pscv_conv3d", conv3d_kernel<H, CIN, NT, KIND, TD, TH, true>, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
+    return launch("pscv_conv3d", conv3d_kernel<H, CIN, NT, KIND, TD, TH, false>, dim3((unsigned)nblk, (unsigned)n_split), dim3(256), LDS, st, a);
 }
 
 // Tile choice.  Large volumes: 4x4x16 (S1), 2x2x16 (S2), 2x4x16 input voxels (T2) with all NT output tiles in one
