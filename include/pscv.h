@@ -581,6 +581,52 @@ int pscv_tsdf_emit_faces(const int* info, const int* vincl, const int* fincl, in
 int pscv_tsdf_case_table(unsigned int* table);
 
 /*
+ * Mesh clean-up (an addition to ABI 14: new exports only, no existing signature changes): connected components of an indexed
+ * triangle mesh, removal of small components / degenerate faces / unused vertices with order-preserving compaction, and
+ * area-weighted vertex normals (csrc/mesh_clean.hip).  faces device int32 [n_faces][3], vertex arrays
+ * device [n_vertices][..]; n_vertices < 2^31, 3 n_faces < 2^31; either may be 0 (nothing is launched on an empty grid).  A face
+ * with an index outside [0, n_vertices) is never followed: it joins nothing, is counted nowhere and survives nothing.  All calls
+ * are asynchronous on `stream`, need no workspace and are bit-reproducible (integer atomics; one lane per output elsewhere).
+ *
+ * pscv_mesh_components: two vertices are connected when some face contains both; label[v] = the smallest vertex index of v's
+ * component (a vertex in no face is its own).  Lock-free union-find on `label` (init, hook with compare-and-swap of the larger
+ * root under the smaller, flatten): label[x] <= x throughout, so every walk descends, no lane waits for another, and the result
+ * does not depend on the schedule.  status device int32 [2], ZEROED BY THE CALLER: [0] += the faces with an index out of range,
+ * [1] += the lanes that left a loop at its trip limit (n_vertices + 1: never, unless the kernel is defective).  A face with a
+ * repeated index is legal.
+ *
+ * pscv_mesh_component_sizes: fcount, vcount device int32 [n_vertices], ZEROED BY THE CALLER: fcount[r] += the faces whose first
+ * vertex has label r, vcount[r] += the vertices with label r (so both stay 0 except at roots).
+ *
+ * pscv_mesh_mark: face f survives iff keep_comp[label[faces[f][0]]] != 0 (device uint8 [n_vertices], indexed by label) and, with
+ * drop_degenerate = 1, it is not degenerate: no repeated index, and the fp64 cross product n = (b - a) x (c - a) of its fp32
+ * corners (differences, products and sums each rounded once, n = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0)) is not exactly
+ * (0, 0, 0).  fmark device int32 [n_faces] = 0 / 1; vmark device int32 [n_vertices], ZEROED BY THE CALLER, = 1 where a surviving
+ * face uses the vertex.
+ *
+ * pscv_mesh_compact: fincl, vincl are the INCLUSIVE int32 prefix sums of fmark, vmark and n_faces_out, n_vertices_out their totals.
+ * Surviving vertex v goes to row vincl[v] - 1 of xyz_out fp32 [..][3], rgb_out uint8 [..][3] and, when `normals` is given,
+ * normals_out fp32 [..][3]; surviving face f to row fincl[f] - 1 of faces_out with its indices renumbered the same way: both keep
+ * their relative order.  A row outside the totals is not written.
+ *
+ * pscv_mesh_vertex_normals: corner 3 f + k is vertex faces[f][k]; corner_off device int32 [n_vertices + 1] and corners device int32
+ * [3 n_faces] are the vertex -> corner adjacency in CSR form, every vertex's corners in ASCENDING corner id.  Per vertex the fp64
+ * sum s of the cross products n (above) of its corners' faces, component by component in that order from 0 (a face that names
+ * the vertex twice counts twice), len = sqrt(s0 s0 + s1 s1 + s2 s2), normals[v] = s / len rounded to fp32, (0, 0, 0) when len is 0
+ * or not finite.  |n| is twice the face's area, so the sum is area-weighted; faces oriented to free space give such normals.
+ */
+int pscv_mesh_components(const int* faces, long n_faces, long n_vertices, int* label, int* status, void* stream);
+int pscv_mesh_component_sizes(const int* label, const int* faces, long n_faces, long n_vertices, int* fcount, int* vcount,
+                              void* stream);
+int pscv_mesh_mark(const float* xyz, const int* faces, const int* label, const unsigned char* keep_comp, long n_faces,
+                   long n_vertices, int drop_degenerate, int* fmark, int* vmark, void* stream);
+int pscv_mesh_compact(const float* xyz, const unsigned char* rgb, const float* normals, const int* faces, const int* fmark,
+                      const int* vmark, const int* fincl, const int* vincl, long n_faces, long n_vertices, float* xyz_out,
+                      unsigned char* rgb_out, float* normals_out, int* faces_out, long n_faces_out, long n_vertices_out, void* stream);
+int pscv_mesh_vertex_normals(const float* xyz, const int* faces, const int* corner_off, const int* corners, long n_faces,
+                             long n_vertices, float* normals, void* stream);
+
+/*
  * Scene set-up from a COLMAP sparse model (an addition to ABI 14: new exports only, no existing signature changes): what
  * utils/colmap_utils.py:compute_src_imgs and compute_min_max_depth_yao compute for every YFCC scene (INTEGRATION.md section 2i,
  * csrc/scene_setup.hip).  All arrays are device memory; all calls are asynchronous on `stream`, need no workspace and are

@@ -7,6 +7,11 @@ distance volume (``ops.tsdf_integrate``) whose zero level set is extracted by ma
 ``fuse_tsdf_mesh`` is the step as a function from tensors to a mesh; ``run(dataloader, args)`` has the interface of the other
 evaluation steps and writes ``<data_path>/Meshes/<model>_<nviews>/<model>_<nviews><scene>.ply``.  It is opt-in: nothing else
 calls it, and no other step's output changes.
+
+``clean_mesh`` is the optional step between extraction and the file: small connected components
+(the closed blobs that depth outliers leave in front of and behind the surface), degenerate faces and unused vertices are
+removed, and area-weighted vertex normals are added.  ``run`` applies it only when one of its arguments is set; with none
+set it writes the same bytes as before.
 """
 from __future__ import annotations
 
@@ -102,6 +107,27 @@ def tsdf_options(args):
     return {kw: getattr(args, name) for kw, name in names if getattr(args, name, None) is not None}
 
 
+def clean_mesh(xyz, rgb, faces, *, min_component_faces: int = 0, min_component_fraction: float = 0.0, keep_largest: int = 0,
+               drop_degenerate: bool = False, vertex_normals: bool = False):
+    """(xyz, rgb, faces) of ``fuse_tsdf_mesh`` -> (xyz, rgb, faces, normals): ``ops.mesh_clean`` with the four choices (with all of
+    them at their defaults it only drops the vertices no face uses), then, with ``vertex_normals``, ``ops.mesh_vertex_normals`` of
+    the cleaned mesh (fp32 [V,3], pointing to free space like the faces); normals is None otherwise."""
+    xyz, rgb, faces = ops.mesh_clean(xyz, rgb, faces, min_component_faces=min_component_faces,
+                                     min_component_fraction=min_component_fraction, keep_largest=keep_largest,
+                                     drop_degenerate=drop_degenerate)
+    return xyz, rgb, faces, (ops.mesh_vertex_normals(xyz, faces) if vertex_normals else None)
+
+
+def clean_options(args):
+    """The keyword arguments of ``clean_mesh`` from ``args.tsdf_min_component_faces``, ``tsdf_min_component_fraction``,
+    ``tsdf_keep_largest``, ``tsdf_drop_degenerate`` and ``tsdf_vertex_normals`` (each absent, None or False = off).  Empty = ``run``
+    writes the extracted mesh as it is; any argument set, a 0 included, runs ``clean_mesh``, which at least drops unused vertices."""
+    names = (("min_component_faces", "tsdf_min_component_faces"), ("min_component_fraction", "tsdf_min_component_fraction"),
+             ("keep_largest", "tsdf_keep_largest"), ("drop_degenerate", "tsdf_drop_degenerate"), ("vertex_normals", "tsdf_vertex_normals"))
+    values = ((kw, getattr(args, name, None)) for kw, name in names)
+    return {kw: v for kw, v in values if v is not None and v is not False}
+
+
 def run(dataloader, args):
     folder_name = depth_folder_name(args)
     out_path = Path(args.data_path) / "Meshes" / folder_name
@@ -109,14 +135,20 @@ def run(dataloader, args):
     if outfile.exists() and not args.override:
         print("TSDF mesh already computed")
         return
-    options = tsdf_options(args)
+    options, cleaning = tsdf_options(args), clean_options(args)
     depth_folder = Path(args.data_path) / "IntRes" / "depthmaps" / folder_name / str(args.scene)
     views = [masked_view(args, batch, depth_folder) for batch in dataloader]
     depths, colors, K, R, t = zip(*views)
     with torch.no_grad():
         xyz, rgb, faces = fuse_tsdf_mesh(depths, colors, torch.stack(K), torch.stack(R), torch.stack(t), **options)
+        normals = None
+        if cleaning:
+            xyz, rgb, faces, normals = clean_mesh(xyz, rgb, faces, **cleaning)
     out_path.mkdir(parents=True, exist_ok=True)
-    write_mesh(outfile, xyz, rgb, faces)
+    if normals is None:
+        write_mesh(outfile, xyz, rgb, faces)
+    else:
+        write_mesh(outfile, xyz, rgb, faces, normals)
     if getattr(args, "tsdf_write_points", False):                  # the vertices as the cloud evaluation/metrics.py reads
         points_path = Path(args.data_path) / "Points" / folder_name
         points_path.mkdir(parents=True, exist_ok=True)

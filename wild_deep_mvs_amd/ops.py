@@ -1087,6 +1087,206 @@ def tsdf_extract(state: TsdfVolume, *, origin, voxel: float, min_weight: int = 1
 
 
 # --------------------------------------------------------------------------------------------
+# mesh clean-up: connected components, fragment removal, vertex normals
+# --------------------------------------------------------------------------------------------
+MESH_MAX_INDEX = 2 ** 31 - 1
+
+
+def _mesh_count(value, name, what):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) < 0:
+        raise ValueError(f"{what}: {name} must be an integer >= 0, got {value!r}")
+    return int(value)
+
+
+def _mesh_faces(faces, n_vertices, what):
+    """faces int32 [F,3], 0 <= n_vertices < 2^31, 3 F < 2^31 -> (F, V); every complaint is a ValueError."""
+    if not torch.is_tensor(faces) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be an int32 tensor [F,3], got {getattr(faces, 'dtype', type(faces))} "
+                         f"{tuple(getattr(faces, 'shape', ()))}")
+    V = _mesh_count(n_vertices, "n_vertices", what)
+    F = int(faces.shape[0])
+    if V > MESH_MAX_INDEX or 3 * F > MESH_MAX_INDEX:
+        raise ValueError(f"{what}: {V} vertices and {F} faces do not fit int32 indices (n_vertices, 3 n_faces < 2^31)")
+    return F, V
+
+
+def _mesh_on_gpu(what, **tensors):
+    dev = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be on the GPU (there is no CPU / PyTorch fallback for the kernels)")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if dev is not None and t.device != dev:
+            raise ValueError(f"{what}: {name} is on {t.device}, the other tensors on {dev}")
+        dev = t.device
+
+
+def _mesh_vertices(xyz, rgb, normals, what):
+    if not torch.is_tensor(xyz) or xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{what}: xyz must be an fp32 tensor [V,3], got {getattr(xyz, 'dtype', type(xyz))} {tuple(getattr(xyz, 'shape', ()))}")
+    if rgb is not None and (not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != tuple(xyz.shape)):
+        raise ValueError(f"{what}: rgb must be a uint8 tensor {tuple(xyz.shape)}, got {getattr(rgb, 'dtype', type(rgb))} "
+                         f"{tuple(getattr(rgb, 'shape', ()))}")
+    if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or tuple(normals.shape) != tuple(xyz.shape)):
+        raise ValueError(f"{what}: normals must be an fp32 tensor {tuple(xyz.shape)}, got {getattr(normals, 'dtype', type(normals))} "
+                         f"{tuple(getattr(normals, 'shape', ()))}")
+    return int(xyz.shape[0])
+
+
+def _mesh_status_error(what, bad_faces, trips):
+    if bad_faces:
+        return RuntimeError(f"{what}: {bad_faces} faces have an index outside [0, n_vertices)")
+    return RuntimeError(f"{what}: {trips} lanes reached the trip limit of the union-find (a defect of the kernel, not of the mesh)")
+
+
+def _mesh_components(faces, F, V, status):
+    """The three launches-worth of pscv_mesh_components and pscv_mesh_component_sizes on the current stream; no host read."""
+    dev = faces.device
+    label = torch.empty(V, dtype=torch.int32, device=dev)
+    fcount = torch.zeros(V, dtype=torch.int32, device=dev)
+    vcount = torch.zeros(V, dtype=torch.int32, device=dev)
+    if V == 0:
+        return label, fcount, vcount
+    st = _stream()
+    # per face two unions: a few dependent 4-byte atomic reads each and one compare-and-swap (the floor is the atomic rate, not HBM)
+    rc = _launch("mesh_components", lambda: L.lib().pscv_mesh_components(_p(faces), F, V, _p(label), _p(status), st),
+                 cost=lambda: (12.0 * F + 8.0 * V, 0.0))
+    L.check(rc, "pscv_mesh_components")
+    rc = _launch("mesh_component_sizes", lambda: L.lib().pscv_mesh_component_sizes(_p(label), _p(faces), F, V, _p(fcount), _p(vcount), st),
+                 cost=lambda: (16.0 * F + 4.0 * V, 0.0))
+    L.check(rc, "pscv_mesh_component_sizes")
+    return label, fcount, vcount
+
+
+def mesh_components(faces: torch.Tensor, n_vertices: int):
+    """Connected components of an indexed triangle mesh on the GPU: faces int32 [F,3] over
+    ``n_vertices`` vertices -> (label, fcount, vcount), int32 [n_vertices].  Two vertices are connected when some face contains
+    both; ``label[v]`` is the smallest vertex index of v's component (a vertex in no face is its own); ``fcount[r]`` counts the
+    faces whose first vertex has label r and ``vcount[r]`` the vertices with label r, both 0 except at roots.  A lock-free
+    union-find whose result does not depend on the schedule: bit-reproducible.  One host read (the status words): a face with
+    an index outside [0, n_vertices) is a RuntimeError that names how many there are."""
+    what = "pscv.mesh_components"
+    F, V = _mesh_faces(faces, n_vertices, what)
+    _mesh_on_gpu(what, faces=faces)
+    status = torch.zeros(2, dtype=torch.int32, device=faces.device)
+    out = _mesh_components(faces, F, V, status)
+    bad, trips = (F, 0) if V == 0 else status.tolist()
+    if bad or trips:
+        raise _mesh_status_error(what, bad, trips)
+    return out
+
+
+def mesh_vertex_normals(xyz: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """Area-weighted unit vertex normals of an indexed triangle mesh on the GPU: xyz fp32 [V,3], faces
+    int32 [F,3] -> fp32 [V,3].  Per vertex the fp64 sum of (b - a) x (c - a) over the faces that use it, in ascending corner
+    order (corner 3 f + k is vertex faces[f,k]; a face that names the vertex twice counts twice), divided by its length and
+    rounded to fp32; (0,0,0) for a vertex in no face and when the length is 0 or not finite.  Faces oriented towards free space
+    (``tsdf_extract``) give normals that point there.  The vertex -> corner adjacency is a stable torch sort (plumbing); one
+    gathering launch, no float atomics, no host read, bit-reproducible.  A face with an index out of range adds nothing."""
+    what = "pscv.mesh_vertex_normals"
+    V = _mesh_vertices(xyz, None, None, what)
+    F, V = _mesh_faces(faces, V, what)
+    _mesh_on_gpu(what, xyz=xyz, faces=faces)
+    dev = xyz.device
+    normals = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    if V == 0:
+        return normals
+    key = faces.reshape(-1).to(torch.int64)
+    key = torch.where((key >= 0) & (key < V), key, torch.full_like(key, V))       # (out of range: behind every vertex's corners)
+    corners = torch.sort(key, stable=True).indices.to(torch.int32)
+    corner_off = torch.zeros(V + 1, dtype=torch.int32, device=dev)
+    corner_off[1:] = torch.cumsum(torch.bincount(key, minlength=V + 1)[:V], dim=0)
+    rc = _launch("mesh_vertex_normals", lambda: L.lib().pscv_mesh_vertex_normals(_p(xyz), _p(faces), _p(corner_off), _p(corners), F, V,
+                                                                                 _p(normals), _stream()),
+                 # per corner the face's indices and three positions (48 B, gathered), per vertex its offsets and the normal
+                 cost=lambda: (3.0 * F * 52.0 + 20.0 * V, 3.0 * F * 20.0))
+    L.check(rc, "pscv_mesh_vertex_normals")
+    return normals
+
+
+def mesh_clean(xyz: torch.Tensor, rgb: torch.Tensor, faces: torch.Tensor, *, min_component_faces: int = 0,
+               min_component_fraction: float = 0.0, keep_largest: int = 0, drop_degenerate: bool = False,
+               normals: Optional[torch.Tensor] = None):
+    """Removes small connected components, degenerate faces and unused vertices from an indexed triangle mesh on the GPU
+    (INTEGRATION.md section 2p): xyz fp32 [V,3], rgb uint8 [V,3], faces int32 [F,3] (and ``normals`` fp32 [V,3], carried along)
+    -> (xyz, rgb, faces) or (xyz, rgb, faces, normals), vertices and faces in their original relative order, indices renumbered.
+
+    A component (``mesh_components``) survives when it has at least max(``min_component_faces``, ceil(``min_component_fraction``
+    x the largest component's faces)) faces, at least one face, and -- with ``keep_largest`` = k > 0 -- is among the first k in the
+    order (faces descending, label ascending).  A face survives when its component does and, with ``drop_degenerate``, it has no
+    repeated index and its fp64 cross product is not exactly (0,0,0); a vertex survives when a surviving face uses it.  With the
+    defaults the call only drops the vertices no face uses.  Applying it twice changes nothing more (the components are those of
+    the INPUT mesh: only ``drop_degenerate`` together with a size option can leave a component that a second call, which counts
+    it without its degenerate faces, finds too small).  The choice is torch on the
+    device, the prefix sums are ``torch.cumsum``; one host read (the two totals and the status words) sizes the outputs."""
+    what = "pscv.mesh_clean"
+    V = _mesh_vertices(xyz, rgb, normals, what)
+    if rgb is None:
+        raise ValueError(f"{what}: rgb must be a uint8 tensor {tuple(xyz.shape)}, got None")
+    F, V = _mesh_faces(faces, V, what)
+    min_faces = _mesh_count(min_component_faces, "min_component_faces", what)
+    k_largest = _mesh_count(keep_largest, "keep_largest", what)
+    try:
+        fraction = float(min_component_fraction)
+    except (TypeError, ValueError):
+        fraction = float("nan")
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"{what}: min_component_fraction must lie in [0, 1], got {min_component_fraction!r}")
+    if not isinstance(drop_degenerate, (bool, np.bool_)):
+        raise ValueError(f"{what}: drop_degenerate must be a bool, got {drop_degenerate!r}")
+    _mesh_on_gpu(what, xyz=xyz, rgb=rgb, faces=faces, normals=normals)
+    dev = xyz.device
+
+    def empty():
+        out = (xyz.new_empty((0, 3)), rgb.new_empty((0, 3)), faces.new_empty((0, 3)))
+        return out if normals is None else out + (normals.new_empty((0, 3)),)
+
+    if V == 0:
+        if F:
+            raise _mesh_status_error(what, F, 0)
+        return empty()
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    label, fcount, vcount = _mesh_components(faces, F, V, status)
+    # the choice, on the device
+    threshold = torch.clamp(torch.ceil(fraction * fcount.max().to(torch.float64)), min=float(min_faces))
+    keep = (fcount > 0) & (fcount.to(torch.float64) >= threshold)
+    if k_largest:
+        order = torch.sort(fcount, stable=True, descending=True).indices         # (faces descending, label ascending)
+        first = torch.zeros(V, dtype=torch.bool, device=dev)
+        first[order[:k_largest]] = True
+        keep &= first
+    keep_comp = keep.to(torch.uint8)
+    fmark = torch.empty(F, dtype=torch.int32, device=dev)
+    vmark = torch.zeros(V, dtype=torch.int32, device=dev)
+    st = _stream()
+    rc = _launch("mesh_mark", lambda: L.lib().pscv_mesh_mark(_p(xyz), _p(faces), _p(label), _p(keep_comp), F, V, int(bool(drop_degenerate)),
+                                                             _p(fmark), _p(vmark), st),
+                 cost=lambda: (F * (12.0 + 4.0 + 1.0 + 4.0 + 12.0 + (36.0 if drop_degenerate else 0.0)), 20.0 * F))
+    L.check(rc, "pscv_mesh_mark")
+    fincl = torch.cumsum(fmark, dim=0, dtype=torch.int32)
+    vincl = torch.cumsum(vmark, dim=0, dtype=torch.int32)
+    # the one host read: the two totals and the status words (no face: status[0], which is 0 then, stands in for the empty sum)
+    n_face, n_vert, bad, trips = torch.cat((fincl[-1:] if F else status[:1], vincl[-1:], status)).tolist()
+    if bad or trips:
+        raise _mesh_status_error(what, bad, trips)
+    xyz_out = torch.empty((n_vert, 3), dtype=torch.float32, device=dev)
+    rgb_out = torch.empty((n_vert, 3), dtype=torch.uint8, device=dev)
+    faces_out = torch.empty((n_face, 3), dtype=torch.int32, device=dev)
+    normals_out = None if normals is None else torch.empty((n_vert, 3), dtype=torch.float32, device=dev)
+    if n_vert:
+        rc = _launch("mesh_compact", lambda: L.lib().pscv_mesh_compact(
+            _p(xyz), _p(rgb), _p(normals), _p(faces), _p(fmark), _p(vmark), _p(fincl), _p(vincl), F, V, _p(xyz_out), _p(rgb_out),
+            _p(normals_out), _p(faces_out), n_face, n_vert, st),
+            cost=lambda: (8.0 * (F + V) + n_face * 36.0 + n_vert * (30.0 + (24.0 if normals is not None else 0.0)), 0.0))
+        L.check(rc, "pscv_mesh_compact")
+    out = (xyz_out, rgb_out, faces_out)
+    return out if normals is None else out + (normals_out,)
+
+
+# --------------------------------------------------------------------------------------------
 # scene set-up from a COLMAP sparse model (utils/colmap_utils.py: compute_src_imgs, compute_min_max_depth_yao)
 # --------------------------------------------------------------------------------------------
 def _sparse_inputs(what, xyz, R, t, **index_arrays):

@@ -106,17 +106,27 @@ def read_ply(path) -> np.ndarray:
 _FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 
 
-def mesh_ply_header(n_vertices: int, n_faces: int) -> bytes:
+_VERTEX_NORMAL = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("red", "u1"),
+                           ("green", "u1"), ("blue", "u1")])
+
+
+def mesh_ply_header(n_vertices: int, n_faces: int, normals: bool = False) -> bytes:
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n_vertices}"]
-    lines += [f"property float32 {c}" for c in "xyz"] + [f"property uint8 {c}" for c in ("red", "green", "blue")]
+    lines += [f"property float32 {c}" for c in (("x", "y", "z", "nx", "ny", "nz") if normals else "xyz")]
+    lines += [f"property uint8 {c}" for c in ("red", "green", "blue")]
     lines += [f"element face {n_faces}", "property list uchar int vertex_indices"]
     return ("\n".join(lines + ["end_header"]) + "\n").encode("ascii")
 
 
-def write_mesh(path, xyz, rgb, faces) -> None:
+def write_mesh(path, xyz, rgb, faces, normals=None) -> None:
     """xyz [V,3] (cast to float32), rgb [V,3] uint8, faces [F,3] integer indices into the vertices -> binary little-endian PLY at
-    ``path`` with ``element face`` / ``property list uchar int vertex_indices`` (numpy arrays or tensors)."""
+    ``path`` with ``element face`` / ``property list uchar int vertex_indices`` (numpy arrays or tensors).  With ``normals`` [V,3]
+    (cast to float32) the vertices also carry ``property float32 nx / ny / nz`` after ``z``; without, the file is what it always was."""
     xyz = np.asarray(getattr(xyz, "cpu", lambda: xyz)(), dtype=np.float32).reshape(-1, 3)
+    if normals is not None:
+        normals = np.asarray(getattr(normals, "cpu", lambda: normals)(), dtype=np.float32)
+        if normals.shape != xyz.shape:
+            raise ValueError(f"write_mesh: normals must be float {xyz.shape}, got {normals.shape}")
     rgb = np.asarray(getattr(rgb, "cpu", lambda: rgb)())
     faces = np.asarray(getattr(faces, "cpu", lambda: faces)())
     if rgb.dtype != np.uint8 or rgb.shape != xyz.shape:
@@ -125,9 +135,11 @@ def write_mesh(path, xyz, rgb, faces) -> None:
         raise ValueError(f"write_mesh: faces must be integer [F,3], got {faces.dtype} {faces.shape}")
     if faces.size and (int(faces.min()) < 0 or int(faces.max()) >= xyz.shape[0]):
         raise ValueError(f"write_mesh: face indices must lie in [0, {xyz.shape[0]})")
-    vdata = np.empty(xyz.shape[0], dtype=_VERTEX)
+    vdata = np.empty(xyz.shape[0], dtype=_VERTEX if normals is None else _VERTEX_NORMAL)
     for k, c in enumerate("xyz"):
         vdata[c] = xyz[:, k]
+        if normals is not None:
+            vdata["n" + c] = normals[:, k]
     for k, c in enumerate(("red", "green", "blue")):
         vdata[c] = rgb[:, k]
     fdata = np.empty(faces.shape[0], dtype=_FACE)
@@ -135,7 +147,7 @@ def write_mesh(path, xyz, rgb, faces) -> None:
     fdata["v"] = faces
     tmp = f"{path}.part"
     with open(tmp, "wb") as fh:
-        fh.write(mesh_ply_header(xyz.shape[0], faces.shape[0]))
+        fh.write(mesh_ply_header(xyz.shape[0], faces.shape[0], normals is not None))
         fh.write(vdata.tobytes())
         fh.write(fdata.tobytes())
     os.replace(tmp, path)
@@ -145,6 +157,12 @@ def read_mesh(path):
     """(xyz float32 [V,3], rgb uint8 [V,3], faces int32 [F,3]) of a binary little-endian PLY triangle mesh as ``write_mesh`` writes
     it: vertex properties by name (x, y, z float32 and red, green, blue uint8 must be among them), faces as a uchar-counted list of
     int / uint indices, every face a triangle."""
+    return read_mesh_normals(path)[:3]
+
+
+def read_mesh_normals(path):
+    """``read_mesh`` plus the vertex normals: (xyz, rgb, faces, normals float32 [V,3]), normals None for a file without the float32
+    properties nx, ny, nz."""
     with open(path, "rb") as fh:
         if b"ply" not in fh.readline():
             raise ValueError(f"{path}: not a PLY file")
@@ -182,4 +200,7 @@ def read_mesh(path):
             raise ValueError(f"{path}: coordinate {c} must be float32")
     xyz = np.stack([vdata[c] for c in "xyz"], axis=-1).astype(np.float32).reshape(-1, 3)
     rgb = np.stack([vdata[c] for c in ("red", "green", "blue")], axis=-1).astype(np.uint8).reshape(-1, 3)
-    return xyz, rgb, fdata["v"].astype(np.int32).reshape(-1, 3)
+    normals = None
+    if all(c in vdata.dtype.names and vdata.dtype[c] == np.dtype("<f4") for c in ("nx", "ny", "nz")):
+        normals = np.stack([vdata[c] for c in ("nx", "ny", "nz")], axis=-1).astype(np.float32).reshape(-1, 3)
+    return xyz, rgb, fdata["v"].astype(np.int32).reshape(-1, 3), normals
