@@ -558,6 +558,33 @@ def test_tail_sweep_equals_the_two_layers(env, shape, with_skip, dtype):
     check_close(f"tail sweep vs ATen {shape} {dtype}", outs[0].cpu(), ref[:, 0], max_abs=3e-2 if dtype == torch.bfloat16 else 6e-3, rel_l2=4e-3 if dtype == torch.bfloat16 else 6e-4)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_tail_sweep_channel_slices_across_a_chunk_seam(env, dtype):
+    """The tail sweep's plane fetch with BOTH of its edge conditions in one launch: input planes outside the volume and beyond a
+    chunk seam (tail_nbk = 1: the smallest chunk, one 6-plane block; 20 output planes = 4 blocks = 2 chunks) and a channel slice
+    (in_coff = 8 of 32 channels, skip_coff = 4 of 16; every other channel is NaN, so one element read beside the slice shows).  Ragged
+    in both image axes (10 x 18 output pixels against the 8 x 28 tile).  IDENTICAL logits to the two layers on the packed tensors."""
+    L, ops = env
+    g = torch.Generator().manual_seed(5)
+    B, Di, Hi, Wi = 2, 10, 5, 9
+    x = bf16_round(torch.randn(B, Di, Hi, Wi, 16, generator=g)).cuda().to(dtype)
+    skip = bf16_round(torch.randn(B, 2 * Di, 2 * Hi, 2 * Wi, 8, generator=g)).cuda().to(dtype)
+    xw = torch.full((B, Di, Hi, Wi, 32), float("nan"), dtype=dtype, device="cuda")
+    sw = torch.full((B, 2 * Di, 2 * Hi, 2 * Wi, 16), float("nan"), dtype=dtype, device="cuda")
+    xw[..., 8:24] = x
+    sw[..., 4:12] = skip
+    bn = (torch.rand(8, generator=g) + 0.5, torch.randn(8, generator=g) * 0.1, torch.randn(8, generator=g) * 0.1, torch.rand(8, generator=g) + 0.5)
+    up = ops.Conv3dLayer.build(bf16_round(torch.randn(16, 8, 3, 3, 3, generator=g) / np.sqrt(27 * 16 / 8)), kind=L.CONV_T2, transposed=True,
+                               device="cuda", bn=bn, relu=True, dtype=dtype)
+    head = ops.Conv3dLayer.build(bf16_round(torch.randn(1, 8, 3, 3, 3, generator=g) / np.sqrt(27 * 8)), kind=L.CONV_S1, device="cuda",
+                                 conv_bias=torch.randn(1, generator=g), dtype=dtype)
+    with L.tuning(c1_sweep=2):
+        two = ops.conv3d(ops.conv3d(x, up, skip=skip), head, out_dtype=torch.float32).view(B, 2 * Di, 2 * Hi, 2 * Wi)
+    with L.tuning(tail_nbk=1):
+        got = ops.tail_sweep(xw, up, head, skip=sw, in_coff=8, skip_coff=4)
+    assert got is not None and torch.isfinite(got).all() and torch.equal(got, two)
+
+
 @pytest.mark.parametrize("cin,cout,kind,shape", [(32, 8, 0, (16, 16, 32)),      # conv0's depth sweep
                                                   (8, 8, 0, (16, 16, 32)),       # narrow sweep
                                                   (8, 16, 1, (16, 16, 32)),      # stride-2 (brick at this size; sweep forced below)

@@ -17,6 +17,7 @@
 // Sequential(ConvTranspose3d, BatchNorm3d, ReLU) blocks and `prob` of models/MVSNet/model.py:43-84,
 // models/CVP_MVSNet/models/net.py:50-85 and the 3-D members of models/VisMVSNet/nn_utils.py:194-278.
 #include "conv_common.h"
+#include "conv_dev.h"
 #include <type_traits>
 
 namespace pscv {
@@ -104,8 +105,6 @@ __device__ __noinline__ void epi_ragged(float y0, float y1, float y2, float y3, 
         else reinterpret_cast<uint16_t*>(op)[k] = Half16<H>::bits(v);
     }
 }
-
-typedef unsigned cv_u32x2 __attribute__((ext_vector_type(2)));   // payload of the raw buffer stores
 
 // HOT: the store side of the layers the U-Nets run -- 16-bit output, c_out a multiple of 16, output and skip slice of a batch item
 // below 2 GiB and 8-byte aligned (chosen on the host, launch_conv).  Output and skip tensor are addressed through one buffer
@@ -213,10 +212,9 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
     __amdgpu_buffer_rsrc_t ors, srs;
     if constexpr (HOT) {
         const long item_out = (long)a.Do * a.Ho * a.Wo * a.out_cs, item_skip = (long)a.Do * a.Ho * a.Wo * a.skip_cs;   // elements
-        ors = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint16_t*>(a.out) + (long)b * item_out + a.out_co, (short)0,
-                                                (int)((item_out - a.out_co) * 2), 0x00020000);
-        srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.skip) + (a.skip ? (long)b * item_skip + a.skip_co : 0), (short)0,
-                                                a.skip ? (int)((item_skip - a.skip_co) * 2) : 0, 0x00020000);
+        // (conv_dev.h; a missing skip tensor gets an empty descriptor: its loads return the +0 that the epilogue adds)
+        ors = buf_rsrc(reinterpret_cast<const uint16_t*>(a.out) + (long)b * item_out + a.out_co, (int)((item_out - a.out_co) * 2));
+        srs = buf_rsrc(a.skip + (a.skip ? (long)b * item_skip + a.skip_co : 0), a.skip ? (int)((item_skip - a.skip_co) * 2) : 0);
     }
     auto out_row = [&](int od, int oh) -> RowT {
         if constexpr (HOT) return (unsigned)od * plane_out + (unsigned)oh * row_out;
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
     // large tiles a workgroup per CU, and the class split keeps its reads per row too (its first class's epilogue runs with the second
     // class's weights and skip values live: 132 instead of 120 VGPRs at 32 -> 16, a workgroup per CU).  Every caller hands it the
     // skip values.
-    const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    const float lo_post = epi_lo_post(a.epi);
     constexpr bool CREG = HOT && NT < 4 && !CSPLIT;
     float4 hsc[CREG ? NT : 1], hbi[CREG ? NT : 1], hfl[CREG ? NT : 1];
     auto epi_consts = [&]() {
@@ -394,10 +392,8 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const ConvArgs a) {
             float y[4] = {relu_floor(fmaf(acc[m][0], sc.x, bi.x), fl.x), relu_floor(fmaf(acc[m][1], sc.y, bi.y), fl.y),
                           relu_floor(fmaf(acc[m][2], sc.z, bi.z), fl.z), relu_floor(fmaf(acc[m][3], sc.w, bi.w), fl.w)};
             if constexpr (HOT) {
-                const uint2 sv = pre[m];
-                y[0] = relu_floor(y[0] + Half16<H>::lo(sv.x), lo_post); y[1] = relu_floor(y[1] + Half16<H>::hi(sv.x), lo_post);
-                y[2] = relu_floor(y[2] + Half16<H>::lo(sv.y), lo_post); y[3] = relu_floor(y[3] + Half16<H>::hi(sv.y), lo_post);
-                __builtin_amdgcn_raw_buffer_store_b64(cv_u32x2{Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3])}, ors,
+                add_skip4_clamp<H>(y, pre[m], lo_post);
+                __builtin_amdgcn_raw_buffer_store_b64(buf_u32x2{Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3])}, ors,
                                                       (int)(lane_out + (unsigned)(m * 32)), (int)(orow + (unsigned)(pw * a.out_cs * 2)), 0);
                 continue;
             }

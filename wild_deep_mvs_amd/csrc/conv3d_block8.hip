@@ -16,6 +16,7 @@
 // Bytes per output voxel through the CU path: 16 x 216/112 in + 16 out = 47 (93 before); MFMAs 1.43 + 1.14 row tiles per output
 // row (2 before).  8-byte stores like the narrow sweep.
 #include "conv_common.h"
+#include "conv_dev.h"
 #include <type_traits>
 
 namespace pscv {
@@ -81,12 +82,13 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
         const int bh = tid / B8_XW, bw = tid - bh * B8_XW;
         const int gh = h0 - 2 + bh, gw = w0 - 2 + bw;
         const bool gval = in_tile && (unsigned)gh < (unsigned)a.Hh && (unsigned)gw < (unsigned)a.W;
-        goff = gval ? (unsigned)(gh * a.W + gw) * (unsigned)a.in_cs * 2u : 0x7ffffff0u;
+        goff = gval ? (unsigned)(gh * a.W + gw) * (unsigned)a.in_cs * 2u : BUF_OOR;
     }
+    // (zero-fill rule: conv_dev.h; own fetch: through plane_fetch 90 / 92 instead of 88 SGPRs, other spills -- profiles/conv_dev_isa.txt)
     auto fetch = [&](int plane) -> uint4 {
         const bool pv = plane >= 0 && plane < a.D;                                                   // wave-uniform
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint16_t*>(inb + (long)(pv ? plane : 0) * plane_stride), (short)0, pv ? (int)plane_bytes : 0, 0x00020000);
+            const_cast<uint16_t*>(inb + (long)(pv ? plane : 0) * plane_stride), (short)0, pv ? (int)plane_bytes : 0, BUF_FLAGS);
         return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)goff, 0, 0));
     };
     auto stash = [&](int rel, const uint4& v) {                       // rel = plane - (dbeg - 2)
@@ -96,11 +98,8 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
     // ---- per-lane constants ----
     const int c0 = (g & 1) * 4;                                       // this lane's 4 output channels; its plane of a pair is g >> 1
     float sc1[4], bi1[4], fl1[4], sc2[4], bi2[4], fl2[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc1[k] = a.scale1 ? a.scale1[c0 + k] : 1.0f; bi1[k] = a.bias1 ? a.bias1[c0 + k] : 0.0f; fl1[k] = a.floor1 ? a.floor1[c0 + k] : 0.0f;
-        sc2[k] = a.scale2 ? a.scale2[c0 + k] : 1.0f; bi2[k] = a.bias2 ? a.bias2[c0 + k] : 0.0f; fl2[k] = a.floor2 ? a.floor2[c0 + k] : 0.0f;
-    }
+    epi_load4(sc1, bi1, fl1, a.scale1, a.bias1, a.floor1, c0);
+    epi_load4(sc2, bi2, fl2, a.scale2, a.bias2, a.floor2, c0);
     const bool tcol_ok = (unsigned)(w0 - 1 + n) < (unsigned)a.W;
     const bool ocol_ok = n < B8_TW && w0 + n < a.W;
     const long vplane = (long)a.Hh * a.W;
@@ -186,8 +185,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
                     if (a.epi1 & PSCV_EPI_RELU_POST) y[c] = relu_floor(y[c], 0.0f);
                 }
                 const bool ok = pl_ok && (unsigned)(h0 - 1 + rb1 + i) < (unsigned)a.Hh;
-                *reinterpret_cast<uint2*>(tp + i * (B8_TCOLS * 16)) =
-                    ok ? make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3])) : make_uint2(0u, 0u);
+                *reinterpret_cast<uint2*>(tp + i * (B8_TCOLS * 16)) = ok ? pack4<H>(y) : make_uint2(0u, 0u);
             }
         }
         if (e2) {
@@ -201,18 +199,11 @@ __global__ __launch_bounds__(256, 3) void conv3d_block8_kernel(const Block8Args 
                     y[c] = fmaf(a2[i][c], sc2[c], bi2[c]);
                     if (a.epi2 & PSCV_EPI_RELU_PRE) y[c] = relu_floor(y[c], fl2[c]);
                 }
-                if (a.residual) {
-                    const uint2 sv = *reinterpret_cast<const uint2*>(rp + i * (B8_XW * 16));
-                    y[0] += Half16<H>::lo(sv.x); y[1] += Half16<H>::hi(sv.x); y[2] += Half16<H>::lo(sv.y); y[3] += Half16<H>::hi(sv.y);
-                }
-                if (a.epi2 & PSCV_EPI_RELU_POST) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) y[c] = relu_floor(y[c], 0.0f);
-                }
+                if (a.residual) add_skip4<H>(y, *reinterpret_cast<const uint2*>(rp + i * (B8_XW * 16)));
+                if (a.epi2 & PSCV_EPI_RELU_POST) relu4(y, 0.0f);
                 if (od < dend && ocol_ok && h0 + rb2 + i < a.Hh) {
                     const long vox = (((long)b * a.D + od) * a.Hh + (h0 + rb2 + i)) * a.W + w0 + n;
-                    *reinterpret_cast<uint2*>(a.out + vox * a.out_cs + a.out_co + c0) =
-                        make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
+                    *reinterpret_cast<uint2*>(a.out + vox * a.out_cs + a.out_co + c0) = pack4<H>(y);
                 }
             }
         }

@@ -19,6 +19,7 @@
 // Replaces (fdarmon/wild_deep_mvs): CostRegNet.prob models/MVSNet/model.py:72,82; prob0 models/CVP_MVSNet/models/
 // net.py:76,83; RegPair / RegFuse final_conv models/VisMVSNet/model_cas.py:55,68.
 #include "conv_common.h"
+#include "conv_dev.h"
 
 namespace pscv {
 
@@ -130,11 +131,10 @@ __global__ __launch_bounds__(256) void conv3d_c1_kernel(const C1Args a) {
 #pragma unroll
     for (int s = 0; s < NSTEPS; ++s)
         wf[s] = a.wpk[s * 64 + lane];
-    const float e_scale = a.scale ? a.scale[0] : 1.0f, e_bias = a.bias ? a.bias[0] : 0.0f,
-                e_floor = a.floor ? a.floor[0] : 0.0f;
+    const float e_scale = epi_scale(a.scale, 0), e_bias = epi_bias(a.bias, 0), e_floor = epi_floor(a.floor, 0);
     // ReLU switches as clamps against -inf (no branches in the epilogue)
     const float lo_pre = (a.epi & PSCV_EPI_RELU_PRE) ? e_floor : -__builtin_inff();
-    const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    const float lo_post = epi_lo_post(a.epi);
     __syncthreads();
     PSCV_STAMP(2)
 
@@ -264,13 +264,8 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
     const int sbh = tid / C1_BW, sbw = tid - sbh * C1_BW;
     const int sgh = h0 - 1 + sbh, sgw = w0 - 1 + sbw;
     const bool vox_ok = tid < PV && (unsigned)sgh < (unsigned)a.Hh && (unsigned)sgw < (unsigned)a.W;
-    const unsigned goff = vox_ok ? (unsigned)(sgh * a.W + sgw) * (unsigned)(a.in_cs * 2) : 0x7ffffff0u;
-    auto fetch = [&](int plane) -> uint4 {
-        const bool pv = plane >= 0 && plane < a.D;                                               // wave-uniform
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(inb + (unsigned long)(pv ? plane : 0) * plane_stride_b), (short)0, pv ? (int)plane_bytes : 0, 0x00020000);
-        return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)goff, 0, 0));
-    };
+    const unsigned goff = vox_ok ? (unsigned)(sgh * a.W + sgw) * (unsigned)(a.in_cs * 2) : BUF_OOR;
+    auto fetch = [&](int plane) { return plane_fetch(inb, plane_stride_b, plane_bytes, a.D - 1, goff, plane); };   // (conv_dev.h)
     auto stash = [&](int prel, const uint4& v) {          // prel = plane - (dbeg - 1)
         if (tid < PV) *reinterpret_cast<uint4*>(smem + (prel & (C1S_NSLOT - 1)) * PSB + tid * VB) = v;
     };
@@ -289,9 +284,9 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
 #pragma unroll
     for (int p = 0; p < C1_P; ++p) nx[p] = fetch(dbeg + C1_P + 1 + p);        // planes of block 1 (prel 8 .. 13)
 
-    const float e_scale = a.scale ? a.scale[0] : 1.0f, e_bias = a.bias ? a.bias[0] : 0.0f, e_floor = a.floor ? a.floor[0] : 0.0f;
+    const float e_scale = epi_scale(a.scale, 0), e_bias = epi_bias(a.bias, 0), e_floor = epi_floor(a.floor, 0);
     const float lo_pre = (a.epi & PSCV_EPI_RELU_PRE) ? e_floor : -__builtin_inff();
-    const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    const float lo_post = epi_lo_post(a.epi);
     // fused tail: the chunk's depth planes in LDS (a global load per block sat in the block's dependency chain: 59 us fused
     // against 40 us for the two separate launches)
     __shared__ float sdep[256];
@@ -344,8 +339,8 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
             float y[2][4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                y[0][r] = clamp_lo(clamp_lo(fmaf(acc0[r], e_scale, e_bias), lo_pre), lo_post);
-                y[1][r] = clamp_lo(clamp_lo(fmaf(acc1[r], e_scale, e_bias), lo_pre), lo_post);
+                y[0][r] = relu_floor(relu_floor(fmaf(acc0[r], e_scale, e_bias), lo_pre), lo_post);
+                y[1][r] = relu_floor(relu_floor(fmaf(acc1[r], e_scale, e_bias), lo_pre), lo_post);
             }
             if (g < 2) {          // rows 0,1 (g = 0) and 4,5 (g = 1)
 #pragma unroll
@@ -402,7 +397,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_c1_sweep_kernel(const C1Args a)
                 for (int r = 0; r < 4; ++r) {
                     const int m = 4 * g + r;
                     ok[r] = m < C1_P && d0 + m < a.D;
-                    yv[r] = clamp_lo(clamp_lo(fmaf(ct ? acc1[r] : acc0[r], e_scale, e_bias), lo_pre), lo_post);
+                    yv[r] = relu_floor(relu_floor(fmaf(ct ? acc1[r] : acc0[r], e_scale, e_bias), lo_pre), lo_post);
                     if (ok[r]) lmax = fmaxf(lmax, yv[r]);
                 }
                 if (lmax > -__builtin_inff()) {

@@ -23,6 +23,7 @@
 // Replaces (fdarmon/wild_deep_mvs): CostRegNet.conv0 = ConvBnReLU3D(32, 8) models/MVSNet/model.py:46,75
 // (block definition models/MVSNet/module.py:41-48).
 #include "conv_common.h"
+#include "conv_dev.h"
 #include <type_traits>
 
 namespace pscv {
@@ -41,8 +42,6 @@ PSCV_PROF_BUFFER(sweep)
 constexpr int SW_BW = 18;
 constexpr int SW_VB = 64;                  // bytes per voxel (32 ch x 2 B)
 constexpr int SW_NSLOT = 6;
-typedef unsigned sw_u32x4 __attribute__((ext_vector_type(4)));   // payloads of the raw buffer stores
-typedef unsigned sw_u32x2 __attribute__((ext_vector_type(2)));
 // Tile height TH (rows) is a template parameter: TH = 8 -> 256 threads, 70 KiB ring, two workgroups per CU;
 // TH = 16 -> 512 threads, 123 KiB ring, one workgroup per CU but 18/16 instead of 10/8 halo rows per tile.
 template <int TH> struct SwGeom {
@@ -100,9 +99,7 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
         for (int kw = 0; kw < 3; ++kw) boff[rr][kw] = sw_lds_off((row0 + rr) * SW_BW + n + kw, g);
 
     // ---- staging descriptors: 3 chunks per thread per plane ----
-    // Planes are fetched with raw buffer loads: the descriptor covers one input plane, a chunk outside the image carries an
-    // out-of-range offset and a plane outside the volume an empty descriptor -- the hardware returns zeros (= the conv's
-    // padding): NLD load instructions per plane, no predicate, zero fill or 64-bit address arithmetic per chunk.
+    // (plane_fetch, conv_dev.h: zeros outside the image and the volume come from the descriptor's bounds)
     unsigned goff[NLD];
     int loff[NLD];
     bool lval[NLD];
@@ -117,18 +114,11 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
         const int gh = h0 - 1 + bh, gw = w0 - 1 + bw;
         lval[i] = id < SW_CHUNKS;
         const bool gval = lval[i] && (unsigned)gh < (unsigned)a.Hh && (unsigned)gw < (unsigned)a.W;
-        goff[i] = gval ? ((unsigned)(gh * a.W + gw) * (unsigned)a.in_cs + (unsigned)(c * 8)) * 2u : 0x7ffffff0u;
+        goff[i] = gval ? ((unsigned)(gh * a.W + gw) * (unsigned)a.in_cs + (unsigned)(c * 8)) * 2u : BUF_OOR;
         loff[i] = sw_lds_off(v, c);
     }
     const int plane_hi = min(a.D - 1, dend);   // last input plane this sweep can use
-    auto fetch = [&](int plane, uint4 (&reg)[NLD]) {
-        const bool pv = plane >= 0 && plane <= plane_hi;                                         // wave-uniform
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint16_t*>(inb + (long)(pv ? plane : 0) * plane_stride), (short)0, pv ? (int)plane_bytes : 0, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i)
-            reg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)goff[i], 0, 0));
-    };
+    auto fetch = [&](int plane, uint4 (&reg)[NLD]) { plane_fetch(inb, plane_stride, plane_bytes, plane_hi, goff, plane, reg); };
     auto stash = [&](int ring, const uint4 (&reg)[NLD]) {
         unsigned char* sp = smem + ring * SW_PB;
 #pragma unroll
@@ -139,21 +129,15 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
     // ---- epilogue constants: this lane always owns channels (g&1)*4 .. +3 of plane d + (g>>1) ----
     const int c0 = (g & 1) * 4;
     float sc[4], bi[4], fl[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc[k] = a.scale ? a.scale[c0 + k] : 1.0f;
-        bi[k] = a.bias ? a.bias[c0 + k] : 0.0f;
-        fl[k] = a.floor ? a.floor[c0 + k] : 0.0f;
-    }
+    epi_load4(sc, bi, fl, a.scale, a.bias, a.floor, c0);
     const bool out_f32 = !HOT && a.out_f32, has_skip = !HOT && a.skip != nullptr, st16 = HOT || a.st16;
     const bool relu_pre = HOT || (a.epi & PSCV_EPI_RELU_PRE), relu_post = !HOT && (a.epi & PSCV_EPI_RELU_POST);
 
-    // ---- store descriptors: the mirror of `fetch` ----
+    // ---- store descriptors: the mirror of `fetch` (the dropped-store rule: conv_dev.h) ----
     // The descriptor of a plane pair starts at output plane d of this batch item and covers plane d, and plane d + 1 if this chunk
     // owns it; a lane's byte offset (made once, here) is its voxel inside plane d plus one plane for the lanes of plane d + 1
-    // (g >> 1).  Rows beyond Hh and columns beyond W carry an out-of-range constant, plane d + 1 beyond dend lies beyond the
-    // range: the hardware drops those stores (and returns zeros for the residual, which then goes nowhere).
-    constexpr unsigned OOR = 0x7ffffff0u;
+    // (g >> 1).  Rows beyond Hh and columns beyond W carry BUF_OOR, plane d + 1 beyond dend lies beyond the range (the residual
+    // read there returns zeros, which then go nowhere).
     const unsigned oes = out_f32 ? 4u : 2u;
     const long oplane_b = (long)a.Hh * a.W * a.out_cs * oes, splane_b = (long)a.Hh * a.W * a.skip_cs * 2;
     const char* outb = reinterpret_cast<const char*>(a.out) + (long)b * a.D * oplane_b + a.out_co * oes;
@@ -166,16 +150,16 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
             const int oh = h0 + row0 + r;
             const bool ok = oh < a.Hh && ow < a.W;
             const unsigned pix = (unsigned)(oh * a.W + ow);
-            ooff[r] = ok ? (unsigned)(g >> 1) * (unsigned)oplane_b + (pix * (unsigned)a.out_cs + (unsigned)c0) * oes : OOR;
-            soff[r] = ok && has_skip ? (unsigned)(g >> 1) * (unsigned)splane_b + (pix * (unsigned)a.skip_cs + (unsigned)c0) * 2u : OOR;
+            ooff[r] = ok ? (unsigned)(g >> 1) * (unsigned)oplane_b + (pix * (unsigned)a.out_cs + (unsigned)c0) * oes : BUF_OOR;
+            soff[r] = ok && has_skip ? (unsigned)(g >> 1) * (unsigned)splane_b + (pix * (unsigned)a.skip_cs + (unsigned)c0) * 2u : BUF_OOR;
         }
         // 16-byte stores: even g owns the whole voxel (channels 0..7) of pixel row 0, odd g that of pixel row 1
         const int oh = h0 + row0 + (g & 1);
-        ooff16 = oh < a.Hh && ow < a.W ? (unsigned)(g >> 1) * (unsigned)oplane_b + (unsigned)(oh * a.W + ow) * (unsigned)a.out_cs * 2u : OOR;
+        ooff16 = oh < a.Hh && ow < a.W ? (unsigned)(g >> 1) * (unsigned)oplane_b + (unsigned)(oh * a.W + ow) * (unsigned)a.out_cs * 2u : BUF_OOR;
     }
     auto pair_rsrc = [&](const char* base, long plane_b, int co_b, int d) {                   // wave-uniform
         const int np = min(2, dend - d);
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base + d * plane_b), (short)0, (int)(np * plane_b - co_b), 0x00020000);
+        return buf_rsrc(base + d * plane_b, (int)(np * plane_b - co_b));
     };
 
     // ---- prologue: planes dbeg-1 .. dbeg+2 into ring slots 0..3 ----
@@ -237,28 +221,20 @@ __global__ __launch_bounds__(32 * SW_TH, 2) void conv3d_sweep8_kernel(const Swee
                 y[k] = fmaf(acc[r][k], sc[k], bi[k]);
                 if (relu_pre) y[k] = relu_floor(y[k], fl[k]);
             }
-            if (has_skip) {
-                y[0] += Half16<H>::lo(sv[r].x); y[1] += Half16<H>::hi(sv[r].x);
-                y[2] += Half16<H>::lo(sv[r].y); y[3] += Half16<H>::hi(sv[r].y);
-            }
-            if (relu_post) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], 0.0f);
-            }
-            if (out_f32)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sw_u32x4, make_float4(y[0], y[1], y[2], y[3])), ors, (int)ooff[r], 0, 0);
-            else
-                pk[r] = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
+            if (has_skip) add_skip4<H>(y, sv[r]);
+            if (relu_post) relu4(y, 0.0f);
+            if (out_f32) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(buf_u32x4, pack4_f32(y)), ors, (int)ooff[r], 0, 0);
+            else pk[r] = pack4<H>(y);
         }
         if (!out_f32) {
             if (st16) {
                 // odd rows of pk[0] <-> even rows of pk[1]: even g = [own row 0 | partner's row 0], odd g = [partner's row 1 | own row 1]
                 const auto rx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
                 const auto ry = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
-                __builtin_amdgcn_raw_buffer_store_b128(sw_u32x4{rx[0], ry[0], rx[1], ry[1]}, ors, (int)ooff16, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(buf_u32x4{rx[0], ry[0], rx[1], ry[1]}, ors, (int)ooff16, 0, 0);
             } else {
 #pragma unroll
-                for (int r = 0; r < R; ++r) __builtin_amdgcn_raw_buffer_store_b64(sw_u32x2{pk[r].x, pk[r].y}, ors, (int)ooff[r], 0, 0);
+                for (int r = 0; r < R; ++r) __builtin_amdgcn_raw_buffer_store_b64(buf_u32x2{pk[r].x, pk[r].y}, ors, (int)ooff[r], 0, 0);
             }
         }
 
@@ -349,7 +325,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) boff[kh][kw] = km_lds_off((row0 + rr + kh) * SW_BW + px + kw, half);
 
-    // ---- staging: raw buffer loads, zero padding from the descriptor bounds (as in the pair kernel) ----
+    // ---- staging: plane_fetch (conv_dev.h), zero padding from the descriptor bounds ----
     unsigned goff[NLD];
     // chunk id = tid + 256 i -> voxel (tid >> 2) + 64 i: the swizzle term (voxel >> 2) & 3 does not depend on i, so the LDS offsets of a
     // thread's chunks are loff0 + 4096 i (immediates), and only the last chunk can lie beyond the 720 of a plane
@@ -366,17 +342,10 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
         const int bh = v / SW_BW, bw = v - bh * SW_BW;
         const int gh = h0 - 1 + bh, gw = w0 - 1 + bw;
         const bool gval = id < KM_CHUNKS && (unsigned)gh < (unsigned)a.Hh && (unsigned)gw < (unsigned)a.W;
-        goff[i] = gval ? ((unsigned)(gh * a.W + gw) * (unsigned)a.in_cs + (unsigned)(c * 8)) * 2u : 0x7ffffff0u;
+        goff[i] = gval ? ((unsigned)(gh * a.W + gw) * (unsigned)a.in_cs + (unsigned)(c * 8)) * 2u : BUF_OOR;
     }
     const int plane_hi = min(a.D - 1, dend);
-    auto fetch = [&](int plane, uint4 (&reg)[NLD]) {
-        const bool pv = plane >= 0 && plane <= plane_hi;                                         // wave-uniform
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint16_t*>(inb + (long)(pv ? plane : 0) * plane_stride), (short)0, pv ? (int)plane_bytes : 0, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i)
-            reg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)goff[i], 0, 0));
-    };
+    auto fetch = [&](int plane, uint4 (&reg)[NLD]) { plane_fetch(inb, plane_stride, plane_bytes, plane_hi, goff, plane, reg); };
     auto stash = [&](int ring, const uint4 (&reg)[NLD]) {
         unsigned char* sp = smem + ring * KM_PB + loff0;
         *reinterpret_cast<uint4*>(sp) = reg[0];
@@ -390,7 +359,7 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
     float* const epc = reinterpret_cast<float*>(smem + KM_NSLOT * KM_PB);
     if (tid < 24) {
         const int k = tid & 7, which = tid >> 3;
-        epc[tid] = which == 0 ? (a.scale ? a.scale[k] : 1.0f) : which == 1 ? (a.bias ? a.bias[k] : 0.0f) : (a.floor ? a.floor[k] : 0.0f);
+        epc[tid] = which == 0 ? epi_scale(a.scale, k) : which == 1 ? epi_bias(a.bias, k) : epi_floor(a.floor, k);
     }
     const int oh = h0 + row0 + rr, ow = w0 + px;
     const bool pix_ok = oh < a.Hh && ow < a.W;
@@ -415,20 +384,10 @@ __global__ __launch_bounds__(256, 3) void conv3d_sweep8_kdm_kernel(const SweepAr
             y[k] = fmaf(y[k], sc[k], bi[k]);
             if (a.epi & PSCV_EPI_RELU_PRE) y[k] = relu_floor(y[k], fl[k]);
         }
-        if (SKIP) {
-            y[0] += Half16<H>::lo(sv.x); y[1] += Half16<H>::hi(sv.x);
-            y[2] += Half16<H>::lo(sv.y); y[3] += Half16<H>::hi(sv.y);
-        }
-        if (a.epi & PSCV_EPI_RELU_POST) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], 0.0f);
-        }
-        if (a.out_f32) {
-            *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + vox * a.out_cs + a.out_co + c0) = make_float4(y[0], y[1], y[2], y[3]);
-        } else {
-            *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + vox * a.out_cs + a.out_co + c0) =
-                make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
-        }
+        if (SKIP) add_skip4<H>(y, sv);
+        if (a.epi & PSCV_EPI_RELU_POST) relu4(y, 0.0f);
+        if (a.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + vox * a.out_cs + a.out_co + c0) = pack4_f32(y);
+        else *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + vox * a.out_cs + a.out_co + c0) = pack4<H>(y);
     };
 
     // ---- prologue: plane dbeg-1 into slot 0, planes dbeg .. dbeg+PD-1 in flight in the register FIFO ----
@@ -562,7 +521,9 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
         for (int kw = 0; kw < 3; ++kw) boff[rr][kw] = ((row0 + rr) * SW_BW + n + kw) * VB + (CIN == 16 ? (g & 1) * 16 : 0);
     const int pl0 = CIN == 8 ? g : (g >> 1);      // this lane's plane (relative to d-1) in MFMA set 0; set 1 (C_in = 16) adds 2
 
-    // (raw buffer loads as in the 32 -> 8 sweep: out-of-image chunks and out-of-volume planes come back as zeros from the hardware)
+    // (the zero-fill rule of conv_dev.h: out-of-image chunks and out-of-volume planes come back as zeros from the hardware; this
+    // kernel keeps its own fetch -- as one-chunk plane_fetch calls 16 of its 18 instances change their VGPR or SGPR counts, e.g.
+    // 8 -> 8: 109 -> 102 VGPRs, 16 -> 8: 150 -> 152 VGPRs and 60 -> 61 SGPRs, two more s_waitcnt; profiles/conv_dev_isa.txt)
     // a thread owns ONE voxel of the 10 x 18 plane and load i fetches that voxel's 16-byte chunk i: chunk 0 (channels 0..7) from
     // `in`, chunk 1 (C_in = 16: channels 8..15) from `in2` -- each load instruction has its own per-plane descriptor, so the two
     // halves of a 16-channel input may live in different tensors (the decoder's cat([deconv, enc]) is never written)
@@ -587,7 +548,7 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
             plane_stride[i] = (long)a.Hh * a.W * cs;
             plane_bytes[i] = (unsigned)(plane_stride[i] * 2 - co * 2);
             inb[i] = base + (long)b * a.D * plane_stride[i] + co;
-            goff[i] = gval ? (unsigned)(gh * a.W + gw) * (unsigned)cs * 2u : 0x7ffffff0u;
+            goff[i] = gval ? (unsigned)(gh * a.W + gw) * (unsigned)cs * 2u : BUF_OOR;
             loff[i] = v * VB + i * 16;
         }
     }
@@ -597,7 +558,7 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint16_t*>(inb[i] + (long)(pv ? plane : 0) * plane_stride[i]), (short)0, pv ? (int)plane_bytes[i] : 0, 0x00020000);
+                const_cast<uint16_t*>(inb[i] + (long)(pv ? plane : 0) * plane_stride[i]), (short)0, pv ? (int)plane_bytes[i] : 0, BUF_FLAGS);
             reg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)goff[i], 0, 0));
         }
     };
@@ -610,12 +571,7 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
 
     const int c0 = COUT == 16 ? g * 4 : (g & 1) * 4;
     float sc[4], bi[4], fl[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc[k] = a.scale ? a.scale[c0 + k] : 1.0f;
-        bi[k] = a.bias ? a.bias[c0 + k] : 0.0f;
-        fl[k] = a.floor ? a.floor[c0 + k] : 0.0f;
-    }
+    epi_load4(sc, bi, fl, a.scale, a.bias, a.floor, c0);
     // this lane's output voxels: plane dd + (g >> 1), rows row0 + r, column n
     const bool col_ok = w0 + n < a.W;
     long vrow[R];
@@ -715,21 +671,10 @@ __global__ __launch_bounds__(256, (CIN == 8 && PD <= 2) ? 4 : (CIN == 8 || (PD =
                                 y[k] = fmaf(acc[op][r][k], sc[k], bi[k]);
                                 if (a.epi & PSCV_EPI_RELU_PRE) y[k] = relu_floor(y[k], fl[k]);
                             }
-                            if (a.skip) {
-                                y[0] += Half16<H>::lo(sk[s][op][r].x); y[1] += Half16<H>::hi(sk[s][op][r].x);
-                                y[2] += Half16<H>::lo(sk[s][op][r].y); y[3] += Half16<H>::hi(sk[s][op][r].y);
-                            }
-                            if (a.epi & PSCV_EPI_RELU_POST) {
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], 0.0f);
-                            }
-                            if (a.out_f32) {
-                                *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + vox * a.out_cs + a.out_co + c0) =
-                                    make_float4(y[0], y[1], y[2], y[3]);
-                            } else {
-                                *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + vox * a.out_cs + a.out_co + c0) =
-                                    make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
-                            }
+                            if (a.skip) add_skip4<H>(y, sk[s][op][r]);
+                            if (a.epi & PSCV_EPI_RELU_POST) relu4(y, 0.0f);
+                            if (a.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + vox * a.out_cs + a.out_co + c0) = pack4_f32(y);
+                            else *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + vox * a.out_cs + a.out_co + c0) = pack4<H>(y);
                         }
                     }
                 }
@@ -797,9 +742,9 @@ int conv3d_sweep8_launch(const ConvCall& c) {
     const long tiles = (long)a.B * a.nth * a.ntw;
     if (!kdm) {
         // the plane-pair kernel stores (and reads the residual) through one descriptor per plane pair with 32-bit lane offsets
-        PSCV_CHECK_ARG(2L * c.H * c.W * c.io.out_cs * (c.io.out_f32 ? 4 : 2) < 0x7ffffff0L,
+        PSCV_CHECK_ARG(2L * c.H * c.W * c.io.out_cs * (c.io.out_f32 ? 4 : 2) < (long)BUF_OOR,
                        "pscv_conv3d(sweep): two output planes of %d x %d x %d channels exceed 2 GiB", c.H, c.W, c.io.out_cs);
-        PSCV_CHECK_ARG(!c.io.skip || 2L * c.H * c.W * c.io.skip_cs * 2 < 0x7ffffff0L,
+        PSCV_CHECK_ARG(!c.io.skip || 2L * c.H * c.W * c.io.skip_cs * 2 < (long)BUF_OOR,
                        "pscv_conv3d(sweep): two residual planes of %d x %d x %d channels exceed 2 GiB", c.H, c.W, c.io.skip_cs);
         a.st16 = !c.io.out_f32 && c.io.out_cs % 8 == 0 && c.io.out_co % 8 == 0 && (reinterpret_cast<uintptr_t>(c.io.out) & 15) == 0;
     }

@@ -17,6 +17,7 @@
 // Replaces (fdarmon/wild_deep_mvs): ConvBnReLU3D(8, 16, stride=2) models/MVSNet/model.py:49,76 (block models/MVSNet/module.py:41-48);
 // BasicBlock(8, 16, stride 2).conv1 + downsample of models/VisMVSNet/nn_utils.py:27-37, 215-226.
 #include "conv_common.h"
+#include "conv_dev.h"
 
 namespace pscv {
 
@@ -75,9 +76,7 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
     }
 
     // ---- staging descriptors: thread t owns chunks t, t + 256, t + 512 of every plane ----
-    // Loads are raw buffer loads: the descriptor covers exactly one input plane, a chunk outside the image carries an
-    // out-of-range offset and a plane outside the volume an empty descriptor -- the hardware returns zeros (= the conv's padding),
-    // so a plane costs three load instructions and no predicate, zero fill or 64-bit address arithmetic per chunk.
+    // (plane_fetch, conv_dev.h: zeros outside the image and the volume come from the descriptor's bounds; three loads per plane)
     unsigned goff[S2S_NLD];
     int loff[S2S_NLD];
     bool lval[S2S_NLD];
@@ -91,18 +90,11 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
         const int gh = 2 * oh0 - 1 + bh, gw = 2 * ow0 - 1 + bw;
         lval[i] = id < S2S_BH * S2S_BW;
         const bool gval = lval[i] && (unsigned)gh < (unsigned)a.Hi && (unsigned)gw < (unsigned)a.Wi;
-        goff[i] = gval ? (unsigned)(gh * a.Wi + gw) * (unsigned)(a.in_cs * 2) : 0x7ffffff0u;      // bytes; invalid -> out of range
+        goff[i] = gval ? (unsigned)(gh * a.Wi + gw) * (unsigned)(a.in_cs * 2) : BUF_OOR;      // bytes; invalid -> out of range
         loff[i] = (bh * S2S_PITCH + (bw & 1) * 17 + (bw >> 1)) * 16;
     }
     const int plane_hi = min(a.Di - 1, 2 * oend - 1);   // last input plane this sweep reads
-    auto fetch = [&](int plane, uint4 (&reg)[S2S_NLD]) {
-        const bool pv = plane >= 0 && plane <= plane_hi;                                         // wave-uniform
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint16_t*>(inb + (long)(pv ? plane : 0) * plane_stride), (short)0, pv ? (int)plane_bytes : 0, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < S2S_NLD; ++i)
-            reg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)goff[i], 0, 0));
-    };
+    auto fetch = [&](int plane, uint4 (&reg)[S2S_NLD]) { plane_fetch(inb, plane_stride, plane_bytes, plane_hi, goff, plane, reg); };
     auto stash = [&](int ring, const uint4 (&reg)[S2S_NLD]) {
         unsigned char* sp = smem + ring * S2S_PB;
 #pragma unroll
@@ -118,11 +110,11 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
         for (int k = 0; k < 4; ++k) {
             const int c = m * 16 + g * 4 + k;
             const bool cv = c < a.cout;
-            sc[m][k] = (a.scale && cv) ? a.scale[c] : 1.0f;
+            sc[m][k] = (a.scale && cv) ? a.scale[c] : 1.0f;      // (epi_scale & co. of conv_dev.h, with this kernel's channel guard)
             bi[m][k] = (a.bias && cv) ? a.bias[c] : 0.0f;
             fl[m][k] = (a.epi & PSCV_EPI_RELU_PRE) ? ((a.floor && cv) ? a.floor[c] : 0.0f) : -__builtin_inff();   // ReLU switches as clamps
         }
-    const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    const float lo_post = epi_lo_post(a.epi);
     const long oplane = (long)a.Ho * a.Wo * a.out_cs, splane = (long)a.Ho * a.Wo * a.skip_cs;
     unsigned lane_out[S2S_R], lane_skip[S2S_R];
     bool lane_ok[S2S_R];
@@ -195,20 +187,19 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
                     if (lane_ok[r] && m * 16 + g * 4 < a.cout) {
                         float y[4];
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) y[k] = clamp_lo(fmaf(acc[r][m][k], sc[m][k], bi[m][k]), fl[m][k]);
+                        for (int k = 0; k < 4; ++k) y[k] = relu_floor(fmaf(acc[r][m][k], sc[m][k], bi[m][k]), fl[m][k]);
                         if constexpr (PLAIN) {
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) y[k] = clamp_lo(y[k], lo_post);
+                            for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], lo_post);
                             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + obase + lane_out[r] + m * 16) =
                                 make_uint2(Half16<H>::pack_ovfl(y[0], y[1]), Half16<H>::pack_ovfl(y[2], y[3]));
                             continue;
                         }
                         uint2 sv = make_uint2(0u, 0u);
                         if (a.skip) sv = *reinterpret_cast<const uint2*>(a.skip + sbase + lane_skip[r] + m * 16);
-                        y[0] = clamp_lo(y[0] + Half16<H>::lo(sv.x), lo_post); y[1] = clamp_lo(y[1] + Half16<H>::hi(sv.x), lo_post);
-                        y[2] = clamp_lo(y[2] + Half16<H>::lo(sv.y), lo_post); y[3] = clamp_lo(y[3] + Half16<H>::hi(sv.y), lo_post);
+                        add_skip4_clamp<H>(y, sv, lo_post);
                         if (a.out_f32)
-                            *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + obase + lane_out[r] + m * 16) = make_float4(y[0], y[1], y[2], y[3]);
+                            *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + obase + lane_out[r] + m * 16) = pack4_f32(y);
                         else
                             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + obase + lane_out[r] + m * 16) =
                                 make_uint2(Half16<H>::pack_ovfl(y[0], y[1]), Half16<H>::pack_ovfl(y[2], y[3]));

@@ -11,6 +11,7 @@
 // Replaces (fdarmon/wild_deep_mvs): Sequential(ConvTranspose3d(16, 8, k3, p1, op1, s2), BatchNorm3d, ReLU) + skip add
 // models/MVSNet/model.py:67-70,81; ConvTranspose3d(16, 8) of the Vis U-Net models/VisMVSNet/nn_utils.py:232.
 #include "conv_common.h"
+#include "conv_dev.h"
 
 namespace pscv {
 
@@ -102,13 +103,8 @@ __global__ __launch_bounds__(256) void conv3d_t2p8_kernel(const Tp8Args a) {
         for (int s = 0; s < 9; ++s) wf[s] = wp[s * 64 + lane];
     }
     float sc[4], bi[4], fl[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc[k] = a.scale ? a.scale[c0 + k] : 1.0f;
-        bi[k] = a.bias ? a.bias[c0 + k] : 0.0f;
-        fl[k] = (a.epi & PSCV_EPI_RELU_PRE) ? (a.floor ? a.floor[c0 + k] : 0.0f) : -__builtin_inff();   // ReLU switches as clamps
-    }
-    const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    epi_load4<true>(sc, bi, fl, a.scale, a.bias, a.floor, c0, a.epi);   // ReLU switches as clamps
+    const float lo_post = epi_lo_post(a.epi);
     PSCV_STAMP_WAIT(1)
     __syncthreads();
     PSCV_STAMP(2)
@@ -146,9 +142,8 @@ __global__ __launch_bounds__(256) void conv3d_t2p8_kernel(const Tp8Args a) {
                 float* y = yf[ph];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) y[k] = relu_floor(fmaf(acc[k], sc[k], bi[k]), fl[k]);
-                y[0] = relu_floor(y[0] + Half16<H>::lo(sv.x), lo_post); y[1] = relu_floor(y[1] + Half16<H>::hi(sv.x), lo_post);
-                y[2] = relu_floor(y[2] + Half16<H>::lo(sv.y), lo_post); y[3] = relu_floor(y[3] + Half16<H>::hi(sv.y), lo_post);
-                pk[ph] = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
+                add_skip4_clamp<H>(yf[ph], sv, lo_post);
+                pk[ph] = pack4<H>(yf[ph]);
             }
             PSCV_STAMP(3)
             if (in_ok) {
@@ -164,7 +159,7 @@ __global__ __launch_bounds__(256) void conv3d_t2p8_kernel(const Tp8Args a) {
                     for (int ph = 0; ph < 2; ++ph) {
                         const long orow = orow0 + (long)ph * row_out;
                         if (a.out_f32)
-                            *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + orow + lane_out) = make_float4(yf[ph][0], yf[ph][1], yf[ph][2], yf[ph][3]);
+                            *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + orow + lane_out) = pack4_f32(yf[ph]);
                         else
                             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + orow + lane_out) = pk[ph];
                     }

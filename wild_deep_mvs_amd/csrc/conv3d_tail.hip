@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "conv_dev.h"
 
 namespace pscv {
 
@@ -107,17 +108,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
     for (int s = 0; s < 18; ++s) wh[s] = a.w_head[s * 64 + lane];
     const int c0 = (g & 1) * 4;                                  // this lane's channel group of a produced voxel
     float sc[4], bi[4], fl[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc[k] = a.up_scale ? a.up_scale[c0 + k] : 1.0f;
-        bi[k] = a.up_bias ? a.up_bias[c0 + k] : 0.0f;
-        fl[k] = (a.up_epi & PSCV_EPI_RELU_PRE) ? (a.up_floor ? a.up_floor[c0 + k] : 0.0f) : -__builtin_inff();
-    }
-    const float e_scale = a.hd_scale ? a.hd_scale[0] : 1.0f, e_bias = a.hd_bias ? a.hd_bias[0] : 0.0f;
-    const float lo_pre = (a.hd_epi & PSCV_EPI_RELU_PRE) ? (a.hd_floor ? a.hd_floor[0] : 0.0f) : -__builtin_inff();
-    const float lo_post = (a.hd_epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    epi_load4<true>(sc, bi, fl, a.up_scale, a.up_bias, a.up_floor, c0, a.up_epi);
+    const float e_scale = epi_scale(a.hd_scale, 0), e_bias = epi_bias(a.hd_bias, 0);
+    const float lo_pre = epi_floor_clamp(a.hd_floor, 0, a.hd_epi), lo_post = epi_lo_post(a.hd_epi);
 
-    // ---- input staging: chunk id -> (voxel, channel half); raw buffer loads, hardware zero fill outside the image / volume ----
+    // ---- input staging: chunk id -> (voxel, channel half); plane_fetch (conv_dev.h), zero fill outside the image / volume ----
     const unsigned in_plane_b = (unsigned)a.Hi * a.Wi * a.in_cs * 2;
     const unsigned in_plane_sz = in_plane_b - (unsigned)a.in_co * 2;
     const char* inb = reinterpret_cast<const char*>(a.in) + ((unsigned long)b * a.Di * in_plane_b + (unsigned long)a.in_co * 2);
@@ -132,16 +127,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
         const int gh = ih0 + r, gw = ix0 + c;
         ival[i] = id < TL_ICH;
         const bool ok = ival[i] && (unsigned)gh < (unsigned)a.Hi && (unsigned)gw < (unsigned)a.Wi;
-        igoff[i] = ok ? ((unsigned)(gh * a.Wi + gw) * (unsigned)a.in_cs + (unsigned)(half * 8)) * 2u : 0x7ffffff0u;
+        igoff[i] = ok ? ((unsigned)(gh * a.Wi + gw) * (unsigned)a.in_cs + (unsigned)(half * 8)) * 2u : BUF_OOR;
         iloff[i] = v * TL_VS + half * 16;
     }
-    auto ifetch = [&](int plane, uint4 (&reg)[2]) {
-        const bool pv = plane >= 0 && plane < a.Di;                                              // wave-uniform
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(inb + (unsigned long)(pv ? plane : 0) * in_plane_b), (short)0, pv ? (int)in_plane_sz : 0, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) reg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)igoff[i], 0, 0));
-    };
+    auto ifetch = [&](int plane, uint4 (&reg)[2]) { plane_fetch(inb, (unsigned long)in_plane_b, in_plane_sz, a.Di - 1, igoff, plane, reg); };
     auto istash = [&](int islot, const uint4 (&reg)[2]) {
         unsigned char* sp = iring + islot * TL_IPB;
 #pragma unroll
@@ -157,10 +146,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
     const unsigned sk_row_b = (unsigned)W * a.skip_cs * 2, sk_plane_b = (unsigned)Hh * sk_row_b;
     const unsigned sk_size = a.skip ? (unsigned)D * sk_plane_b : 0u;
     const char* skb = reinterpret_cast<const char*>(a.skip) + ((unsigned long)b * sk_size + (unsigned long)a.skip_co * 2);
-    const unsigned sk_voff = x_ok ? ((unsigned)ox * a.skip_cs + c0) * 2u : 0x7ffffff0u;
+    const unsigned sk_voff = x_ok ? ((unsigned)ox * a.skip_cs + c0) * 2u : BUF_OOR;
     auto skip_load = [&](int op, int orow) -> uint2 {            // op, orow wave-uniform
         const bool ok = (unsigned)op < (unsigned)D && (unsigned)orow < (unsigned)Hh;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(skb), (short)0, ok ? (int)(sk_size - a.skip_co * 2) : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(skb, ok ? (int)(sk_size - a.skip_co * 2) : 0);
         const unsigned soff = ok ? (unsigned)op * sk_plane_b + (unsigned)orow * sk_row_b : 0u;
         return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)sk_voff, (int)soff, 0));
     };
@@ -178,12 +167,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
         float y[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) y[k] = relu_floor(fmaf(acc[k], sc[k], bi[k]), fl[k]);
-        y[0] += Half16<H>::lo(sv.x); y[1] += Half16<H>::hi(sv.x); y[2] += Half16<H>::lo(sv.y); y[3] += Half16<H>::hi(sv.y);
-        if (UP_POST) {
+        add_skip4<H>(y, sv);
+        if (UP_POST) {       // (spelled out: through relu4 these instances come out with 58 more s_waitcnt)
 #pragma unroll
             for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], 0.0f);
         }
-        uint2 pk = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
+        uint2 pk = pack4<H>(y);
         // outside the volume the head sees its zero padding
         const bool inside = x_ok && (unsigned)op < (unsigned)D && (unsigned)orow < (unsigned)Hh;
         if (!inside) pk = make_uint2(0u, 0u);
@@ -306,8 +295,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) { sM[rr][ct] = -__builtin_inff(); sZ[rr][ct] = 0.f; sD[rr][ct] = 0.f; sI[rr][ct] = 0.f; }
     const unsigned lg_plane_b = (unsigned)Hh * W * 4;
-    const __amdgpu_buffer_rsrc_t lrs = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char*>(a.logits) + (unsigned long)b * D * lg_plane_b, (short)0, (int)((unsigned)D * lg_plane_b), 0x00020000);
+    const __amdgpu_buffer_rsrc_t lrs = buf_rsrc(reinterpret_cast<const char*>(a.logits) + (unsigned long)b * D * lg_plane_b, (int)((unsigned)D * lg_plane_b));
 
     for (int k = 0; k < nbk; ++k) {
         const int d0 = dbeg + k * TL_P;
@@ -356,10 +344,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_tail_kernel(const TailArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float y = fmaf(ct ? acc1[r] : acc0[r], e_scale, e_bias);
-                    if (HD_CLAMP) y = clamp_lo(clamp_lo(y, lo_pre), lo_post);
+                    if (HD_CLAMP) y = relu_floor(relu_floor(y, lo_pre), lo_post);
                     yv[r] = y;
                     const bool okr = ok && 4 * g + r < TL_P && d0 + 4 * g + r < D;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), lrs, (int)(okr ? voff : 0x7ffffff0u),
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, y), lrs, (int)(okr ? voff : BUF_OOR),
                                                           (int)(soff0 + (unsigned)r * lg_plane_b), 0);
                 }
                 if (FUSE && g < 2) {

@@ -23,6 +23,7 @@
 // Replaces (fdarmon/wild_deep_mvs): ConvBnReLU3D 32 -> 32, 32 -> 64 (stride 1), 64 -> 64 and the stride-1 ConvTranspose3d block
 // 64 -> 32 of models/CVP_MVSNet/models/net.py:50-85 at the refinement levels' sizes.
 #include "conv_common.h"
+#include "conv_dev.h"
 
 namespace pscv {
 
@@ -107,9 +108,8 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
     auto bfetch = [&](const Tile& T, uint4 (&val)[NLD]) {
         int tid_ = tid;
         asm volatile("" : "+v"(tid_));
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char*>(reinterpret_cast<const char*>(a.in) + ((unsigned long)T.b * vol_b + (unsigned long)a.in_co * 2)), (short)0,
-            (int)(vol_b - (unsigned)a.in_co * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(reinterpret_cast<const char*>(a.in) + ((unsigned long)T.b * vol_b + (unsigned long)a.in_co * 2),
+                                                   (int)(vol_b - (unsigned)a.in_co * 2));
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int c = tid_ + 512 * i;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
             const int bh = rem / WD_BW, bw = rem - bh * WD_BW;
             const int gd = T.t0d - 1 + bd, gh = T.t0h - 1 + bh, gw = T.t0w - 1 + bw;
             const bool ok = c < NCH && (unsigned)gd < (unsigned)a.D && (unsigned)gh < (unsigned)a.Hh && (unsigned)gw < (unsigned)a.W;
-            const unsigned off = ok ? (unsigned)gd * plane_b + (unsigned)gh * row_b + ((unsigned)gw * a.in_cs + cc * 8) * 2u : 0x7ffffff0u;
+            const unsigned off = ok ? (unsigned)gd * plane_b + (unsigned)gh * row_b + ((unsigned)gw * a.in_cs + cc * 8) * 2u : BUF_OOR;
             val[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0));
         }
     };
@@ -134,14 +134,14 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
     };
     uint4 wn[2][WLD];
     // (weights through a buffer descriptor: the stage's base is the scalar offset, a thread's chunk one 32-bit register)
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(a.wpk), (short)0, NSTEPS * NT * 1024, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = buf_rsrc(a.wpk, NSTEPS * NT * 1024);
     auto wfetch = [&](const int stage, const int buf) {
         const int cnt = wp_slen(CIN, stage) * NT * 64, base = wp_sbase(CIN, stage) * NT * 64;
 #pragma unroll
         for (int r = 0; r < WLD; ++r) {
             const int idx = tid + 512 * r;
             if (512 * r + 511 < cnt) wn[buf][r] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wrs, idx * 16, base * 16, 0));
-            else if (512 * r < cnt) wn[buf][r] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wrs, idx < cnt ? idx * 16 : 0x7ffffff0, base * 16, 0));
+            else if (512 * r < cnt) wn[buf][r] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(wrs, idx < cnt ? idx * 16 : (int)BUF_OOR, base * 16, 0));
         }
     };
     auto wstash = [&](const int stage, const int buf) {
@@ -160,13 +160,13 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
     wfetch(0, 0);
     wfetch(1, 1);
     if (tid < NT * 16) {
-        epi[tid] = a.scale ? a.scale[tid] : 1.0f;
-        epi[NT * 16 + tid] = a.bias ? a.bias[tid] : 0.0f;
-        epi[2 * NT * 16 + tid] = (a.epi & PSCV_EPI_RELU_PRE) ? (a.floor ? a.floor[tid] : 0.0f) : -__builtin_inff();
+        epi[tid] = epi_scale(a.scale, tid);
+        epi[NT * 16 + tid] = epi_bias(a.bias, tid);
+        epi[2 * NT * 16 + tid] = epi_floor_clamp(a.floor, tid, a.epi);
     }
     bstash(val);
     wstash(0, 0);
-    const float lo_post = (a.epi & PSCV_EPI_RELU_POST) ? 0.0f : -__builtin_inff();
+    const float lo_post = epi_lo_post(a.epi);
     const int mt0 = 2 * wave;                                   // this wave's rows (M-tiles) mt0, mt0 + 1: (d, h) = (mt / 4, mt % 4)
     // B-fragment addresses.  32 channels: anchor + constant.  64 channels (swizzled): voxel v = anchor voxel + tap voxel, chunk 4 cb + g at
     // (chunk ^ (v & 7)) -- (v & 7) = (anchor & 7) + (tap voxel & 7) mod 8, so a lane keeps one byte offset per residue r of the tap voxel
@@ -265,8 +265,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_widep_kernel(const WideArgs a, 
                 float y[4] = {relu_floor(fmaf(acc[i][m][0], sc.x, bi.x), fl.x), relu_floor(fmaf(acc[i][m][1], sc.y, bi.y), fl.y),
                               relu_floor(fmaf(acc[i][m][2], sc.z, bi.z), fl.z), relu_floor(fmaf(acc[i][m][3], sc.w, bi.w), fl.w)};
                 // (always added, +0 without a skip tensor: the brick kernel's chain, down to the sign of a zero)
-                y[0] = relu_floor(y[0] + Half16<H>::lo(skv[i][m].x), lo_post); y[1] = relu_floor(y[1] + Half16<H>::hi(skv[i][m].x), lo_post);
-                y[2] = relu_floor(y[2] + Half16<H>::lo(skv[i][m].y), lo_post); y[3] = relu_floor(y[3] + Half16<H>::hi(skv[i][m].y), lo_post);
+                add_skip4_clamp<H>(y, skv[i][m], lo_post);
                 if (staged)
                     *reinterpret_cast<uint2*>(so + n * OPITCH + m * 32 + g * 8) = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
                 else if (col_ok) {

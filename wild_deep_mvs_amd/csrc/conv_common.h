@@ -1,6 +1,7 @@
 // Host half shared by the 3-D convolution kernels (conv3d*.hip): the head of their argument blocks, the call descriptor that the
 // extern "C" entry points hand to the launchers, the launchers' declarations, the depth-chunk plan and the grid finish.
 // A new conv kernel is a kernel, a `struct XArgs : ConvIO`, a launcher declared here and one branch in pscv_conv3d.
+// The device half -- buffer descriptors and the zero-padding rule, the plane fetch, the epilogue pieces -- is conv_dev.h.
 #pragma once
 #include "pscv_common.h"
 

@@ -254,7 +254,6 @@ __device__ __forceinline__ uint32_t pack_f16x2_ovfl(float lo, float hi) {
 // non-NaN operand, which turned a diverged activation into -inf or 0 and hid it from isfinite checks): v_cmp + v_cndmask.
 // lo = -inf is the "no ReLU" constant of the conv epilogues (x < -inf is never true).
 __device__ __forceinline__ float relu_floor(float x, float lo) { return x < lo ? lo : x; }
-__device__ __forceinline__ float clamp_lo(float x, float lo) { return relu_floor(x, lo); }
 
 // 16-bit storage type tags (both are raw uint16 in memory)
 struct bf16_t { uint16_t bits; };
