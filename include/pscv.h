@@ -581,6 +581,47 @@ int pscv_tsdf_emit_faces(const int* info, const int* vincl, const int* fincl, in
 int pscv_tsdf_case_table(unsigned int* table);
 
 /*
+ * Brick-sparse TSDF volume (an addition to ABI 14: new exports only, no existing signature changes): the rule above in a second
+ * storage layout, a pool of 8 x 8 x 8 bricks behind a dense directory (csrc/tsdf_bricks.hip).  The mesh
+ * is the dense mesh: the same vertices, colours and triangles as sets, bit for bit.
+ * Lattice (nx, ny, nz), origin and voxel as above, but nx ny nz may exceed 2^31: lin = (k ny + j) nx + i is int64.  Bricks:
+ * nb* = ceil(n* / 8), nbx nby nbz < 2^31, brick index (bz nby + by) nbx + bx.  directory device int32 [nbz][nby][nbx]: the brick's
+ * pool slot or -1; brick_ids device int32 [n_bricks]: the brick of every slot, ascending; 0 <= n_bricks < 2^22.  Pool, device
+ * arrays, zero at the start: tsdf_sum fp32, weight int32, cweight int32 [n_bricks][8][8][8], rgb_sum fp32 [n_bricks][8][8][8][3]
+ * (x fastest); pool voxels outside the lattice stay zero.  A call with n_bricks 0 launches nothing.
+ *
+ * pscv_tsdf_brick_probe: a lattice point is touched when one of the 1 <= n_views <= PSCV_FUSE_MAX_VIEWS views updates it with
+ * -trunc <= sd <= trunc.  masks device int32 [nbz][nby][nbx], zero before the first call, OR-ed by every call: a touched point at
+ * local (x, y, z) of its brick sets bit (dz+1) 9 + (dy+1) 3 + (dx+1) for dx in {0}, plus -1 if x == 0, plus +1 if x == 7, and
+ * likewise dy, dz.  Brick b is to be allocated iff some brick b - (dx, dy, dz) has that bit set (the caller's step).  dmax as above;
+ * dmin device fp32 [n_views]: the smallest valid depth of each view, +inf for a view without one.
+ *
+ * pscv_tsdf_brick_integrate: pscv_tsdf_integrate on every lattice point of every brick of brick_ids.  The allocation must have been
+ * decided from all views before the first call.
+ *
+ * pscv_tsdf_brick_mark / _emit_vertices / _emit_faces: pscv_tsdf_mark / _emit_vertices / _emit_faces with "in the grid" read as "in
+ * the lattice and in an allocated brick".  info, vincl, fincl: device int32 [n_bricks][512] in pool order.  Vertices are numbered by
+ * (slot, local voxel, d), faces by (slot, local cell, tetrahedron); a face starts at its vertex of the smallest key
+ * lin(p) 7 + (d - 1) -- in the dense layout that is the smallest index, so every quad is cut alike.  keys: device int64
+ * [n_vertices], the vertices' keys, or null.
+ */
+int pscv_tsdf_brick_probe(const float* const* depth, const int* hw, int n_views, const float* cams, const float* dmax,
+                          const float* dmin, double o0, double o1, double o2, double voxel, double trunc, int nx, int ny, int nz,
+                          int* masks, void* stream);
+int pscv_tsdf_brick_integrate(const float* const* depth, const unsigned int* const* color, const int* hw, int n_views,
+                              const float* cams, const float* dmax, double o0, double o1, double o2, double voxel, double trunc,
+                              int nx, int ny, int nz, const int* brick_ids, int n_bricks, float* tsdf_sum, int* weight,
+                              float* rgb_sum, int* cweight, void* stream);
+int pscv_tsdf_brick_mark(const float* tsdf_sum, const int* weight, const int* directory, const int* brick_ids, int n_bricks, int nx,
+                         int ny, int nz, int min_weight, int* info, void* stream);
+int pscv_tsdf_brick_emit_vertices(const float* tsdf_sum, const int* weight, const float* rgb_sum, const int* cweight, const int* info,
+                                  const int* vincl, const int* directory, const int* brick_ids, int n_bricks, int nx, int ny, int nz,
+                                  double o0, double o1, double o2, double voxel, float* xyz, unsigned char* rgb, long* keys,
+                                  long n_vertices, void* stream);
+int pscv_tsdf_brick_emit_faces(const int* info, const int* vincl, const int* fincl, const int* directory, const int* brick_ids,
+                               int n_bricks, int nx, int ny, int nz, int* faces, long n_faces, void* stream);
+
+/*
  * Mesh clean-up (an addition to ABI 14: new exports only, no existing signature changes): connected components of an indexed
  * triangle mesh, removal of small components / degenerate faces / unused vertices with order-preserving compaction, and
  * area-weighted vertex normals (csrc/mesh_clean.hip).  faces device int32 [n_faces][3], vertex arrays

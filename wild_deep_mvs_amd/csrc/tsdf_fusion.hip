@@ -22,68 +22,14 @@
 //
 // Extraction: pscv_tsdf_mark writes one int32 per voxel (edge mask, flags, vertex count, face count), the caller turns the two
 // counts into inclusive prefix sums, and pscv_tsdf_emit_vertices / pscv_tsdf_emit_faces write the mesh in its defined order.
-#include "geo_common.h"
+#include "tsdf_dev.h"
 
 #include <float.h>
 
 namespace pscv {
 
-// ---- integration -------------------------------------------------------------------------------------------------------------
+// ---- integration (the rule itself: tsdf_dev.h) -----------------------------------------------------------------------------------
 constexpr int TI_TX = 64, TI_TY = 4, TI_THREADS = TI_TX * TI_TY;
-
-struct TsdfArgs {
-    const float* depth[PSCV_FUSE_MAX_VIEWS];            // [h_v, w_v]
-    const unsigned int* color[PSCV_FUSE_MAX_VIEWS];     // [h_v, w_v] rgba8, red in the low byte
-    int h[PSCV_FUSE_MAX_VIEWS], w[PSCV_FUSE_MAX_VIEWS];
-    const float* cams;                                  // [n][PSCV_GEO_CAM_FLOATS]
-    const float* dmax;                                  // [n]: the largest valid depth of each view (0 when it has none)
-    double o0, o1, o2, s, trunc;
-    int nx, ny, nz, n_views;
-    float* tsdf_sum;
-    int* weight;
-    float* rgb_sum;
-    int* cweight;
-};
-static_assert(sizeof(TsdfArgs) <= 4096, "the kernel-argument segment holds 4 KB");
-
-struct TsdfF3 { float x, y, z; };
-
-// True only when no lattice point of the box [lo, hi]^3 (coordinates as the lanes compute them; o + i s is monotone in i, so every
-// point of the tile lies in the box) can be updated by the view.  x, y, z of cf_project are affine in X, so an affine test that
-// holds at the eight corners holds inside; the corners and the lanes round differently, by at most ~20 ulp of S, the sum of the
-// absolute values of every term of the projection at the box's largest coordinates.  The margin m = 1e-9 S (1 + max(w, h)) is six
-// orders above that and far below a pixel or a voxel:
-//   * behind:  z < -m at every corner, so every lane computes z <= 0;
-//   * left:    x + z / 2 < -m at every corner: a lane with z > 0 has x / z + 0.5 < -m / (2 z) + |x / z| 2^-52 < 0 (m > 1e-9 |x|),
-//              so px < 0; "top" is the same with y;
-//   * right:   x + z / 2 - w z > m at every corner: a lane with z > 0 has x / z + 0.5 > w before rounding, >= w after, so px >= w;
-//              "bottom" is the same with y and h;
-//   * deep:    z > dmax + trunc + m at every corner: every valid d <= dmax gives d - z < -trunc - m / 2, and |d - z| < z <= S puts
-//              its rounding far below m / 2, so sd < -trunc.
-// A NaN or inf anywhere makes every comparison false: the view is kept.
-__device__ __forceinline__ bool tile_culled(const float* c, double w, double h, double dmax, double trunc, const double (&bx)[2],
-                                            const double (&by)[2], const double (&bz)[2]) {
-    const float *K = c + CAM_K, *R = c + CAM_R, *t = c + CAM_T;
-    const double ax = fmax(fabs(bx[0]), fabs(bx[1])), ay = fmax(fabs(by[0]), fabs(by[1])), az = fmax(fabs(bz[0]), fabs(bz[1]));
-    double e[3], S = 0.0;
-    for (int r = 0; r < 3; ++r)
-        e[r] = fabs((double)R[3 * r]) * ax + fabs((double)R[3 * r + 1]) * ay + fabs((double)R[3 * r + 2]) * az + fabs((double)t[r]);
-    for (int r = 0; r < 9; ++r) S += fabs((double)K[r]) * e[r % 3];
-    const double m = 1e-9 * S * (1.0 + fmax(w, h));
-    bool behind = true, left = true, right = true, top = true, bottom = true, deep = true;
-    for (int q = 0; q < 8; ++q) {
-        double x, y, z;
-        cf_project(c, bx[q & 1], by[q >> 1 & 1], bz[q >> 2], x, y, z);
-        const double gx = x + 0.5 * z, gy = y + 0.5 * z;
-        behind = behind && z < -m;
-        left = left && gx < -m;
-        top = top && gy < -m;
-        right = right && gx - w * z > m;
-        bottom = bottom && gy - h * z > m;
-        deep = deep && z > dmax + trunc + m;
-    }
-    return behind || left || right || top || bottom || deep;
-}
 
 __global__ __launch_bounds__(TI_THREADS) void tsdf_integrate_kernel(const TsdfArgs a) {
     __shared__ unsigned long long s_live;
@@ -93,147 +39,29 @@ __global__ __launch_bounds__(TI_THREADS) void tsdf_integrate_kernel(const TsdfAr
     const int k = b / (tiles_x * tiles_y), rem = b - k * (tiles_x * tiles_y);
     const int ty = rem / tiles_x, tx = rem - ty * tiles_x;
     const int i0 = tx * TI_TX, j0 = ty * TI_TY;
-    if (tid < 64) {                                               // wave 0: lane v judges view v
-        bool live = false;
-        if (tid < a.n_views) {
-            const int i1 = min(i0 + TI_TX, a.nx) - 1, j1 = min(j0 + TI_TY, a.ny) - 1;
-            const double bx[2] = {a.o0 + (double)i0 * a.s, a.o0 + (double)i1 * a.s};
-            const double by[2] = {a.o1 + (double)j0 * a.s, a.o1 + (double)j1 * a.s};
-            const double bz[2] = {a.o2 + (double)k * a.s, a.o2 + (double)k * a.s};
-            // (a.w[tid], a.h[tid] and the camera row are indexed per lane: the by-value argument struct stays in the kernel-argument
-            // segment and these become loads from it.  Indexing a COPY of the struct, or of its arrays, per lane would put it in
-            // scratch: check "ScratchSize: 0" in -Rpass-analysis=kernel-resource-usage after any change here)
-            live = !tile_culled(a.cams + (long)tid * PSCV_GEO_CAM_FLOATS, (double)a.w[tid], (double)a.h[tid], (double)a.dmax[tid],
-                                a.trunc, bx, by, bz);
-        }
-        const unsigned long long m = __ballot(live);
-        if (tid == 0) s_live = m;
+    bool keep = false;
+    if (tid < a.n_views) {                                        // wave 0: lane v judges view v (n_views <= 64)
+        const int i1 = min(i0 + TI_TX, a.nx) - 1, j1 = min(j0 + TI_TY, a.ny) - 1;
+        const double bx[2] = {a.o0 + (double)i0 * a.s, a.o0 + (double)i1 * a.s};
+        const double by[2] = {a.o1 + (double)j0 * a.s, a.o1 + (double)j1 * a.s};
+        const double bz[2] = {a.o2 + (double)k * a.s, a.o2 + (double)k * a.s};
+        // (a.w[tid], a.h[tid] and the camera row are indexed per lane: the by-value argument struct stays in the kernel-argument
+        // segment and these become loads from it.  Indexing a COPY of the struct, or of its arrays, per lane would put it in
+        // scratch: check "ScratchSize: 0" in -Rpass-analysis=kernel-resource-usage after any change here)
+        keep = !tile_culled(a.cams + (long)tid * PSCV_GEO_CAM_FLOATS, (double)a.w[tid], (double)a.h[tid], (double)a.dmax[tid],
+                            a.trunc, bx, by, bz);
     }
-    __syncthreads();
-    const unsigned long long lv = s_live;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)lv), hi = __builtin_amdgcn_readfirstlane((unsigned)(lv >> 32));
-    unsigned long long live = ((unsigned long long)hi << 32) | lo;           // (in scalar registers: the view loop is uniform)
+    const unsigned long long live = tsdf_share_live(s_live, tid < 64, keep);   // (in scalar registers: the view loop is uniform)
     if (live == 0) return;
     const int i = i0 + (tid & (TI_TX - 1)), j = j0 + tid / TI_TX;
     if (i >= a.nx || j >= a.ny) return;
     const long lin = ((long)k * a.ny + j) * a.nx + i;
-    TsdfF3* rgbp = reinterpret_cast<TsdfF3*>(a.rgb_sum) + lin;
-    double S = (double)a.tsdf_sum[lin];
-    int wgt = a.weight[lin], cw = a.cweight[lin];
-    const TsdfF3 c0 = *rgbp;
-    int cr = (int)c0.x, cg = (int)c0.y, cb = (int)c0.z;                      // (integer sums: exact in fp32 below 2^24)
-    const double X = a.o0 + (double)i * a.s, Y = a.o1 + (double)j * a.s, Z = a.o2 + (double)k * a.s;
-    while (live) {
-        const int v = __builtin_ctzll(live);
-        live &= live - 1;
-        double x, y, z;
-        cf_project(a.cams + (long)v * PSCV_GEO_CAM_FLOATS, X, Y, Z, x, y, z);
-        if (!(z > 0.0)) continue;
-        const double px = floor(x / z + 0.5), py = floor(y / z + 0.5);
-        const int w = a.w[v], h = a.h[v];
-        if (!(px >= 0.0 && px < (double)w && py >= 0.0 && py < (double)h)) continue;
-        const long o = (long)(int)py * w + (int)px;
-        const float d = a.depth[v][o];
-        if (!cf_depth_ok(d)) continue;
-        const double sd = (double)d - z;
-        if (sd < -a.trunc) continue;
-        const double q = sd / a.trunc;
-        S += q < 1.0 ? q : 1.0;
-        wgt += 1;
-        if (sd <= a.trunc) {
-            const unsigned c = a.color[v][o];
-            cr += (int)(c & 255u);
-            cg += (int)(c >> 8 & 255u);
-            cb += (int)(c >> 16 & 255u);
-            cw += 1;
-        }
-    }
-    a.tsdf_sum[lin] = (float)S;
-    a.weight[lin] = wgt;
-    *rgbp = TsdfF3{(float)cr, (float)cg, (float)cb};
-    a.cweight[lin] = cw;
+    tsdf_update_voxel(a, live, lin, a.o0 + (double)i * a.s, a.o1 + (double)j * a.s, a.o2 + (double)k * a.s);
 }
 
-// ---- extraction: marching tetrahedra ------------------------------------------------------------------------------------------
-// Corner c of a cell is p + (c & 1, c >> 1 & 1, c >> 2 & 1); tetrahedron T of the six axis orders (a, b, c) has the corners
-// (0, a, a | b, 7) at positions 0..3; its edge between positions u < v is the global edge (p + offset(c_u), c_v ^ c_u).
-//
-// The case table: entry [T][neg] for the 4-bit set `neg` of negative corner positions = the number of vertices of the cycle (0, 3
-// or 4) in bits 0-2 and vertex k's edge in bits 3 + 6 k .. 8 + 6 k as c_u | (c_v ^ c_u) << 3, in the ORIENTED cyclic order of the
-// rule: one or three negatives give the three edges at the lone corner, two negatives N0 < N1 and positives P0 < P1 give (N0,P0),
-// (N0,P1), (N1,P1), (N1,P0); with every vertex replaced by its edge's midpoint, the cycle is kept when the normal of its first
-// three midpoints has a positive dot product with (centroid of the positive corners - centroid of the negative corners), and
-// reversed otherwise -- exact in integers (midpoints doubled, centroids scaled by the two counts).  make_tet_table() IS that
-// rule, evaluated by the compiler; pscv_tsdf_case_table hands the result to tests/test_tsdf_cpu.py, which checks all 96 entries
-// against the rule restated in Python.
-struct TetTable { unsigned int e[6 * 16]; };
-
-constexpr int TET_ORDERS[6][3] = {{1, 2, 4}, {1, 4, 2}, {2, 1, 4}, {2, 4, 1}, {4, 1, 2}, {4, 2, 1}};
-
-constexpr TetTable make_tet_table() {
-    TetTable tab{};
-    for (int T = 0; T < 6; ++T) {
-        const int cc[4] = {0, TET_ORDERS[T][0], TET_ORDERS[T][0] | TET_ORDERS[T][1], 7};
-        for (int neg = 0; neg < 16; ++neg) {
-            int nn = 0, N[4] = {0, 0, 0, 0}, P[4] = {0, 0, 0, 0}, np = 0;
-            for (int u = 0; u < 4; ++u) {
-                if (neg >> u & 1) N[nn++] = u;
-                else P[np++] = u;
-            }
-            int cnt = 0, eu[4] = {0, 0, 0, 0}, ev[4] = {0, 0, 0, 0};
-            if (nn == 1 || nn == 3) {
-                const int lone = nn == 1 ? N[0] : P[0];
-                for (int u = 0; u < 4; ++u) {
-                    if (u == lone) continue;
-                    eu[cnt] = u < lone ? u : lone;
-                    ev[cnt] = u < lone ? lone : u;
-                    ++cnt;
-                }
-            } else if (nn == 2) {
-                const int pairs[4][2] = {{N[0], P[0]}, {N[0], P[1]}, {N[1], P[1]}, {N[1], P[0]}};
-                for (int q = 0; q < 4; ++q) {
-                    eu[q] = pairs[q][0] < pairs[q][1] ? pairs[q][0] : pairs[q][1];
-                    ev[q] = pairs[q][0] < pairs[q][1] ? pairs[q][1] : pairs[q][0];
-                }
-                cnt = 4;
-            }
-            unsigned int entry = (unsigned int)cnt;
-            if (cnt) {
-                int M[3][3] = {};                                            // doubled midpoints of the first three vertices
-                for (int q = 0; q < 3; ++q)
-                    for (int ax = 0; ax < 3; ++ax) M[q][ax] = (cc[eu[q]] >> ax & 1) + (cc[ev[q]] >> ax & 1);
-                const int ux = M[1][0] - M[0][0], uy = M[1][1] - M[0][1], uz = M[1][2] - M[0][2];
-                const int vx = M[2][0] - M[0][0], vy = M[2][1] - M[0][1], vz = M[2][2] - M[0][2];
-                const int nrm[3] = {uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx};
-                int dot = 0;
-                for (int ax = 0; ax < 3; ++ax) {
-                    int sp = 0, sn = 0;
-                    for (int u = 0; u < 4; ++u) {
-                        if (neg >> u & 1) sn += cc[u] >> ax & 1;
-                        else sp += cc[u] >> ax & 1;
-                    }
-                    dot += nrm[ax] * (nn * sp - np * sn);                    // (centroid difference times nn np > 0)
-                }
-                for (int q = 0; q < cnt; ++q) {
-                    const int src = dot > 0 ? q : cnt - 1 - q;
-                    const unsigned int code = (unsigned int)cc[eu[src]] | (unsigned int)(cc[ev[src]] ^ cc[eu[src]]) << 3;
-                    entry |= code << (3 + 6 * q);
-                }
-            }
-            tab.e[T * 16 + neg] = entry;
-        }
-    }
-    return tab;
-}
-
-constexpr TetTable H_TET_TABLE = make_tet_table();
-__constant__ TetTable d_tet_table = make_tet_table();
-
-// info[lin] = edge mask (bits 0-6: bit d-1 = edge (p, d) carries a vertex) | observed << 8 | negative << 9 |
-//             vertex count << 16 | face count of the cell << 24
+// ---- extraction: marching tetrahedra (the case table, the flags and the vertex and face rules: tsdf_dev.h) -------------------------
 constexpr int TM_TX = 32, TM_TY = 4, TM_TZ = 2, TM_THREADS = TM_TX * TM_TY * TM_TZ;
 constexpr int TM_PX = TM_TX + 1, TM_PY = TM_TY + 1, TM_PZ = TM_TZ + 1;
-constexpr unsigned F_OBS = 1u, F_NEG = 2u;
 
 __device__ __forceinline__ long corner_lin(long lin, int c, int nx, int ny) {
     return lin + (c & 1) + (long)(c >> 1 & 1) * nx + (long)(c >> 2) * nx * ny;
@@ -254,11 +82,7 @@ __global__ __launch_bounds__(TM_THREADS) void tsdf_mark_kernel(const float* __re
         unsigned f = 0;
         if (i < nx && j < ny && k < nz) {
             const long lin = ((long)k * ny + j) * nx + i;
-            const int wv = weight[lin];
-            if (wv >= min_weight) {
-                const double val = (double)tsdf_sum[lin] / (double)wv;
-                f = F_OBS | (val < 0.0 ? F_NEG : 0u);
-            }
+            f = tsdf_flags(tsdf_sum[lin], weight[lin], min_weight);
         }
         fl[n] = (unsigned char)f;
     }
@@ -269,36 +93,7 @@ __global__ __launch_bounds__(TM_THREADS) void tsdf_mark_kernel(const float* __re
     unsigned cf[8];                                                          // flags of the cell's eight corners
 #pragma unroll
     for (int c = 0; c < 8; ++c) cf[c] = fl[((lz + (c >> 2)) * TM_PY + ly + (c >> 1 & 1)) * TM_PX + lx + (c & 1)];
-    unsigned mask = 0;
-#pragma unroll
-    for (int d = 1; d < 8; ++d)
-        if ((cf[0] & cf[d] & F_OBS) && ((cf[0] ^ cf[d]) & F_NEG)) mask |= 1u << (d - 1);
-    unsigned faces = 0;
-#pragma unroll
-    for (int T = 0; T < 6; ++T) {
-        const int c1 = TET_ORDERS[T][0], c2 = c1 | TET_ORDERS[T][1];
-        if (cf[0] & cf[c1] & cf[c2] & cf[7] & F_OBS) {
-            const unsigned nn = (cf[0] >> 1 & 1u) + (cf[c1] >> 1 & 1u) + (cf[c2] >> 1 & 1u) + (cf[7] >> 1 & 1u);
-            faces += nn == 2 ? 2u : (nn == 1 || nn == 3) ? 1u : 0u;
-        }
-    }
-    info[((long)k * ny + j) * nx + i] = (int)(mask | cf[0] << 8 | (unsigned)__popc(mask) << 16 | faces << 24);
-}
-
-// vertex index of edge (voxel at lin2, d): the voxel's exclusive vertex offset + the edges of smaller type it carries
-__device__ __forceinline__ int edge_vertex(const int* __restrict__ info, const int* __restrict__ vincl, long lin2, int d) {
-    const unsigned f = (unsigned)info[lin2];
-    return vincl[lin2] - (int)(f >> 16 & 255u) + __popc(f & ((1u << (d - 1)) - 1u));
-}
-
-struct TsdfVal { double f, m[3]; int cw; };
-
-__device__ __forceinline__ TsdfVal load_val(const float* tsdf_sum, const int* weight, const float* rgb_sum, const int* cweight, long lin) {
-    TsdfVal r;
-    r.f = (double)tsdf_sum[lin] / (double)weight[lin];
-    r.cw = cweight[lin];
-    for (int c = 0; c < 3; ++c) r.m[c] = r.cw > 0 ? (double)rgb_sum[3 * lin + c] / (double)r.cw : 0.0;
-    return r;
+    info[((long)k * ny + j) * nx + i] = tsdf_cell_info(cf);
 }
 
 __global__ __launch_bounds__(256) void tsdf_emit_vertices_kernel(const float* __restrict__ tsdf_sum, const int* __restrict__ weight,
@@ -321,25 +116,12 @@ __global__ __launch_bounds__(256) void tsdf_emit_vertices_kernel(const float* __
         const long linq = corner_lin(lin, d, nx, ny);
         if (linq >= nvox) break;                                             // (a mask that is not pscv_tsdf_mark's reads nothing outside)
         const TsdfVal Q = load_val(tsdf_sum, weight, rgb_sum, cweight, linq);
-        const double t = P.f / (P.f - Q.f);
         const double Xq[3] = {o0 + (double)(i + (d & 1)) * s, o1 + (double)(j + (d >> 1 & 1)) * s, o2 + (double)(k + (d >> 2)) * s};
-        if (out >= 0 && out < n_vertices) {                                  // (prefix sums that do not belong to `info` write nothing)
-            for (int c = 0; c < 3; ++c) {
-                xyz[3 * out + c] = (float)(Xp[c] + t * (Xq[c] - Xp[c]));
-                double val = 0.0;
-                if (P.cw > 0 && Q.cw > 0) val = P.m[c] + t * (Q.m[c] - P.m[c]);
-                else if (P.cw > 0) val = P.m[c];
-                else if (Q.cw > 0) val = Q.m[c];
-                double by = floor(val + 0.5);
-                by = by < 0.0 ? 0.0 : by > 255.0 ? 255.0 : by;
-                rgb[3 * out + c] = (unsigned char)(int)by;
-            }
-        }
+        if (out >= 0 && out < n_vertices) tsdf_write_vertex(P, Q, Xp, Xq, xyz, rgb, out);   // (prefix sums that do not belong to `info`
+                                                                                            // write nothing)
         ++out;
     }
 }
-
-__device__ __forceinline__ int sel4(int k, int a, int b, int c, int d) { return k == 0 ? a : k == 1 ? b : k == 2 ? c : d; }
 
 __global__ __launch_bounds__(256) void tsdf_emit_faces_kernel(const int* __restrict__ info, const int* __restrict__ vincl,
                                                               const int* __restrict__ fincl, int nx, int ny, long nvox,
@@ -374,28 +156,7 @@ __global__ __launch_bounds__(256) void tsdf_emit_faces_kernel(const int* __restr
             const unsigned code = e >> (3 + 6 * n) & 63u;                     // (n >= cnt: code 0 = the cell's own voxel; not used)
             q[n] = n < cnt ? edge_vertex(info, vincl, corner_lin(lin, (int)(code & 7u), nx, ny), (int)(code >> 3)) : 0x7fffffff;
         }
-        int first = 0, best = q[0];
-#pragma unroll
-        for (int n = 1; n < 4; ++n)
-            if (q[n] < best) best = q[n], first = n;
-        const int r1 = first + 1 >= cnt ? first + 1 - cnt : first + 1, r2 = first + 2 >= cnt ? first + 2 - cnt : first + 2;
-        const int r3 = first + 3 >= cnt ? first + 3 - cnt : first + 3;
-        const int q0 = best, q1 = sel4(r1, q[0], q[1], q[2], q[3]), q2 = sel4(r2, q[0], q[1], q[2], q[3]);
-        if (out >= 0 && out < n_faces) {
-            faces[3 * out] = q0;
-            faces[3 * out + 1] = q1;
-            faces[3 * out + 2] = q2;
-        }
-        ++out;
-        if (cnt == 4) {
-            const int q3 = sel4(r3, q[0], q[1], q[2], q[3]);
-            if (out >= 0 && out < n_faces) {
-                faces[3 * out] = q0;
-                faces[3 * out + 1] = q2;
-                faces[3 * out + 2] = q3;
-            }
-            ++out;
-        }
+        tsdf_write_faces(q, q, cnt, faces, out, n_faces);
     }
 }
 

@@ -3,6 +3,8 @@
 The reference (fdarmon/wild_deep_mvs) ends at a fused point cloud and has no counterpart of this step.  The masked depth maps
 and colours that ``evaluation/fusibile.py`` prepares for the point-cloud fusion are integrated into a dense truncated signed
 distance volume (``ops.tsdf_integrate``) whose zero level set is extracted by marching tetrahedra (``ops.tsdf_extract``).
+With ``layout="bricks"`` (``args.tsdf_layout``) the volume is a pool of 8 x 8 x 8 bricks allocated only near the surface
+(``ops.tsdf_brick_*``, section 2q): the same mesh from a fraction of the memory, on lattices the dense layout refuses.
 
 ``fuse_tsdf_mesh`` is the step as a function from tensors to a mesh; ``run(dataloader, args)`` has the interface of the other
 evaluation steps and writes ``<data_path>/Meshes/<model>_<nviews>/<model>_<nviews><scene>.ply``.  It is opt-in: nothing else
@@ -67,16 +69,21 @@ def grid_dims(lo, hi, voxel: float):
 
 
 def fuse_tsdf_mesh(depths: Sequence, images: Sequence, K, R, t, *, voxel=None, trunc_voxels: float = 3, min_weight: int = 1,
-                   bounds=None, max_voxels: int = 2 ** 31 - 1, device="cuda"):
+                   bounds=None, max_voxels: int = 2 ** 31 - 1, device="cuda", layout: str = "dense", max_bricks=None):
     """depths N x [h_v,w_v] (masked pixels 0), images N x uint8 [h_v,w_v,3], K,R [N,3,3], t [N,3,1] (intrinsics at each depth map's
     resolution; tensors or numpy arrays) -> (xyz fp32 [V,3], rgb uint8 [V,3], faces int32 [F,3]) on ``device``.  ``voxel`` None =
     ``default_voxel``; the truncation is ``trunc_voxels`` voxels; ``bounds`` = ((x0,y0,z0), (x1,y1,z1)) or None = the extent of
     the unprojected valid pixels padded by the truncation.  A grid of more than ``max_voxels`` lattice points is a ValueError.
-    ``device`` is where the inputs are moved to and the volume lives, as in ``fusibile.fuse_depth_maps``; the ops run on a GPU only."""
+    ``device`` is where the inputs are moved to and the volume lives, as in ``fusibile.fuse_depth_maps``; the ops run on a GPU only.
+    ``layout`` "bricks" stores the same lattice (the same lo, dims and voxel) as a pool of 8 x 8 x 8 bricks allocated only near the
+    surface: the mesh holds the same vertices, colours and triangles bit for bit, in brick order.
+    ``max_voxels`` does not apply to it; more than ``max_bricks`` (None: 2^22 - 1) bricks is a ValueError."""
     tens = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)
     K, R, t = tens(K).to(torch.float32), tens(R).to(torch.float32), tens(t).to(torch.float32)
     d = [tens(x).to(device=device, dtype=torch.float32) for x in depths]
     c = [tens(x).to(device=device, dtype=torch.uint8) for x in images]
+    if layout not in ("dense", "bricks"):
+        raise ValueError(f"fuse_tsdf_mesh: layout must be 'dense' or 'bricks', got {layout!r}")
     if not (float(trunc_voxels) > 0.0 and math.isfinite(float(trunc_voxels))):
         raise ValueError(f"fuse_tsdf_mesh: trunc_voxels must be positive and finite, got {trunc_voxels}")
     s = default_voxel(d, K) if voxel is None else float(voxel)
@@ -91,6 +98,12 @@ def fuse_tsdf_mesh(depths: Sequence, images: Sequence, K, R, t, *, voxel=None, t
         if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a <= b for a, b in zip(lo, hi)):
             raise ValueError(f"fuse_tsdf_mesh: bounds must be ((x0,y0,z0), (x1,y1,z1)) with finite lo <= hi, got {bounds!r}")
     dims = grid_dims(lo, hi, s)
+    if layout == "bricks":
+        cams = ops.geo_filter_cams(K, R, t).to(device)
+        masks = ops.tsdf_brick_probe(d, cams, dims, origin=lo, voxel=s, trunc=trunc)
+        bricks = ops.tsdf_bricks(masks, dims, max_bricks)
+        ops.tsdf_brick_integrate(bricks, d, c, cams, origin=lo, voxel=s, trunc=trunc)
+        return ops.tsdf_brick_extract(bricks, origin=lo, voxel=s, min_weight=min_weight)
     if dims[0] * dims[1] * dims[2] > min(int(max_voxels), ops.TSDF_MAX_VOXELS):
         raise ValueError(f"fuse_tsdf_mesh: the grid of {dims[0]} x {dims[1]} x {dims[2]} voxels of {s:g} exceeds max_voxels = "
                          f"{max_voxels}: pass `bounds` or a larger `voxel`")
@@ -101,9 +114,10 @@ def fuse_tsdf_mesh(depths: Sequence, images: Sequence, K, R, t, *, voxel=None, t
 
 
 def tsdf_options(args):
-    """The keyword arguments of ``fuse_tsdf_mesh`` from ``args.tsdf_voxel``, ``tsdf_trunc_voxels``, ``tsdf_min_weight`` and
-    ``tsdf_bounds`` (each absent or None = the default of ``fuse_tsdf_mesh``)."""
-    names = (("voxel", "tsdf_voxel"), ("trunc_voxels", "tsdf_trunc_voxels"), ("min_weight", "tsdf_min_weight"), ("bounds", "tsdf_bounds"))
+    """The keyword arguments of ``fuse_tsdf_mesh`` from ``args.tsdf_voxel``, ``tsdf_trunc_voxels``, ``tsdf_min_weight``,
+    ``tsdf_bounds``, ``tsdf_layout`` and ``tsdf_max_bricks`` (each absent or None = the default of ``fuse_tsdf_mesh``)."""
+    names = (("voxel", "tsdf_voxel"), ("trunc_voxels", "tsdf_trunc_voxels"), ("min_weight", "tsdf_min_weight"), ("bounds", "tsdf_bounds"),
+             ("layout", "tsdf_layout"), ("max_bricks", "tsdf_max_bricks"))
     return {kw: getattr(args, name) for kw, name in names if getattr(args, name, None) is not None}
 
 

@@ -1087,6 +1087,247 @@ def tsdf_extract(state: TsdfVolume, *, origin, voxel: float, min_weight: int = 1
 
 
 # --------------------------------------------------------------------------------------------
+# the same volume as a pool of 8 x 8 x 8 bricks behind a dense directory
+# --------------------------------------------------------------------------------------------
+TSDF_BRICK = 8
+TSDF_MAX_BRICKS = 2 ** 22 - 1                  # a pool voxel index (slot 512 + local) fits int32
+TSDF_BRICK_BYTES = 24 * TSDF_BRICK ** 3        # the state of one brick
+
+
+@dataclass
+class TsdfBricks:
+    """A TSDF lattice of ``dims`` = (nx, ny, nz) stored as n bricks of 8 x 8 x 8: ``directory`` int32 [nbz,nby,nbx] (the brick's pool
+    slot, -1 = not allocated), ``brick_ids`` int32 [n] (the brick of every slot, ascending), the pool arrays tsdf_sum fp32, weight
+    int32, cweight int32 [n,8,8,8] and rgb_sum fp32 [n,8,8,8,3]; ``views`` counts the views integrated so far (host side)."""
+    dims: tuple
+    directory: torch.Tensor
+    brick_ids: torch.Tensor
+    tsdf_sum: torch.Tensor
+    weight: torch.Tensor
+    rgb_sum: torch.Tensor
+    cweight: torch.Tensor
+    views: int = 0
+
+    def arrays(self):
+        return self.tsdf_sum, self.weight, self.rgb_sum, self.cweight
+
+
+def _brick_dims(dims, what):
+    """(nx, ny, nz), (nbx, nby, nbz): the lattice may exceed 2^31 points, the directory may not."""
+    try:
+        nx, ny, nz = (int(v) for v in dims)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: dims must be three integers (nx, ny, nz), got {dims!r}")
+    if min(nx, ny, nz) < 1 or max(nx, ny, nz) > 2 ** 31 - 1 - TSDF_BRICK:
+        raise ValueError(f"{what}: dims {nx} x {ny} x {nz} must be positive int32")
+    nb = tuple(-(-n // TSDF_BRICK) for n in (nx, ny, nz))
+    if nb[0] * nb[1] * nb[2] >= 2 ** 31:
+        raise ValueError(f"{what}: dims {nx} x {ny} x {nz} need {nb[0]} x {nb[1]} x {nb[2]} bricks: nbx nby nbz must stay below 2^31")
+    return (nx, ny, nz), nb
+
+
+def _trunc(trunc, what):
+    tr = float(trunc)
+    if not (tr > 0.0 and math.isfinite(tr)):
+        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
+    return tr
+
+
+def _depth_maps(depths, cams, what):
+    depths = list(depths)
+    n = len(depths)
+    if n < 1:
+        raise ValueError(f"{what}: at least one depth map expected")
+    if not torch.is_tensor(cams):
+        raise ValueError(f"{what}: cams must be a tensor [V,{L.GEO_CAM_FLOATS}]")
+    _check_cams(cams, n, what)
+    for v, d in enumerate(depths):
+        if not torch.is_tensor(d) or d.dtype != torch.float32 or d.dim() != 2:
+            raise ValueError(f"{what}: depth map {v} must be fp32 [h,w], got {getattr(d, 'dtype', type(d))} {tuple(getattr(d, 'shape', ()))}")
+    return [d.contiguous() for d in depths], cams.contiguous()
+
+
+def _min_valid_depth(depths):
+    """fp32 [V] on the device: the smallest valid (0 < d finite) depth of each map, +inf for a map without one (plumbing)."""
+    def amin(d):
+        ok = (d > 0) & (d <= torch.finfo(torch.float32).max)
+        return torch.where(ok, d, torch.full_like(d, float("inf"))).flatten(-2).amin(dim=-1)
+    if all(d.shape == depths[0].shape for d in depths):
+        return amin(torch.stack(depths)).contiguous()
+    return torch.stack([amin(d) for d in depths]).contiguous()
+
+
+def tsdf_brick_probe(depths: Sequence[torch.Tensor], cams: torch.Tensor, dims, *, origin, voxel: float, trunc: float) -> torch.Tensor:
+    """Where the surface can be -> masks int32 [nbz,nby,nbx] on the GPU of the depth maps.  A lattice
+    point is touched when some view updates it with -trunc <= sd <= trunc; a touched point at local (x, y, z) of its brick sets bit
+    (dz+1) 9 + (dy+1) 3 + (dx+1) of the brick's mask for every neighbour brick (itself included) that holds one of its 26
+    neighbours.  No state is read; one pscv_tsdf_brick_probe launch per 64 views, no host synchronisation."""
+    what = "pscv.tsdf_brick_probe"
+    (nx, ny, nz), nb = _brick_dims(dims, what)
+    o, s = _tsdf_grid(origin, voxel, what)
+    tr = _trunc(trunc, what)
+    depths, cams = _depth_maps(depths, cams, what)
+    _dev(cams, *depths)
+    dev = cams.device
+    if any(d.device != dev for d in depths):
+        raise ValueError(f"{what}: depth maps and cams must be on the same device")
+    masks = torch.zeros(nb[::-1], dtype=torch.int32, device=dev)
+    nbricks = nb[0] * nb[1] * nb[2]
+    for first in range(0, len(depths), L.FUSE_MAX_VIEWS):
+        part = slice(first, min(first + L.FUSE_MAX_VIEWS, len(depths)))
+        _, dptr, hw = _maps(depths[part], what)
+        k = part.stop - first
+        dmax, dmin, cam_part = _max_valid_depth(depths[part]), _min_valid_depth(depths[part]), cams[part]
+        rc = _launch("tsdf_brick_probe", lambda: L.lib().pscv_tsdf_brick_probe(
+            dptr, hw, k, _p(cam_part), _p(dmax), _p(dmin), o[0], o[1], o[2], s, tr, nx, ny, nz, _p(masks), _stream()),
+            cost=lambda: (8.0 * nbricks, 100.0 * nbricks * k))
+        L.check(rc, "pscv_tsdf_brick_probe")
+    return masks
+
+
+def tsdf_bricks(masks: torch.Tensor, dims, max_bricks=None) -> TsdfBricks:
+    """The zeroed brick volume for the masks of ``tsdf_brick_probe``: brick b is allocated iff some brick b - (dx,dy,dz) has the bit
+    of (dx,dy,dz) set (requests that leave the directory are dropped), slots are numbered by ascending brick index.  The shifts,
+    the nonzero and the directory are torch plumbing; one host read (the number of bricks) sizes the pool.  More than ``max_bricks``
+    (None: no limit of the caller's) or 2^22 - 1 bricks is a ValueError that names the count and the bytes."""
+    what = "pscv.tsdf_bricks"
+    dims, nb = _brick_dims(dims, what)
+    if not torch.is_tensor(masks) or masks.dtype != torch.int32 or tuple(masks.shape) != nb[::-1]:
+        raise ValueError(f"{what}: masks must be int32 {nb[::-1]} (tsdf_brick_probe), got {getattr(masks, 'dtype', type(masks))} "
+                         f"{tuple(getattr(masks, 'shape', ()))}")
+    if max_bricks is not None and (isinstance(max_bricks, bool) or int(max_bricks) != max_bricks or int(max_bricks) < 0):
+        raise ValueError(f"{what}: max_bricks must be None or an integer >= 0, got {max_bricks!r}")
+    alloc = torch.zeros(masks.shape, dtype=torch.bool, device=masks.device)
+    for bit in range(27):
+        d = (bit % 3 - 1, bit // 3 % 3 - 1, bit // 9 - 1)                     # (dx, dy, dz)
+        src = tuple(slice(max(0, -v), n - max(0, v)) for v, n in zip(d[::-1], masks.shape))
+        dst = tuple(slice(max(0, v), n - max(0, -v)) for v, n in zip(d[::-1], masks.shape))
+        alloc[dst] |= (masks[src] >> bit & 1).bool()
+    brick_ids = torch.nonzero(alloc.reshape(-1)).reshape(-1)                  # (ascending; its size is the one host read)
+    n = int(brick_ids.shape[0])
+    limit = TSDF_MAX_BRICKS if max_bricks is None else min(int(max_bricks), TSDF_MAX_BRICKS)
+    if n > limit:
+        raise ValueError(f"{what}: the views ask for {n} bricks ({n * TSDF_BRICK_BYTES} bytes of state), more than "
+                         f"{'max_bricks = ' + str(max_bricks) if limit < TSDF_MAX_BRICKS else 'the 2^22 - 1 a pool can hold'}: "
+                         f"pass `bounds` or a larger `voxel`")
+    brick_ids = brick_ids.to(torch.int32)
+    directory = torch.full((alloc.numel(),), -1, dtype=torch.int32, device=masks.device)
+    directory[brick_ids.long()] = torch.arange(n, dtype=torch.int32, device=masks.device)
+    B = TSDF_BRICK
+    z = lambda dt, *more: torch.zeros((n, B, B, B) + more, dtype=dt, device=masks.device)
+    return TsdfBricks(dims, directory.reshape(alloc.shape), brick_ids, z(torch.float32), z(torch.int32), z(torch.float32, 3), z(torch.int32))
+
+
+def _tsdf_brick_state(bricks, what):
+    if not isinstance(bricks, TsdfBricks):
+        raise ValueError(f"{what}: bricks must be the TsdfBricks of ops.tsdf_bricks, got {type(bricks).__name__}")
+    (nx, ny, nz), nb = _brick_dims(bricks.dims, what)
+    ids, direc = bricks.brick_ids, bricks.directory
+    if not torch.is_tensor(ids) or ids.dtype != torch.int32 or ids.dim() != 1 or ids.shape[0] > TSDF_MAX_BRICKS:
+        raise ValueError(f"{what}: bricks.brick_ids must be int32 [n], n < 2^22")
+    if not torch.is_tensor(direc) or direc.dtype != torch.int32 or tuple(direc.shape) != nb[::-1]:
+        raise ValueError(f"{what}: bricks.directory must be int32 {nb[::-1]}")
+    n, B = int(ids.shape[0]), TSDF_BRICK
+    want = ((torch.float32, (n, B, B, B)), (torch.int32, (n, B, B, B)), (torch.float32, (n, B, B, B, 3)), (torch.int32, (n, B, B, B)))
+    for name, t, (dt, shape) in zip(("tsdf_sum", "weight", "rgb_sum", "cweight"), bricks.arrays(), want):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: bricks.{name} must be {dt} {shape}, got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return (nx, ny, nz), n
+
+
+def tsdf_brick_integrate(bricks: TsdfBricks, depths: Sequence[torch.Tensor], colors: Sequence[torch.Tensor], cams: torch.Tensor, *,
+                         origin, voxel: float, trunc: float) -> TsdfBricks:
+    """``tsdf_integrate`` on every lattice point of every allocated brick, in place: the views in ascending order, one
+    pscv_tsdf_brick_integrate launch per 64, tsdf_sum rounded to fp32 once per launch.  The views, origin, voxel and trunc must be
+    those the bricks were probed with: a brick allocated for other views would miss free-space updates."""
+    what = "pscv.tsdf_brick_integrate"
+    (nx, ny, nz), nbr = _tsdf_brick_state(bricks, what)
+    o, s = _tsdf_grid(origin, voxel, what)
+    tr = _trunc(trunc, what)
+    depths, colors = list(depths), list(colors)
+    n = len(depths)
+    if n < 1 or len(colors) != n:
+        raise ValueError(f"{what}: at least one depth map and as many colour images expected, got {n} and {len(colors)}")
+    if bricks.views + n > TSDF_MAX_VIEWS:
+        raise ValueError(f"{what}: {bricks.views} + {n} views exceed the {TSDF_MAX_VIEWS} a volume can hold (its fp32 colour sums stay "
+                         f"exact only while 255 cweight < 2^24)")
+    depths, cams = _depth_maps(depths, cams, what)
+    packed = []
+    for v, (d, c) in enumerate(zip(depths, colors)):
+        if torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
+            packed.append(c)
+        elif torch.is_tensor(c) and c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
+            packed.append(None)
+        else:
+            raise ValueError(f"{what}: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
+    _dev(cams, *depths, *bricks.arrays(), bricks.brick_ids, bricks.directory)
+    dev = bricks.tsdf_sum.device
+    for c in colors:
+        _dev(c.contiguous())
+    if any(t.device != dev for t in [cams, bricks.brick_ids, bricks.directory] + depths + colors + list(bricks.arrays())):
+        raise ValueError(f"{what}: bricks, depth maps, colours and cams must be on the same device")
+    packed = [pack_rgba8(c) if p is None else p.contiguous() for c, p in zip(colors, packed)]
+    for first in range(0, n, L.FUSE_MAX_VIEWS):
+        part = slice(first, min(first + L.FUSE_MAX_VIEWS, n))
+        _, dptr, hw = _maps(depths[part], what)
+        k = part.stop - first
+        dmax, cam_part = _max_valid_depth(depths[part]), cams[part]
+        rc = _launch("tsdf_brick_integrate", lambda: L.lib().pscv_tsdf_brick_integrate(
+            dptr, _used_ptrs(packed[part]), hw, k, _p(cam_part), _p(dmax), o[0], o[1], o[2], s, tr, nx, ny, nz, _p(bricks.brick_ids), nbr,
+            _p(bricks.tsdf_sum), _p(bricks.weight), _p(bricks.rgb_sum), _p(bricks.cweight), _stream()),
+            cost=lambda: (48.0 * 512 * nbr, 100.0 * 512 * nbr * k))
+        L.check(rc, "pscv_tsdf_brick_integrate")
+        bricks.views += k
+    return bricks
+
+
+def tsdf_brick_extract(bricks: TsdfBricks, *, origin, voxel: float, min_weight: int = 1, return_keys: bool = False):
+    """``tsdf_extract`` over a brick volume -> (xyz fp32 [V,3], rgb uint8 [V,3], faces int32 [F,3]) and, with ``return_keys``, the
+    vertices' int64 keys lin(p) 7 + (d - 1) [V].  A voxel outside the lattice or in a brick that is not allocated counts as
+    unobserved.  The mesh holds the vertices and triangles of the dense extraction, ordered by (slot, local voxel, edge type) and
+    (slot, local cell, tetrahedron); every face starts at its vertex of the smallest key, as the dense faces do."""
+    what = "pscv.tsdf_brick_extract"
+    (nx, ny, nz), nbr = _tsdf_brick_state(bricks, what)
+    o, s = _tsdf_grid(origin, voxel, what)
+    if isinstance(min_weight, bool) or int(min_weight) != min_weight or int(min_weight) < 1:
+        raise ValueError(f"{what}: min_weight must be an integer >= 1, got {min_weight!r}")
+    _dev(*bricks.arrays(), bricks.brick_ids, bricks.directory)
+    dev = bricks.tsdf_sum.device
+    nvox = nbr * TSDF_BRICK ** 3
+    empty = lambda n: (torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n, 3), dtype=torch.uint8, device=dev))
+    keys = lambda n: (torch.empty((n,), dtype=torch.int64, device=dev),) if return_keys else ()
+    if nbr == 0:
+        return empty(0) + (torch.empty((0, 3), dtype=torch.int32, device=dev),) + keys(0)
+    info = torch.empty(nvox, dtype=torch.int32, device=dev)
+    st = _stream()
+    grid = (_p(bricks.directory), _p(bricks.brick_ids), nbr, nx, ny, nz)
+    rc = _launch("tsdf_brick_mark", lambda: L.lib().pscv_tsdf_brick_mark(_p(bricks.tsdf_sum), _p(bricks.weight), *grid, int(min_weight),
+                                                                         _p(info), st), cost=lambda: (12.0 * nvox, 2.0 * nvox))
+    L.check(rc, "pscv_tsdf_brick_mark")
+    counts = info.view(torch.uint8).view(nvox, 4)[:, 2:]              # (little-endian: byte 2 = vertices, byte 3 = faces)
+    if 12 * nvox >= 2 ** 31:
+        totals = counts.sum(dim=0, dtype=torch.int64).tolist()
+        if max(totals) >= 2 ** 31:
+            raise L.PscvError(f"{what}: {totals[0]} vertices and {totals[1]} faces do not fit int32 indices")
+    vincl = torch.cumsum(counts[:, 0], dim=0, dtype=torch.int32)
+    fincl = torch.cumsum(counts[:, 1], dim=0, dtype=torch.int32)
+    n_vert, n_face = (int(v) for v in torch.stack((vincl[-1], fincl[-1])).tolist())   # the totals: the one host read
+    (xyz, rgb), faces, vkeys = empty(n_vert), torch.empty((n_face, 3), dtype=torch.int32, device=dev), keys(n_vert)
+    if n_vert == 0:
+        return (xyz, rgb, faces) + vkeys
+    rc = _launch("tsdf_brick_emit_vertices", lambda: L.lib().pscv_tsdf_brick_emit_vertices(
+        _p(bricks.tsdf_sum), _p(bricks.weight), _p(bricks.rgb_sum), _p(bricks.cweight), _p(info), _p(vincl), *grid, o[0], o[1], o[2], s,
+        _p(xyz), _p(rgb), _p(vkeys[0]) if return_keys else None, n_vert, st), cost=lambda: (8.0 * nvox + 60.0 * n_vert, 40.0 * n_vert))
+    L.check(rc, "pscv_tsdf_brick_emit_vertices")
+    if n_face:
+        rc = _launch("tsdf_brick_emit_faces", lambda: L.lib().pscv_tsdf_brick_emit_faces(_p(info), _p(vincl), _p(fincl), *grid, _p(faces),
+                                                                                         n_face, st),
+                     cost=lambda: (8.0 * nvox + 12.0 * n_face, 0.0))
+        L.check(rc, "pscv_tsdf_brick_emit_faces")
+    return (xyz, rgb, faces) + vkeys
+
+
+# --------------------------------------------------------------------------------------------
 # mesh clean-up: connected components, fragment removal, vertex normals (INTEGRATION.md section 2p)
 # --------------------------------------------------------------------------------------------
 MESH_MAX_INDEX = 2 ** 31 - 1
