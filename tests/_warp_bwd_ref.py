@@ -13,6 +13,10 @@ Sampling is ``F.grid_sample`` (bilinear, zeros, align_corners=True) in float64, 
 formulas, and the gradients come from autograd.  ``tap_scatter`` restates the bilinear scatter by hand (it does not go through
 grid_sample), which gives the per-texel tap counts and absolute sums the error-bound tests need, and a second, independent route
 to ``dsrc`` that tests/test_warp_bwd_ref_cpu.py holds against autograd.
+
+The same pieces give the FORWARD volume of ``pscv_warp_cost_rows`` (``forward``; ``variance_partial`` / ``variance_finish``;
+``positions`` with ``ref_y0``), and ``fragile`` marks the samples whose fp32 evaluation may sit on the other side of q_z = 0:
+tests/test_gpu_warp_fwd.py compares every forward kernel family with it, tests/test_warp_fwd_ref_cpu.py pins it to the oracles.
 """
 import math
 
@@ -23,8 +27,18 @@ COSTS = ("variance", "variance_cvp", "softmin", "groupcorr", "warp_only")
 GEOMS = ("proj", "homog")
 
 
-def positions(cams, depth, geom, ref_hw, src_hw):
-    """Source-map pixel index of every (view, item, plane, reference pixel): (ix, iy, qz), float64 [n_src,B,D,h,w]."""
+def _pixels(geom, ref_hw, ref_y0):
+    """Homogeneous reference pixel coordinates [3,hw] float64: integer centres (PROJ) or half-pixel centres (HOMOG); row y of the
+    slab is row y + ref_y0 of the whole grid (WarpArgs::ref_y0)."""
+    h, w = int(ref_hw[0]), int(ref_hw[1])
+    off = 0.5 if geom == "homog" else 0.0
+    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float64) + (off + int(ref_y0)), torch.arange(w, dtype=torch.float64) + off, indexing="ij")
+    return torch.stack((xx.reshape(-1), yy.reshape(-1), torch.ones(h * w, dtype=torch.float64)))
+
+
+def positions(cams, depth, geom, ref_hw, src_hw, ref_y0=0):
+    """Source-map pixel index of every (view, item, plane, reference pixel): (ix, iy, qz), float64 [n_src,B,D,h,w].  ``ref_y0``: the
+    h rows are rows [ref_y0, ref_y0 + h) of a larger reference grid whose cameras ``cams`` are."""
     assert geom in GEOMS
     h, w = int(ref_hw[0]), int(ref_hw[1])
     hs, ws = int(src_hw[0]), int(src_hw[1])
@@ -32,9 +46,7 @@ def positions(cams, depth, geom, ref_hw, src_hw):
     depth = depth.detach().cpu().double()
     n, B = cams.shape[:2]
     D = depth.shape[1]
-    off = 0.5 if geom == "homog" else 0.0
-    yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float64) + off, torch.arange(w, dtype=torch.float64) + off, indexing="ij")
-    p = torch.stack((xx.reshape(-1), yy.reshape(-1), torch.ones(h * w, dtype=torch.float64)))      # [3,hw]
+    p = _pixels(geom, (h, w), ref_y0)                                                              # [3,hw]
     dv = depth.reshape(1, B, 1, D, -1)                                                             # [1,B,1,D,1|hw]
     m0 = cams[..., 0:9].reshape(n, B, 3, 3) @ p                                                    # [n,B,3,hw]
     if geom == "proj":
@@ -126,6 +138,91 @@ def backward(ref, srcs, cams, depth, grad_out, *, geom="proj", cost="variance", 
             "dtemp": tt.grad.sum().reshape(1) if cost == "softmin" else None,
             "dtemp_cond": float(tt.grad.abs().sum() / tt.grad.sum().abs()) if cost == "softmin" else None,
             "gw": [wv.grad for wv in warped], "ix": ix, "iy": iy}
+
+
+FWD_COSTS = COSTS + ("variance_partial",)
+
+
+def variance_finish(sums, n_views, cost):
+    """(sum f, sum f^2) [2,...] over ``n_views`` views -> the variance volume, with the two formulas of ``cost_volume``."""
+    assert cost in ("variance", "variance_cvp")
+    s, sq, N = sums[0].double(), sums[1].double(), int(n_views)
+    return sq / N - (s ** 2) / (N ** 2) if cost == "variance" else sq / N - (s / N) ** 2
+
+
+def forward(ref, srcs, cams, depth, *, geom, cost, temp=0.0, ref_hw=None, ref_y0=0):
+    """The forward volume in float64 with the layout of ``ops.warp_cost``: [B,D,h,w,C] in general, [n,B,D,h,w,C/4] for the group
+    correlation, [n,B,D,h,w,C] for the plain warp, [2,B,D,h,w,C] = (sum f, sum f^2) for ``variance_partial`` (over the reference and
+    the warped views, or over the warped views alone when ``ref`` is None).  Returns (volume, ix, iy, qz), the last three
+    [n,B,D,h,w].  ``ref`` / per-pixel ``depth`` are rows [ref_y0, ref_y0 + h) of the grid whose cameras ``cams`` are.  Operands may
+    have any floating type; their values are taken as they are."""
+    assert cost in FWD_COSTS
+    srcs_cf = [_cf(s) for s in srcs]
+    B, C, hs, ws = srcs_cf[0].shape
+    h, w = (ref.shape[1:3] if ref is not None else ((hs, ws) if ref_hw is None else ref_hw))
+    ix, iy, qz = positions(cams, depth, geom, (h, w), (hs, ws), ref_y0)
+    warped = [sample(s, ix[v], iy[v]) for v, s in enumerate(srcs_cf)]
+    ref_cf = _cf(ref) if (ref is not None and cost != "warp_only") else None
+    if cost == "variance_partial":
+        s = ref_cf.unsqueeze(2).expand_as(warped[0]).clone() if ref_cf is not None else torch.zeros_like(warped[0])
+        sq = s ** 2
+        for wv in warped:
+            s, sq = s + wv, sq + wv ** 2
+        vol = torch.stack((s, sq))
+    else:
+        vol = cost_volume(ref_cf, warped, cost, float(temp))
+    return vol.movedim(1 if vol.dim() == 5 else 2, -1).contiguous(), ix, iy, qz
+
+
+FRAGILE_EPS = 2.0 ** -18         # 32 fp32 ulps: sweep_index has six roundings and two rcp approximations of one ulp each
+FRAGILE_TEXELS = 1.0 / 64
+
+
+def fragile(cams, depth, geom, ref_hw, src_hw, ref_y0=0):
+    """Boolean [n_src,B,D,h,w]: samples whose fp32 evaluation may legitimately land on the other side of the one discontinuity the
+    warp has (q_z > 0 or not), or so far from the float64 position that a comparison of values says nothing.  From float64 alone.
+
+    With e = 2^-18 and S(row) = sum of |terms| of a row of q (PROJ: the three products of ``rot p d`` and the addend ``trans``;
+    HOMOG: the three terms of ``A p`` and the three of ``(Bm p) / (d + 1e-9)``), a sample is fragile when
+    * |q_z| <= e S(z): the test ``hz > 0`` may flip.  EXACT ZEROS ARE EXEMPT: with S(z) == 0 every term of q_z is exactly zero, fp32
+      computes exactly 0 as well and the sample is behind the camera on both sides -- a rig with such a sample checks ``>`` against ``>=``;
+    * or, in front of the camera, the error of the index implied by the same relative bound on numerator and denominator,
+      u +- e (S(x) + |u| S(z)) / q_z (and likewise for v), exceeds 1/64 texel: cancellation in hx, hy or hz.  The error is taken of the
+      index that is sampled, i.e. after the index scale and the grid clamp: a position far beyond the clamp on both sides of its
+      error interval has no error at all (next to q_z = 0 every u is huge, and clamped)."""
+    assert geom in GEOMS
+    h, w = int(ref_hw[0]), int(ref_hw[1])
+    hs, ws = int(src_hw[0]), int(src_hw[1])
+    cams = cams.detach().cpu().double()
+    depth = depth.detach().cpu().double()
+    n, B = cams.shape[:2]
+    D = depth.shape[1]
+    p = _pixels(geom, (h, w), ref_y0)
+    dv = depth.reshape(1, B, 1, D, -1)
+    M0 = cams[..., 0:9].reshape(n, B, 3, 3)
+    a, sa = (M0 @ p).unsqueeze(3), (M0.abs() @ p.abs()).unsqueeze(3)                              # [n,B,3,1,hw]
+    if geom == "proj":
+        t = cams[..., 9:12].reshape(n, B, 3, 1, 1)
+        q, S = a * dv + t, sa * dv.abs() + t.abs()
+        sx = sy = 1.0
+    else:
+        M1 = cams[..., 9:18].reshape(n, B, 3, 3)
+        dd = dv + 1e-9
+        q, S = a - (M1 @ p).unsqueeze(3) / dd, sa + (M1.abs() @ p.abs()).unsqueeze(3) / dd.abs()
+        sx, sy = (ws - 1) / ws, (hs - 1) / hs
+    q, S = q.expand(n, B, 3, D, h * w), S.expand(n, B, 3, D, h * w)
+    qz, Sz = q[:, :, 2], S[:, :, 2]
+    sign = (qz.abs() <= FRAGILE_EPS * Sz) & (Sz > 0)
+    front = qz > 0
+    div = torch.where(front, qz, torch.ones_like(qz))
+    lo, hi = (-4.5, 5.5) if geom == "proj" else (-0.05, 1.05)
+    far = torch.zeros_like(front)
+    for k, (scale, size) in enumerate(((sx, ws), (sy, hs))):
+        u = q[:, :, k] / div
+        du = FRAGILE_EPS * (S[:, :, k] + u.abs() * Sz) / div
+        idx = lambda t: (t * scale).clamp(lo * (size - 1), hi * (size - 1))          # the index after the grid clamp: what is sampled
+        far |= front & (torch.maximum(idx(u + du) - idx(u), idx(u) - idx(u - du)) > FRAGILE_TEXELS)
+    return (sign | far).reshape(n, B, D, h, w)
 
 
 def tap_scatter(ix, iy, gw, src_hw):

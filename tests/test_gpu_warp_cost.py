@@ -1,4 +1,5 @@
-"""HIP fused warp + cost kernel vs the CPU oracle and the reference goldens (through the C ABI)."""
+"""HIP fused warp + cost kernel vs the CPU oracle and the reference goldens (through the C ABI).
+The kernel variants are compared with each other here; tests/test_gpu_warp_fwd.py is their independent (float64) reference."""
 import numpy as np
 import pytest
 import torch
