@@ -1,4 +1,5 @@
-"""HIP fused softmax / regression kernel vs the oracle."""
+"""HIP fused softmax / regression kernel vs the oracle.  The bounds are those of tests/test_gpu_softargmin_ref.py (4 x the worst
+error measured against float64: index 3e-6 x (D + offset), depth 3e-6 x max |plane|, confidence 3e-6, entropy 8e-6, prob 1e-6)."""
 import numpy as np
 import pytest
 import torch
@@ -24,8 +25,8 @@ def test_depth_and_confidence_from_reference_logits(env, fname):
     logits = t(g["logits"]).squeeze(1).contiguous()
     dv = t(g["depth_values"])[:, 0].contiguous()
     o = ops.softargmin(logits.cuda(), dv.cuda(), want_conf=True, want_prob=True, want_index=True)
-    check_close("depth", o["depth"].cpu(), t(g["depth"]), max_abs=2e-5 * float(dv.max()))
-    check_close("photometric confidence", o["conf"].cpu(), t(g["photometric_confidence"]), max_abs=2e-5)
+    check_close("depth", o["depth"].cpu(), t(g["depth"]), max_abs=3e-6 * float(dv.max()))
+    check_close("photometric confidence", o["conf"].cpu(), t(g["photometric_confidence"]), max_abs=3e-6)
     prob = torch.softmax(logits, 1)
     check_close("prob volume", o["prob"].cpu(), prob, max_abs=1e-6)
 
@@ -39,18 +40,18 @@ def test_per_pixel_planes_window_entropy_bf16(env):
     depth_pp = torch.rand(B, D, h, w, generator=gen) + torch.arange(D).view(1, D, 1, 1)
     o = ops.softargmin(logits.cuda(), depth_pp.cuda(), want_index=True, want_conf=True, conf_mode=1, window=2.0,
                        want_entropy=True)
-    p = torch.softmax(logits, 1)
-    idx = torch.arange(D, dtype=torch.float32).view(1, D, 1, 1)
+    p = torch.softmax(logits.double(), 1)
+    idx = torch.arange(D, dtype=torch.float64).view(1, D, 1, 1)
     e_idx = (p * idx).sum(1)
-    check_close("per-pixel depth", o["depth"].cpu(), (p * depth_pp).sum(1), max_abs=2e-5 * D)
-    check_close("expected index", o["index"].cpu(), e_idx, max_abs=2e-5 * D)
-    mask = ((idx - e_idx.unsqueeze(1)).abs() <= 2).float()
-    check_close("window prob", o["conf"].cpu(), (p * mask).sum(1), max_abs=2e-5)
-    check_close("entropy", o["entropy"].cpu(), (-p * p.clamp(1e-9, 1.0).log()).sum(1), max_abs=2e-5)
+    check_close("per-pixel depth", o["depth"].cpu(), (p * depth_pp).sum(1), max_abs=3e-6 * D)
+    check_close("expected index", o["index"].cpu(), e_idx, max_abs=3e-6 * D)
+    mask = ((idx - e_idx.unsqueeze(1)).abs() <= 2).double()
+    check_close("window prob", o["conf"].cpu(), (p * mask).sum(1), max_abs=3e-6)
+    check_close("entropy", o["entropy"].cpu(), (-p * p.clamp(1e-9, 1.0).log()).sum(1), max_abs=8e-6)
     # bf16 logits are read as bf16 and computed in fp32
     lb = logits.to(torch.bfloat16)
     ob = ops.softargmin(lb.cuda(), depth_pp.cuda())
-    check_close("bf16 logits", ob["depth"].cpu(), (torch.softmax(lb.float(), 1) * depth_pp).sum(1), max_abs=2e-5 * D)
+    check_close("bf16 logits", ob["depth"].cpu(), (torch.softmax(lb.double(), 1) * depth_pp).sum(1), max_abs=3e-6 * D)
 
 
 def test_shift_invariance_and_partials_at_full_size(env):
@@ -71,8 +72,8 @@ def test_shift_invariance_and_partials_at_full_size(env):
     se = lo[:, 1] * a + hi[:, 1] * b
     depth = (lo[:, 2] * a + hi[:, 2] * b) / se
     index = (lo[:, 3] * a + hi[:, 3] * b) / se
-    assert float((depth - full["depth"]).abs().max()) <= 1e-4
-    assert float((index - full["index"]).abs().max()) <= 2e-3
+    assert float((depth - full["depth"]).abs().max()) <= 2 * 3e-6 * 6.0         # (both sides within 3e-6 x max |plane|)
+    assert float((index - full["index"]).abs().max()) <= 2 * 3e-6 * D
 
 
 @pytest.mark.parametrize("D", [1, 5, 8, 9, 16, 24, 32])
@@ -97,8 +98,8 @@ def test_short_depth_axes_thread_per_pixel_kernel(env, D, per_pixel):
                 res[small] = ops.softargmin(logits, depth, want_index=True, want_conf=True, conf_mode=mode, window=2.0, want_entropy=True,
                                             index_offset=3)
         o = res[1]
-        check_close(f"depth D={D}", o["depth"].cpu(), (p * dd).sum(1).float(), max_abs=3e-5 * float(dd.max()))
-        check_close(f"index D={D}", o["index"].cpu(), (e_idx + 3).float(), max_abs=2e-5 * max(D, 4))
-        check_close(f"entropy D={D}", o["entropy"].cpu(), (-p * p.clamp(1e-9, 1.0).log()).sum(1).float(), max_abs=2e-5)
+        check_close(f"depth D={D}", o["depth"].cpu(), (p * dd).sum(1).float(), max_abs=3e-6 * float(dd.max()))
+        check_close(f"index D={D}", o["index"].cpu(), (e_idx + 3).float(), max_abs=3e-6 * (D + 3))
+        check_close(f"entropy D={D}", o["entropy"].cpu(), (-p * p.clamp(1e-9, 1.0).log()).sum(1).float(), max_abs=8e-6)
         for k in ("depth", "index", "entropy", "conf"):
-            check_close(f"{k} small vs slice kernel D={D} mode {mode}", o[k].cpu(), res[0][k].cpu(), max_abs=3e-5 * max(1.0, float(res[0][k].abs().max())))
+            check_close(f"{k} small vs slice kernel D={D} mode {mode}", o[k].cpu(), res[0][k].cpu(), max_abs=6e-6 * max(1.0, float(res[0][k].abs().max())))

@@ -54,6 +54,8 @@ __global__ __launch_bounds__(256) void softargmin_kernel(const SoftArgs a) {
 
     // a slice of up to SA_PMAX planes is read ONCE into registers (all loads in flight together), then reduced;
     // longer slices fall back to two passes over memory
+    // a slice whose planes are all -inf (masked planes, or no planes at all) subtracts 0 instead of its max: every e is then 0 and
+    // the slice hands (-inf, 0, 0, 0) to the merge, where expf(-inf - -inf) would have made its sums NaN
     float m = -INFINITY, se = 0.f, sd = 0.f, si = 0.f;
     if (per <= SA_PMAX) {
         float v[SA_PMAX];
@@ -61,10 +63,11 @@ __global__ __launch_bounds__(256) void softargmin_kernel(const SoftArgs a) {
         for (int k = 0; k < SA_PMAX; ++k) v[k] = (d0 + k < d1) ? ldlogit<T>(lp + (long)(d0 + k) * hw) : -INFINITY;
 #pragma unroll
         for (int k = 0; k < SA_PMAX; ++k) m = fmaxf(m, v[k]);
+        const float ms = m > -INFINITY ? m : 0.f;
 #pragma unroll
         for (int k = 0; k < SA_PMAX; ++k) {
             if (d0 + k < d1) {
-                const float e = expf(v[k] - m);
+                const float e = expf(v[k] - ms);
                 se += e;
                 if (dp) sd = fmaf(e, dp[(d0 + k) * dstep], sd);
                 si = fmaf(e, (float)(d0 + k + a.index_offset), si);
@@ -72,8 +75,9 @@ __global__ __launch_bounds__(256) void softargmin_kernel(const SoftArgs a) {
         }
     } else {
         for (int d = d0; d < d1; ++d) m = fmaxf(m, ldlogit<T>(lp + d * hw));
+        const float ms = m > -INFINITY ? m : 0.f;
         for (int d = d0; d < d1; ++d) {
-            const float e = expf(ldlogit<T>(lp + d * hw) - m);
+            const float e = expf(ldlogit<T>(lp + d * hw) - ms);
             se += e;
             if (dp) sd = fmaf(e, dp[d * dstep], sd);
             si = fmaf(e, (float)(d + a.index_offset), si);
@@ -119,7 +123,7 @@ __global__ __launch_bounds__(256) void softargmin_kernel(const SoftArgs a) {
                 for (int d = dlo; d <= dhi; ++d)
                     if (fabsf((float)d - lidx) <= a.window) c += expf(ldlogit<T>(lp + d * hw) - M) * inv;
             }
-            a.o_conf[pix] = c;
+            a.o_conf[pix] = eidx == eidx ? c : eidx;   // a NaN column selects no plane: its confidence is NaN like torch's p * mask
         }
     }
     if (a.o_entropy || a.o_prob) {
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(256) void softargmin_small_kernel(const SoftArgs a)
             for (int d = 0; d < DMAX; ++d)                    // |d - E[index]| <= window                  nn_utils.py:464-465
                 if (fabsf((float)d - lidx) <= a.window) c += v[d] * inv;
         }
-        a.o_conf[pix] = c;
+        a.o_conf[pix] = eidx == eidx ? c : eidx;
     }
     if (a.o_entropy) {
         float ent = 0.f;

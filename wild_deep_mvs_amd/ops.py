@@ -2604,9 +2604,11 @@ def uncert_net(entropy: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
 def softargmin(logits: torch.Tensor, depth: Optional[torch.Tensor] = None, *, want_index: bool = False,
                want_conf: bool = False, conf_mode: int = 0, window: float = 2.0, want_entropy: bool = False,
                want_prob: bool = False, want_partials: bool = False, index_offset: int = 0, into: Optional[dict] = None) -> dict:
-    """logits [B,D,h,w] (fp32 or bf16); depth [B,D] or [B,D,h,w] fp32.  Returns a dict with the requested
+    """logits [B,D,h,w] (fp32, bf16 or fp16; 16-bit logits are read as stored and every sum is fp32); depth [B,D] or
+    [B,D,h,w] fp32.  Returns a dict with the requested
     maps, each [B,h,w] fp32 (``prob`` [B,D,h,w], ``partials`` [B,4,h,w]).  ``into`` = {name: tensor}: write those maps into
-    the caller's contiguous fp32 tensors (e.g. batch slices of one buffer for all source views) instead of new ones."""
+    the caller's contiguous fp32 tensors (e.g. batch slices of one buffer for all source views) instead of new ones.
+    torch.softmax semantics: a -inf logit weighs zero; a pixel whose logits are all -inf, or hold NaN or +inf, is NaN in every map."""
     _dev(logits, depth)
     if logits.dim() != 4:
         raise ValueError("pscv.softargmin: logits must be [B,D,h,w]")
