@@ -402,8 +402,7 @@ int cf_pass(const char* what, int view, int tag, const float* const* depth, cons
     using namespace pscv;
     PSCV_CHECK_ARG(depth && color && fused && claim && hw && cams && overlap && counter && workspace,
                    "%s: null pointer argument", what);
-    PSCV_CHECK_ARG(n_views >= 2 && n_views <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [2,%d]", what, n_views,
-                   PSCV_FUSE_MAX_VIEWS);
+    if (check_view_count(what, n_views, 2)) return -1;
     PSCV_CHECK_ARG(view >= 0 && view < n_views, "%s: view %d outside [0,%d)", what, view, n_views);
     const unsigned long long processed = (unsigned long long)processed_mask;
     PSCV_CHECK_ARG(!((processed >> view) & 1ull), "%s: view %d is already processed", what, view);
@@ -416,21 +415,16 @@ int cf_pass(const char* what, int view, int tag, const float* const* depth, cons
     PSCV_CHECK_ARG(capacity >= 0 && (capacity == 0 || (out_xyz && out_rgb)), "%s: bad output buffer (capacity %ld)", what,
                    capacity);
     typename CfArgsOf<NORMALS>::type a;
-    if (fill_views(a, a.fused, what, n_views, depth, color, fused, hw)) return -1;
-    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n_views;
-        a.claim[v] = on ? claim[v] : nullptr;
-        a.overlap[v] = on ? ((unsigned long long)overlap[v] & ~(1ull << v)) & (n_views == 64 ? ~0ull : ((1ull << n_views) - 1ull)) : 0ull;
-        PSCV_CHECK_ARG(!on || claim[v], "%s: view %d has a null pointer", what, v);
-    }
+    if (fill_views(a, what, depth, hw, n_views) || fill_view_ptrs(a.color, what, color, n_views) ||
+        fill_view_ptrs(a.fused, what, fused, n_views) || fill_view_ptrs(a.claim, what, claim, n_views))
+        return -1;
+    const unsigned long long all = n_views == 64 ? ~0ull : ((1ull << n_views) - 1ull);
+    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) a.overlap[v] = v < n_views ? ((unsigned long long)overlap[v] & ~(1ull << v)) & all : 0ull;
     if constexpr (NORMALS) {
         PSCV_CHECK_ARG(normal, "%s: null pointer argument", what);
         PSCV_CHECK_ARG(max_normal_error > 0.0f && max_normal_error <= 180.0f, "%s: max_normal_error=%g outside (0,180] degrees", what,
                        (double)max_normal_error);
-        for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-            a.normal[v] = v < n_views ? normal[v] : nullptr;
-            PSCV_CHECK_ARG(v >= n_views || normal[v], "%s: view %d has a null normal map", what, v);
-        }
+        if (fill_view_ptrs(a.normal, what, normal, n_views, "normal map")) return -1;
         a.min_cos = cos((double)max_normal_error * 3.14159265358979323846 / 180.0);
     }
     const long npix = (long)a.h[view] * a.w[view], nseg = cf_nseg(npix);
@@ -456,22 +450,21 @@ int cf_pass(const char* what, int view, int tag, const float* const* depth, cons
     const long nblk = (npix + groups - 1) / groups;
     PSCV_CHECK_ARG(nblk < (1L << 31), "%s: %ld blocks", what, nblk);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (w2) hipLaunchKernelGGL((colmap_fuse_kernel<2, false, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    else hipLaunchKernelGGL((colmap_fuse_kernel<1, false, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    PSCV_CHECK_LAUNCH(what);
-    if (w2) hipLaunchKernelGGL((colmap_fuse_kernel<2, true, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    else hipLaunchKernelGGL((colmap_fuse_kernel<1, true, NORMALS>), dim3((unsigned)nblk), dim3(CF_WAVE), 0, st, a);
-    PSCV_CHECK_LAUNCH(what);
-    const unsigned aux = (unsigned)((npix + CF_AUX_THREADS - 1) / CF_AUX_THREADS);
-    hipLaunchKernelGGL(colmap_count_kernel, dim3(aux), dim3(CF_AUX_THREADS), 0, st, a.flag, npix, seg_count);
-    PSCV_CHECK_LAUNCH(what);
-    hipLaunchKernelGGL((scan_kernel<CF_SCAN_THREADS, long long, true>), dim3(1), dim3(CF_SCAN_THREADS), 0, st, seg_count, seg_off, counter,
-                       (int)nseg);
-    PSCV_CHECK_LAUNCH(what);
-    hipLaunchKernelGGL(colmap_scatter_kernel, dim3(aux), dim3(CF_AUX_THREADS), 0, st, a.flag, seg_off, a.stage, npix, view,
-                       (long long)capacity, out_xyz, out_normal, out_rgb, out_view, out_pixel);
-    PSCV_CHECK_LAUNCH(what);
-    return 0;
+    const dim3 grid((unsigned)nblk), wave(CF_WAVE);
+    int rc = w2 ? launch(what, colmap_fuse_kernel<2, false, NORMALS>, grid, wave, 0, st, a)
+                : launch(what, colmap_fuse_kernel<1, false, NORMALS>, grid, wave, 0, st, a);
+    if (rc) return rc;
+    rc = w2 ? launch(what, colmap_fuse_kernel<2, true, NORMALS>, grid, wave, 0, st, a)
+            : launch(what, colmap_fuse_kernel<1, true, NORMALS>, grid, wave, 0, st, a);
+    if (rc) return rc;
+    const dim3 aux((unsigned)((npix + CF_AUX_THREADS - 1) / CF_AUX_THREADS)), aux_threads(CF_AUX_THREADS);
+    rc = launch(what, colmap_count_kernel, aux, aux_threads, 0, st, a.flag, npix, seg_count);
+    if (rc) return rc;
+    rc = launch(what, scan_kernel<CF_SCAN_THREADS, long long, true>, dim3(1), dim3(CF_SCAN_THREADS), 0, st, seg_count, seg_off, counter,
+                (int)nseg);
+    if (rc) return rc;
+    return launch(what, colmap_scatter_kernel, aux, aux_threads, 0, st, a.flag, seg_off, a.stage, npix, view, (long long)capacity, out_xyz,
+                  out_normal, out_rgb, out_view, out_pixel);
 }
 }  // namespace
 

@@ -176,15 +176,17 @@ extern "C" int pscv_fuse_depth_pass(int pass, const float* const* depth, const u
                                     int* out_view, int* out_pixel, long capacity, long long* counter, void* workspace,
                                     long workspace_bytes, void* stream) {
     using namespace pscv;
+    const char* what = "pscv_fuse_depth_pass";
     PSCV_CHECK_ARG(depth && color && used && hw && cams && counter && workspace, "pscv_fuse_depth_pass: null pointer argument");
-    PSCV_CHECK_ARG(n_views >= 2 && n_views <= PSCV_FUSE_MAX_VIEWS, "pscv_fuse_depth_pass: n_views=%d outside [2,%d]", n_views,
-                   PSCV_FUSE_MAX_VIEWS);
+    if (check_view_count(what, n_views, 2)) return -1;
     PSCV_CHECK_ARG(pass >= 0 && pass < n_views, "pscv_fuse_depth_pass: pass %d outside [0,%d)", pass, n_views);
     PSCV_CHECK_ARG(capacity >= 0 && (capacity == 0 || (out_xyz && out_rgb)), "pscv_fuse_depth_pass: bad output buffer (capacity %ld)",
                    capacity);
     PSCV_CHECK_ARG(num_consistent >= 0, "pscv_fuse_depth_pass: num_consistent=%d < 0", num_consistent);
     FuseArgs a;
-    if (fill_views(a, a.used, "pscv_fuse_depth_pass", n_views, depth, color, used, hw)) return -1;
+    if (fill_views(a, what, depth, hw, n_views) || fill_view_ptrs(a.color, what, color, n_views) ||
+        fill_view_ptrs(a.used, what, used, n_views))
+        return -1;
     const int h = a.h[pass], w = a.w[pass];
     const long nseg = fuse_nseg(h, w);
     PSCV_CHECK_ARG(workspace_bytes >= pscv_fuse_depth_workspace(h, w), "pscv_fuse_depth_pass: workspace of %ld bytes < %ld",
@@ -199,15 +201,14 @@ extern "C" int pscv_fuse_depth_pass(int pass, const float* const* depth, const u
     a.n = n_views; a.i = pass; a.nsx = (w + FUSE_TW - 1) / FUSE_TW; a.need = num_consistent;
     a.disp_thresh = disp_thresh; a.depth_min = depth_min; a.depth_max = depth_max;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(fuse_depth_kernel, dim3((unsigned)a.nsx, (unsigned)((h + FUSE_TH - 1) / FUSE_TH)), dim3(FUSE_THREADS), 0, s, a);
-    PSCV_CHECK_LAUNCH("pscv_fuse_depth_pass (fuse)");
+    int rc = launch("pscv_fuse_depth_pass (fuse)", fuse_depth_kernel, dim3((unsigned)a.nsx, (unsigned)((h + FUSE_TH - 1) / FUSE_TH)),
+                    dim3(FUSE_THREADS), 0, s, a);
+    if (rc) return rc;
     PSCV_CHECK_ARG(nseg < (1L << 31), "pscv_fuse_depth_pass: %ld segments", nseg);
-    hipLaunchKernelGGL((scan_kernel<FUSE_SCAN_THREADS, long long, true>), dim3(1), dim3(FUSE_SCAN_THREADS), 0, s, seg_count, seg_off, counter,
-                       (int)nseg);
-    PSCV_CHECK_LAUNCH("pscv_fuse_depth_pass (scan)");
+    rc = launch("pscv_fuse_depth_pass (scan)", scan_kernel<FUSE_SCAN_THREADS, long long, true>, dim3(1), dim3(FUSE_SCAN_THREADS), 0, s,
+                seg_count, seg_off, counter, (int)nseg);
+    if (rc) return rc;
     const long nslot = nseg * FUSE_TW;
-    hipLaunchKernelGGL(fuse_scatter_kernel, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, s, seg_count, seg_off, stage, nslot,
-                       pass, a.nsx, w, (long long)capacity, out_xyz, out_rgb, out_view, out_pixel);
-    PSCV_CHECK_LAUNCH("pscv_fuse_depth_pass (scatter)");
-    return 0;
+    return launch("pscv_fuse_depth_pass (scatter)", fuse_scatter_kernel, dim3((unsigned)((nslot + 255) / 256)), dim3(256), 0, s, seg_count,
+                  seg_off, stage, nslot, pass, a.nsx, w, (long long)capacity, out_xyz, out_rgb, out_view, out_pixel);
 }

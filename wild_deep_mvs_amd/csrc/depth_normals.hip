@@ -183,24 +183,17 @@ extern "C" int pscv_depth_normals(const float* const* depth, const int* hw, int 
     using namespace pscv;
     const char* what = "pscv_depth_normals";
     PSCV_CHECK_ARG(depth && hw && cams && normal, "%s: null pointer argument", what);
-    PSCV_CHECK_ARG(n_views >= 1 && n_views <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [1,%d]", what, n_views, PSCV_FUSE_MAX_VIEWS);
+    if (check_view_count(what, n_views, 1)) return -1;
     PSCV_CHECK_ARG(radius >= 1 && radius <= DN_MAX_RADIUS, "%s: radius=%d outside [1,%d]", what, radius, DN_MAX_RADIUS);
     PSCV_CHECK_ARG(rel_gate > 0.0 && rel_gate <= DBL_MAX, "%s: rel_gate=%g must be positive and finite", what, rel_gate);
     const int window = (2 * radius + 1) * (2 * radius + 1);
     PSCV_CHECK_ARG(min_support >= 3 && min_support <= window, "%s: min_support=%d outside [3,%d]", what, min_support, window);
     DnArgs a;
+    if (fill_views(a, what, depth, hw, n_views) || fill_view_ptrs(a.normal, what, normal, n_views) ||
+        fill_view_ptrs(a.support, what, support, n_views))
+        return -1;
     long max_tiles = 0;
-    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n_views;
-        a.depth[v] = on ? depth[v] : nullptr;
-        a.normal[v] = on ? normal[v] : nullptr;
-        a.support[v] = on && support ? support[v] : nullptr;
-        a.h[v] = on ? hw[2 * v] : 1;
-        a.w[v] = on ? hw[2 * v + 1] : 1;
-        if (!on) continue;
-        PSCV_CHECK_ARG(depth[v] && normal[v] && (!support || support[v]), "%s: view %d has a null pointer", what, v);
-        PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31), "%s: view %d has bad size %dx%d", what, v,
-                       a.h[v], a.w[v]);
+    for (int v = 0; v < n_views; ++v) {
         const long tiles = (long)((a.h[v] + DN_TH - 1) / DN_TH) * ((a.w[v] + DN_TW - 1) / DN_TW);
         if (tiles > max_tiles) max_tiles = tiles;
     }
@@ -223,17 +216,14 @@ extern "C" int pscv_point_world_normals(const int* view, const int* pixel, long 
     const char* what = "pscv_point_world_normals";
     PSCV_CHECK_ARG(n_points >= 0, "%s: n_points=%ld < 0", what, n_points);
     PSCV_CHECK_ARG(normal && hw && cams, "%s: null pointer argument", what);
-    PSCV_CHECK_ARG(n_views >= 1 && n_views <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [1,%d]", what, n_views, PSCV_FUSE_MAX_VIEWS);
+    if (check_view_count(what, n_views, 1)) return -1;
     PwnArgs a;
+    if (fill_view_ptrs(a.normal, what, normal, n_views)) return -1;
     for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n_views;
-        a.normal[v] = on ? normal[v] : nullptr;
         a.pixels[v] = 0;
-        if (!on) continue;
-        const int h = hw[2 * v], w = hw[2 * v + 1];
-        PSCV_CHECK_ARG(normal[v], "%s: view %d has a null pointer", what, v);
-        PSCV_CHECK_ARG(h > 0 && w > 0 && (long)h * w < (1L << 31), "%s: view %d has bad size %dx%d", what, v, h, w);
-        a.pixels[v] = h * w;
+        if (v >= n_views) continue;
+        if (check_view_size(what, v, hw[2 * v], hw[2 * v + 1])) return -1;
+        a.pixels[v] = hw[2 * v] * hw[2 * v + 1];
     }
     if (n_points == 0) return 0;
     PSCV_CHECK_ARG(view && pixel && out, "%s: null pointer argument", what);

@@ -1,4 +1,5 @@
-// Shared pieces of the evaluation kernels (geo_filter, depth_fusion, colmap_fusion, patch_match, point_metrics).  gfx950.
+// Shared pieces of the evaluation kernels.  Included by geo_filter, depth_fusion, colmap_fusion, view_covis, depth_normals, patch_match,
+// point_metrics and, through tsdf_dev.h, tsdf_fusion and tsdf_bricks.  gfx950.
 #pragma once
 #include "pscv_common.h"
 
@@ -103,23 +104,38 @@ __global__ __launch_bounds__(THREADS) void scan_kernel(const int* __restrict__ c
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 inline long align256(long bytes) { return (bytes + 255) / 256 * 256; }
 
-// The per-view table of a fusion pass (depth, color, h, w and the caller's mask array `amask`) for views [0, n); the entries past
-// n are null, 1 x 1.  Returns -1 with the error set when a view has a null pointer or a bad size.
-template <typename Args, typename Mask>
-int fill_views(Args& a, Mask* (&amask)[PSCV_FUSE_MAX_VIEWS], const char* what, int n, const float* const* depth,
-               const unsigned int* const* color, Mask* const* mask, const int* hw) {
+// The view table of a multi-view operator.  An operator that takes up to PSCV_FUSE_MAX_VIEWS views of different sizes carries them
+// as kernel arguments: a struct with depth[], h[], w[] (filled by fill_views) and whatever per-view companion pointers it needs
+// (fill_view_ptrs).  Each helper returns -1 with the error set.
+inline int check_view_count(const char* what, int n, int lo) {
+    PSCV_CHECK_ARG(n >= lo && n <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [%d,%d]", what, n, lo, PSCV_FUSE_MAX_VIEWS);
+    return 0;
+}
+inline int check_view_size(const char* what, int v, int h, int w) {
+    PSCV_CHECK_ARG(h > 0 && w > 0 && (long)h * w < (1L << 31), "%s: view %d has bad size %dx%d", what, v, h, w);
+    return 0;
+}
+// a.depth, a.h, a.w = the views [first, first + n) of depth / hw; the entries past n are null, 1 x 1
+template <typename Args>
+int fill_views(Args& a, const char* what, const float* const* depth, const int* hw, int n, int first = 0) {
+    for (int k = 0; k < PSCV_FUSE_MAX_VIEWS; ++k) {
+        const bool on = k < n;
+        const int v = first + k;
+        a.depth[k] = on ? depth[v] : nullptr;
+        a.h[k] = on ? hw[2 * v] : 1;
+        a.w[k] = on ? hw[2 * v + 1] : 1;
+        if (!on) continue;
+        PSCV_CHECK_ARG(depth[v], "%s: view %d has a null pointer", what, v);
+        if (check_view_size(what, v, a.h[k], a.w[k])) return -1;
+    }
+    return 0;
+}
+// dst = src[0 .. n), null past n; a null src is an optional array that was not given: every entry null
+template <typename T>
+int fill_view_ptrs(T* (&dst)[PSCV_FUSE_MAX_VIEWS], const char* what, T* const* src, int n, const char* noun = "pointer") {
     for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n;
-        a.depth[v] = on ? depth[v] : nullptr;
-        a.color[v] = on ? color[v] : nullptr;
-        amask[v] = on ? mask[v] : nullptr;
-        a.h[v] = on ? hw[2 * v] : 1;
-        a.w[v] = on ? hw[2 * v + 1] : 1;
-        if (on) {
-            PSCV_CHECK_ARG(depth[v] && color[v] && mask[v], "%s: view %d has a null pointer", what, v);
-            PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31), "%s: view %d has bad size %dx%d", what, v,
-                           a.h[v], a.w[v]);
-        }
+        dst[v] = src && v < n ? src[v] : nullptr;
+        PSCV_CHECK_ARG(!src || v >= n || src[v], "%s: view %d has a null %s", what, v, noun);
     }
     return 0;
 }

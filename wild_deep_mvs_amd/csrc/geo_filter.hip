@@ -134,7 +134,5 @@ extern "C" int pscv_geo_filter(const float* depth, const float* const* src_depth
     a.n_src = n_src; a.h = h; a.w = w; a.need = num_consistent - 1;
     a.max_reproj = max_reproj_error; a.depth_thr = depth_threshold; a.min_tri = min_tri_angle;
     const long nblk = ((long)h * w + 255) / 256;
-    hipLaunchKernelGGL(geo_filter_kernel, dim3((unsigned)nblk), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    PSCV_CHECK_LAUNCH("pscv_geo_filter");
-    return 0;
+    return launch("pscv_geo_filter", geo_filter_kernel, dim3((unsigned)nblk), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
 }

@@ -487,10 +487,8 @@ extern "C" int pscv_patch_match_init(float* state, int h, int w, const float* ca
     a.dmin = depth_min; a.dmax = depth_max;
     a.seed = (uint32_t)seed; a.view = (uint32_t)view;
     const long n = (long)h * w;
-    hipLaunchKernelGGL(patch_match_init_kernel, dim3((unsigned)((n + PM_THREADS - 1) / PM_THREADS)), dim3(PM_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    PSCV_CHECK_LAUNCH("pscv_patch_match_init");
-    return 0;
+    return launch("pscv_patch_match_init", patch_match_init_kernel, dim3((unsigned)((n + PM_THREADS - 1) / PM_THREADS)), dim3(PM_THREADS), 0,
+                  reinterpret_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int pscv_patch_match_cost(const float* state, const float* ref, int h, int w, const float* const* src, const int* src_hw,
@@ -502,9 +500,8 @@ extern "C" int pscv_patch_match_cost(const float* state, const float* ref, int h
     PSCV_CHECK_ARG(state && out_cost, "pscv_patch_match_cost: null state or out_cost");
     a.state = reinterpret_cast<float4*>(const_cast<float*>(state));
     a.out_cost = out_cost; a.out_err = out_err; a.out_agg = out_agg;
-    hipLaunchKernelGGL(patch_match_kernel<PM_COST>, pm_grid(PM_COST, h, w), dim3(PM_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
-    PSCV_CHECK_LAUNCH("pscv_patch_match_cost");
-    return 0;
+    return launch("pscv_patch_match_cost", patch_match_kernel<PM_COST>, pm_grid(PM_COST, h, w), dim3(PM_THREADS), 0,
+                  reinterpret_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int pscv_patch_match_half_step(float* state, const float* ref, int h, int w, const float* const* src, const int* src_hw,
@@ -526,9 +523,8 @@ extern "C" int pscv_patch_match_half_step(float* state, const float* ref, int h,
     a.colour = colour; a.delta = delta; a.theta = theta;
     a.out_choice = out_choice;
     a.out_cand = reinterpret_cast<float4*>(out_cand);
-    hipLaunchKernelGGL(patch_match_kernel<PM_HALF>, pm_grid(PM_HALF, h, w), dim3(PM_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
-    PSCV_CHECK_LAUNCH("pscv_patch_match_half_step");
-    return 0;
+    return launch("pscv_patch_match_half_step", patch_match_kernel<PM_HALF>, pm_grid(PM_HALF, h, w), dim3(PM_THREADS), 0,
+                  reinterpret_cast<hipStream_t>(stream), a);
 }
 
 extern "C" int pscv_patch_match_filter(const float* state, const float* ref, int h, int w, const float* const* src, const int* src_hw,
@@ -541,8 +537,6 @@ extern "C" int pscv_patch_match_filter(const float* state, const float* ref, int
     PSCV_CHECK_ARG(state && out_depth && out_normal, "pscv_patch_match_filter: null state or output");
     a.state = reinterpret_cast<float4*>(const_cast<float*>(state));
     a.out_depth = out_depth; a.out_normal = out_normal; a.out_count = out_count;
-    hipLaunchKernelGGL(patch_match_kernel<PM_FILTER>, pm_grid(PM_FILTER, h, w), dim3(PM_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    PSCV_CHECK_LAUNCH("pscv_patch_match_filter");
-    return 0;
+    return launch("pscv_patch_match_filter", patch_match_kernel<PM_FILTER>, pm_grid(PM_FILTER, h, w), dim3(PM_THREADS), 0,
+                  reinterpret_cast<hipStream_t>(stream), a);
 }

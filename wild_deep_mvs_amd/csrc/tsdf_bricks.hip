@@ -18,7 +18,6 @@
 // lin(p) 7 + (d - 1), which in the dense layout is the smallest index: every quad is cut as the dense one.
 #include "tsdf_dev.h"
 
-#include <float.h>
 #include <limits.h>
 
 namespace pscv {
@@ -277,39 +276,6 @@ static int check_pool(const char* what, int n_bricks) {
     return 0;
 }
 
-static int check_grid(const char* what, double o0, double o1, double o2, double voxel) {
-    PSCV_CHECK_ARG(fabs(o0) <= DBL_MAX && fabs(o1) <= DBL_MAX && fabs(o2) <= DBL_MAX, "%s: origin (%g, %g, %g) must be finite", what, o0,
-                   o1, o2);
-    PSCV_CHECK_ARG(voxel > 0.0 && voxel <= DBL_MAX, "%s: voxel=%g must be positive and finite", what, voxel);
-    return 0;
-}
-
-// the views and the lattice of a probe or an integration call (color null: the probe reads no colour)
-static int fill_views(const char* what, TsdfArgs& a, const float* const* depth, const unsigned int* const* color, const int* hw,
-                      int n_views, const float* cams, const float* dmax, double o0, double o1, double o2, double voxel, double trunc,
-                      int nx, int ny, int nz) {
-    PSCV_CHECK_ARG(n_views >= 1 && n_views <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [1,%d]", what, n_views, PSCV_FUSE_MAX_VIEWS);
-    if (check_grid(what, o0, o1, o2, voxel)) return -1;
-    PSCV_CHECK_ARG(trunc > 0.0 && trunc <= DBL_MAX, "%s: trunc=%g must be positive and finite", what, trunc);
-    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n_views;
-        a.depth[v] = on ? depth[v] : nullptr;
-        a.color[v] = on && color ? color[v] : nullptr;
-        a.h[v] = on ? hw[2 * v] : 1;
-        a.w[v] = on ? hw[2 * v + 1] : 1;
-        if (!on) continue;
-        PSCV_CHECK_ARG(depth[v] && (!color || color[v]), "%s: view %d has a null pointer", what, v);
-        PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31), "%s: view %d has bad size %dx%d", what, v, a.h[v],
-                       a.w[v]);
-    }
-    a.cams = cams;
-    a.dmax = dmax;
-    a.o0 = o0, a.o1 = o1, a.o2 = o2, a.s = voxel, a.trunc = trunc;
-    a.nx = nx, a.ny = ny, a.nz = nz, a.n_views = n_views;
-    a.tsdf_sum = nullptr, a.weight = nullptr, a.rgb_sum = nullptr, a.cweight = nullptr;
-    return 0;
-}
-
 }  // namespace pscv
 
 extern "C" int pscv_tsdf_brick_probe(const float* const* depth, const int* hw, int n_views, const float* cams, const float* dmax,
@@ -320,7 +286,7 @@ extern "C" int pscv_tsdf_brick_probe(const float* const* depth, const int* hw, i
     PSCV_CHECK_ARG(depth && hw && cams && dmax && dmin && masks, "%s: null pointer argument", what);
     TsdfBrickArgs a;
     if (check_lattice(what, nx, ny, nz, a.nbx, a.nby, a.nbz)) return -1;
-    if (fill_views(what, a.v, depth, nullptr, hw, n_views, cams, dmax, o0, o1, o2, voxel, trunc, nx, ny, nz)) return -1;
+    if (tsdf_setup(what, a.v, depth, nullptr, hw, n_views, cams, dmax, o0, o1, o2, voxel, trunc, nx, ny, nz, false)) return -1;
     a.dmin = dmin, a.masks = masks, a.brick_ids = nullptr;
     const long bricks = (long)a.nbx * a.nby * a.nbz, gx = bricks < TP_GRID_X ? bricks : TP_GRID_X;
     return launch(what, tsdf_brick_probe_kernel, dim3((unsigned)gx, (unsigned)((bricks + gx - 1) / gx)), dim3(TP_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
@@ -336,7 +302,7 @@ extern "C" int pscv_tsdf_brick_integrate(const float* const* depth, const unsign
     TsdfBrickArgs a;
     if (check_lattice(what, nx, ny, nz, a.nbx, a.nby, a.nbz)) return -1;
     if (check_pool(what, n_bricks)) return -1;
-    if (fill_views(what, a.v, depth, color, hw, n_views, cams, dmax, o0, o1, o2, voxel, trunc, nx, ny, nz)) return -1;
+    if (tsdf_setup(what, a.v, depth, color, hw, n_views, cams, dmax, o0, o1, o2, voxel, trunc, nx, ny, nz, false)) return -1;
     if (n_bricks == 0) return 0;
     PSCV_CHECK_ARG(brick_ids && tsdf_sum && weight && rgb_sum && cweight, "%s: null pointer argument", what);
     a.v.tsdf_sum = tsdf_sum, a.v.weight = weight, a.v.rgb_sum = rgb_sum, a.v.cweight = cweight;

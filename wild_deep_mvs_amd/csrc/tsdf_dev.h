@@ -4,6 +4,8 @@
 #pragma once
 #include "geo_common.h"
 
+#include <float.h>
+
 namespace pscv {
 
 // ---- integration -------------------------------------------------------------------------------------------------------------
@@ -310,6 +312,38 @@ __device__ __forceinline__ void tsdf_write_faces(const int (&q)[4], const Key (&
         }
         ++out;
     }
+}
+
+// ---- host side: the checks and the argument block of a call, once for the two layouts ---------------------------------------------
+inline int check_grid(const char* what, double o0, double o1, double o2, double voxel) {
+    PSCV_CHECK_ARG(fabs(o0) <= DBL_MAX && fabs(o1) <= DBL_MAX && fabs(o2) <= DBL_MAX, "%s: origin (%g, %g, %g) must be finite", what, o0,
+                   o1, o2);
+    PSCV_CHECK_ARG(voxel > 0.0 && voxel <= DBL_MAX, "%s: voxel=%g must be positive and finite", what, voxel);
+    return 0;
+}
+
+// the dense grid: a linear voxel index fits int32
+inline int check_dims(const char* what, int nx, int ny, int nz) {
+    PSCV_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && (long)nx * ny < (1L << 31) && (long)nx * ny * nz < (1L << 31),
+                   "%s: dims %dx%dx%d must be positive with nx ny nz < 2^31", what, nx, ny, nz);
+    return 0;
+}
+
+// The views and the lattice of an integration or probe call (color null: the probe reads no colour); the state pointers are left
+// null for the caller.  `dense` adds check_dims; a brick lattice is checked by its caller, which also derives the brick counts.
+inline int tsdf_setup(const char* what, TsdfArgs& a, const float* const* depth, const unsigned int* const* color, const int* hw,
+                      int n_views, const float* cams, const float* dmax, double o0, double o1, double o2, double voxel, double trunc,
+                      int nx, int ny, int nz, bool dense) {
+    if (check_view_count(what, n_views, 1) || check_grid(what, o0, o1, o2, voxel)) return -1;
+    PSCV_CHECK_ARG(trunc > 0.0 && trunc <= DBL_MAX, "%s: trunc=%g must be positive and finite", what, trunc);
+    if (dense && check_dims(what, nx, ny, nz)) return -1;
+    if (fill_views(a, what, depth, hw, n_views) || fill_view_ptrs(a.color, what, color, n_views)) return -1;
+    a.cams = cams;
+    a.dmax = dmax;
+    a.o0 = o0, a.o1 = o1, a.o2 = o2, a.s = voxel, a.trunc = trunc;
+    a.nx = nx, a.ny = ny, a.nz = nz, a.n_views = n_views;
+    a.tsdf_sum = nullptr, a.weight = nullptr, a.rgb_sum = nullptr, a.cweight = nullptr;
+    return 0;
 }
 
 }  // namespace pscv

@@ -24,8 +24,6 @@
 // counts into inclusive prefix sums, and pscv_tsdf_emit_vertices / pscv_tsdf_emit_faces write the mesh in its defined order.
 #include "tsdf_dev.h"
 
-#include <float.h>
-
 namespace pscv {
 
 // ---- integration (the rule itself: tsdf_dev.h) -----------------------------------------------------------------------------------
@@ -160,12 +158,6 @@ __global__ __launch_bounds__(256) void tsdf_emit_faces_kernel(const int* __restr
     }
 }
 
-static int check_dims(const char* what, int nx, int ny, int nz) {
-    PSCV_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && (long)nx * ny < (1L << 31) && (long)nx * ny * nz < (1L << 31),
-                   "%s: dims %dx%dx%d must be positive with nx ny nz < 2^31", what, nx, ny, nz);
-    return 0;
-}
-
 }  // namespace pscv
 
 extern "C" int pscv_tsdf_integrate(const float* const* depth, const unsigned int* const* color, const int* hw, int n_views,
@@ -174,28 +166,8 @@ extern "C" int pscv_tsdf_integrate(const float* const* depth, const unsigned int
     using namespace pscv;
     const char* what = "pscv_tsdf_integrate";
     PSCV_CHECK_ARG(depth && color && hw && cams && dmax && tsdf_sum && weight && rgb_sum && cweight, "%s: null pointer argument", what);
-    PSCV_CHECK_ARG(n_views >= 1 && n_views <= PSCV_FUSE_MAX_VIEWS, "%s: n_views=%d outside [1,%d]", what, n_views, PSCV_FUSE_MAX_VIEWS);
-    PSCV_CHECK_ARG(fabs(o0) <= DBL_MAX && fabs(o1) <= DBL_MAX && fabs(o2) <= DBL_MAX, "%s: origin (%g, %g, %g) must be finite", what, o0,
-                   o1, o2);
-    PSCV_CHECK_ARG(voxel > 0.0 && voxel <= DBL_MAX, "%s: voxel=%g must be positive and finite", what, voxel);
-    PSCV_CHECK_ARG(trunc > 0.0 && trunc <= DBL_MAX, "%s: trunc=%g must be positive and finite", what, trunc);
-    if (check_dims(what, nx, ny, nz)) return -1;
     TsdfArgs a;
-    for (int v = 0; v < PSCV_FUSE_MAX_VIEWS; ++v) {
-        const bool on = v < n_views;
-        a.depth[v] = on ? depth[v] : nullptr;
-        a.color[v] = on ? color[v] : nullptr;
-        a.h[v] = on ? hw[2 * v] : 1;
-        a.w[v] = on ? hw[2 * v + 1] : 1;
-        if (!on) continue;
-        PSCV_CHECK_ARG(depth[v] && color[v], "%s: view %d has a null pointer", what, v);
-        PSCV_CHECK_ARG(a.h[v] > 0 && a.w[v] > 0 && (long)a.h[v] * a.w[v] < (1L << 31), "%s: view %d has bad size %dx%d", what, v, a.h[v],
-                       a.w[v]);
-    }
-    a.cams = cams;
-    a.dmax = dmax;
-    a.o0 = o0, a.o1 = o1, a.o2 = o2, a.s = voxel, a.trunc = trunc;
-    a.nx = nx, a.ny = ny, a.nz = nz, a.n_views = n_views;
+    if (tsdf_setup(what, a, depth, color, hw, n_views, cams, dmax, o0, o1, o2, voxel, trunc, nx, ny, nz, true)) return -1;
     a.tsdf_sum = tsdf_sum, a.weight = weight, a.rgb_sum = rgb_sum, a.cweight = cweight;
     const long tiles = (long)((nx + TI_TX - 1) / TI_TX) * ((ny + TI_TY - 1) / TI_TY) * nz;
     return launch(what, tsdf_integrate_kernel, dim3((unsigned)tiles), dim3(TI_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
@@ -218,10 +190,7 @@ extern "C" int pscv_tsdf_emit_vertices(const float* tsdf_sum, const int* weight,
     using namespace pscv;
     const char* what = "pscv_tsdf_emit_vertices";
     PSCV_CHECK_ARG(n_vertices >= 0 && n_vertices < (1L << 31), "%s: n_vertices=%ld outside [0, 2^31)", what, n_vertices);
-    PSCV_CHECK_ARG(fabs(o0) <= DBL_MAX && fabs(o1) <= DBL_MAX && fabs(o2) <= DBL_MAX, "%s: origin (%g, %g, %g) must be finite", what, o0,
-                   o1, o2);
-    PSCV_CHECK_ARG(voxel > 0.0 && voxel <= DBL_MAX, "%s: voxel=%g must be positive and finite", what, voxel);
-    if (check_dims(what, nx, ny, nz)) return -1;
+    if (check_grid(what, o0, o1, o2, voxel) || check_dims(what, nx, ny, nz)) return -1;
     if (n_vertices == 0) return 0;
     PSCV_CHECK_ARG(tsdf_sum && weight && rgb_sum && cweight && info && vincl && xyz && rgb, "%s: null pointer argument", what);
     const long nvox = (long)nx * ny * nz;

@@ -134,13 +134,17 @@ extern "C" int pscv_view_covisibility(const float* const* depth, const int* hw, 
                    (double)max_depth_error);
     PSCV_CHECK_ARG(workspace_bytes >= pscv_view_covisibility_workspace(n_views), "%s: workspace of %ld bytes < %ld", what,
                    workspace_bytes, pscv_view_covisibility_workspace(n_views));
+    // The views go through a VcRows PSCV_FUSE_MAX_VIEWS at a time, twice: the first pass checks them and sizes the grid, so that
+    // nothing is launched for a bad view; the second uploads the table.
+    VcRows r;
     long max_samples = 0;
-    for (int v = 0; v < n_views; ++v) {
-        const int h = hw[2 * v], w = hw[2 * v + 1];
-        PSCV_CHECK_ARG(depth[v], "%s: view %d has a null pointer", what, v);
-        PSCV_CHECK_ARG(h > 0 && w > 0 && (long)h * w < (1L << 31), "%s: view %d has bad size %dx%d", what, v, h, w);
-        const long ns = (long)((h + stride - 1) / stride) * ((w + stride - 1) / stride);
-        if (ns > max_samples) max_samples = ns;
+    for (int first = 0; first < n_views; first += PSCV_FUSE_MAX_VIEWS) {
+        const int n = n_views - first < PSCV_FUSE_MAX_VIEWS ? n_views - first : PSCV_FUSE_MAX_VIEWS;
+        if (fill_views(r, what, depth, hw, n, first)) return -1;
+        for (int k = 0; k < n; ++k) {
+            const long ns = (long)((r.h[k] + stride - 1) / stride) * ((r.w[k] + stride - 1) / stride);
+            if (ns > max_samples) max_samples = ns;
+        }
     }
     const long tiles = (max_samples + VC_THREADS - 1) / VC_THREADS;
     PSCV_CHECK_ARG(tiles <= VC_MAX_TILES, "%s: %ld samples in one view: more than %d tiles of %d (raise the stride)", what,
@@ -149,22 +153,14 @@ extern "C" int pscv_view_covisibility(const float* const* depth, const int* hw, 
     VcView* table = static_cast<VcView*>(workspace);
     for (int first = 0; first < n_views; first += PSCV_FUSE_MAX_VIEWS) {
         const int n = n_views - first < PSCV_FUSE_MAX_VIEWS ? n_views - first : PSCV_FUSE_MAX_VIEWS;
-        VcRows r;
-        for (int k = 0; k < PSCV_FUSE_MAX_VIEWS; ++k) {
-            const bool on = k < n;
-            r.depth[k] = on ? depth[first + k] : nullptr;
-            r.h[k] = on ? hw[2 * (first + k)] : 1;
-            r.w[k] = on ? hw[2 * (first + k) + 1] : 1;
-        }
-        hipLaunchKernelGGL(covis_table_kernel, dim3(1), dim3(PSCV_FUSE_MAX_VIEWS), 0, st, r, table, first, n);
-        PSCV_CHECK_LAUNCH(what);
+        if (fill_views(r, what, depth, hw, n, first)) return -1;
+        const int rc = launch(what, covis_table_kernel, dim3(1), dim3(PSCV_FUSE_MAX_VIEWS), 0, st, r, table, first, n);
+        if (rc) return rc;
     }
     const long ncount = (long)n_views * n_views * 2;
     const long zb = (ncount + VC_THREADS - 1) / VC_THREADS;
-    hipLaunchKernelGGL(covis_zero_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(VC_THREADS), 0, st, counts, ncount);
-    PSCV_CHECK_LAUNCH(what);
-    hipLaunchKernelGGL(view_covis_kernel, dim3((unsigned)n_views, (unsigned)tiles), dim3(VC_THREADS), 0, st, table, cams, counts,
-                       n_views, stride, (double)max_depth_error);
-    PSCV_CHECK_LAUNCH(what);
-    return 0;
+    const int rc = launch(what, covis_zero_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(VC_THREADS), 0, st, counts, ncount);
+    if (rc) return rc;
+    return launch(what, view_covis_kernel, dim3((unsigned)n_views, (unsigned)tiles), dim3(VC_THREADS), 0, st, table, cams, counts, n_views,
+                  stride, (double)max_depth_error);
 }

@@ -439,6 +439,16 @@ def geo_filter_cams(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor) -> torch.
     return blocks.contiguous()
 
 
+def _ptrs(tensors):
+    """c_void_p array of the addresses of a list of tensors (a per-view pointer table of the C ABI)."""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _hw(maps):
+    """c_int array of the (h, w) pairs of a list of [h,w] maps."""
+    return (C.c_int * (2 * len(maps)))(*[v for m in maps for v in m.shape])
+
+
 def _maps(maps, what):
     """fp32 [h,w] device maps -> (the list, c_void_p array of their addresses, c_int array of their (h, w) pairs)."""
     maps = list(maps)
@@ -446,7 +456,7 @@ def _maps(maps, what):
     for m in maps:
         if m.dtype != torch.float32 or m.dim() != 2:
             raise ValueError(f"{what}: fp32 [h,w] maps expected, got {m.dtype} {tuple(m.shape)}")
-    return maps, (C.c_void_p * len(maps))(*[m.data_ptr() for m in maps]), (C.c_int * (2 * len(maps)))(*[v for m in maps for v in m.shape])
+    return maps, _ptrs(maps), _hw(maps)
 
 
 def _check_cams(cams, rows, what):
@@ -456,20 +466,70 @@ def _check_cams(cams, rows, what):
                          f"got {cams.dtype} {tuple(cams.shape)}")
 
 
+def _view_maps(what, depths, cams, *, lo, hi=None, cast):
+    """Checked (depths, cams): ``cast`` makes them fp32 (geo_filter, fuse_depth_*, colmap_fuse*, view_covisibility, depth_normals), else
+    only fp32 passes (the three tsdf_* operators).  The device is not looked at (``_one_device``)."""
+    depths = list(depths)
+    n = len(depths)
+    if n < lo or (hi is not None and n > hi):
+        raise ValueError(f"{what}: {f'{lo}..{hi} depth maps' if hi else 'at least one depth map'} expected, got {n}")
+    if not torch.is_tensor(cams):
+        raise ValueError(f"{what}: cams must be a tensor [V,{L.GEO_CAM_FLOATS}]")
+    if cast:
+        cams = cams.to(torch.float32)
+    for v, d in enumerate(depths):
+        if not (isinstance(d, torch.Tensor) and d.dim() == 2 and (cast or d.dtype == torch.float32)):
+            raise ValueError(f"{what}: depth map {v} must be fp32 [h,w], got {getattr(d, 'dtype', type(d))} {tuple(getattr(d, 'shape', ()))}")
+        depths[v] = (d if d.dtype == torch.float32 else d.to(torch.float32)).contiguous()
+    _check_cams(cams, n or None, what)
+    return depths, cams.contiguous()
+
+
+def _view_colors(what, depths, colors):
+    """One colour image per depth map, uint8 [h,w,3] or packed int32 [h,w] (``pack_rgba8``) -> the packed list."""
+    colors = list(colors)
+    if len(colors) != len(depths):
+        raise ValueError(f"{what}: {len(depths)} depth maps and as many colour images expected, got {len(colors)}")
+    packed = []
+    for v, (d, c) in enumerate(zip(depths, colors)):
+        if torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
+            packed.append(c.contiguous())
+        elif torch.is_tensor(c) and c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
+            packed.append(pack_rgba8(c))
+        else:
+            raise ValueError(f"{what}: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
+    return packed
+
+
+def _one_device(what, names, *tensors):
+    """Every tensor on the GPU, contiguous, and on the same one -> that device.  ``names`` says what they are in the message."""
+    _dev(*tensors)
+    dev = tensors[0].device
+    if any(t.device != dev for t in tensors):
+        raise ValueError(f"{what}: {names} must be on the same device")
+    return dev
+
+
+def _view_chunks(depths, cams):
+    """The views in launches of at most FUSE_MAX_VIEWS: (slice, view count, depth pointers, (h, w) pairs, camera rows) of each."""
+    for first in range(0, len(depths), L.FUSE_MAX_VIEWS):
+        part = slice(first, min(first + L.FUSE_MAX_VIEWS, len(depths)))
+        yield part, part.stop - first, _ptrs(depths[part]), _hw(depths[part]), cams[part]
+
+
 def geo_filter(depth: torch.Tensor, src_depth: Sequence[torch.Tensor], cams: torch.Tensor, *, max_reproj_error: float = 1.0,
                depth_threshold: float = 0.01, min_tri_angle: float = 1.0, num_consistent: int = 3,
                want_counts: bool = False):
     """depth [h,w] fp32, src_depth N x [h_i,w_i] fp32, cams [N+1,30] (``geo_filter_cams``), all on the GPU ->
     (mask_depth, mask_disp, geo_mask) bool [h,w] (and int32 counts [3,h,w] with ``want_counts``): the masks of
     evaluation/filtering.py:73-83 in one launch (pscv_geo_filter)."""
-    depth = depth.to(torch.float32).contiguous()
-    cams = cams.to(torch.float32).contiguous()
-    _dev(depth, cams)
-    src_depth, ptrs, hw = _maps([s.to(torch.float32).contiguous() for s in src_depth], "pscv.geo_filter")
+    src_depth = list(src_depth)
     n = len(src_depth)
-    if n < 1 or n > L.GEO_MAX_SRC or depth.dim() != 2:
+    if n < 1 or n > L.GEO_MAX_SRC:
         raise ValueError(f"pscv.geo_filter: depth [h,w] and 1..{L.GEO_MAX_SRC} source maps expected")
-    _check_cams(cams, n + 1, "pscv.geo_filter")
+    (depth, *src_depth), cams = _view_maps("pscv.geo_filter", [depth] + src_depth, cams, lo=0, cast=True)
+    _one_device("pscv.geo_filter", "depth maps and cams", cams, depth, *src_depth)
+    ptrs, hw = _ptrs(src_depth), _hw(src_depth)
     h, w = depth.shape
     masks = torch.empty((3, h, w), dtype=torch.uint8, device=depth.device)
     counts = torch.empty((3, h, w), dtype=torch.int32, device=depth.device) if want_counts else None
@@ -493,27 +553,13 @@ def pack_rgba8(colors: torch.Tensor) -> torch.Tensor:
 
 
 def _fuse_inputs(depths, colors, cams):
-    depths = [d.to(torch.float32).contiguous() for d in depths]
-    n = len(depths)
-    if n < 2 or n > L.FUSE_MAX_VIEWS or len(colors) != n:
-        raise ValueError(f"pscv.fuse_depth: 2..{L.FUSE_MAX_VIEWS} depth maps and as many colour images expected, got {n} and {len(colors)}")
-    cams = cams.to(torch.float32).contiguous()
-    _dev(cams)
-    depths, dptr, hw = _maps(depths, "pscv.fuse_depth")
-    _check_cams(cams, n, "pscv.fuse_depth")
-    packed = []
-    for v, (d, c) in enumerate(zip(depths, colors)):
-        _dev(c)
-        if c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
-            packed.append(c.contiguous())
-        elif c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
-            packed.append(pack_rgba8(c))
-        else:
-            raise ValueError(f"pscv.fuse_depth: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
+    what = "pscv.fuse_depth"
+    depths, cams = _view_maps(what, depths, cams, lo=2, hi=L.FUSE_MAX_VIEWS, cast=True)
+    packed = _view_colors(what, depths, colors)
+    dev = _one_device(what, "depth maps, colours and cams", cams, *depths, *packed)
     ws_bytes = max(int(L.lib().pscv_fuse_depth_workspace(int(d.shape[0]), int(d.shape[1]))) for d in depths)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=depths[0].device)
-    ptrs = (dptr, (C.c_void_p * n)(*[c.data_ptr() for c in packed]), hw)
-    return depths, packed, cams, ptrs, ws
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    return depths, packed, cams, (_ptrs(depths), _ptrs(packed), _hw(depths)), ws
 
 
 def _check_used(used, depths):
@@ -523,10 +569,6 @@ def _check_used(used, depths):
         _dev(u)
         if u.dtype != torch.uint8 or tuple(u.shape) != tuple(d.shape):
             raise ValueError(f"pscv.fuse_depth: used mask {v} must be uint8 [h,w] at the depth map's size")
-
-
-def _used_ptrs(used):
-    return (C.c_void_p * len(used))(*[u.data_ptr() for u in used])
 
 
 def _fuse_pass(i, depths, ptrs, uptr, cams, ws, params, out, counter):
@@ -572,7 +614,7 @@ def fuse_depth_pass(i: int, depths: Sequence[torch.Tensor], colors: Sequence[tor
     cap = int(depths[i].numel()) if capacity is None else int(capacity)
     out = _fuse_out(cap, cams.device, want_view=False)
     counter = torch.zeros(1, dtype=torch.int64, device=cams.device)
-    _fuse_pass(i, depths, ptrs, _used_ptrs(used), cams, ws, (disp_thresh, num_consistent, depth_min, depth_max), out, counter)
+    _fuse_pass(i, depths, ptrs, _ptrs(used), cams, ws, (disp_thresh, num_consistent, depth_min, depth_max), out, counter)
     m = _fuse_total(counter, cap, "pscv.fuse_depth_pass")
     return out[0][:m], out[1][:m], out[3][:m]
 
@@ -590,7 +632,7 @@ def fuse_depth_maps(depths: Sequence[torch.Tensor], colors: Sequence[torch.Tenso
     depths, packed, cams, ptrs, ws = _fuse_inputs(depths, colors, cams)
     dev = cams.device
     used = [torch.zeros(d.shape, dtype=torch.uint8, device=dev) for d in depths]
-    uptr = _used_ptrs(used)
+    uptr = _ptrs(used)
     cap = sum(int(d.numel()) for d in depths) if capacity is None else int(capacity)
     out = _fuse_out(cap, dev)
     counter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -694,7 +736,7 @@ class _ColmapRun:
         n = len(self.depths)
         _colmap_check(n, *params)
         self.normals, self.max_normal_error = _colmap_normals(normals, max_normal_error, self.depths, "pscv.colmap_fuse")
-        self.nptr = None if self.normals is None else _used_ptrs(self.normals)
+        self.nptr = None if self.normals is None else _ptrs(self.normals)
         self.params = params
         self.overlap = colmap_overlap_lists(overlap, n)
         self.bits = (C.c_long * n)(*[C.c_long(sum(1 << m for m in row)).value for row in self.overlap])
@@ -704,9 +746,9 @@ class _ColmapRun:
             fused = [torch.zeros(d.shape, dtype=torch.uint8, device=dev) for d in self.depths]
         _check_used(fused, self.depths)
         self.fused = fused
-        self.fptr = _used_ptrs(fused)
+        self.fptr = _ptrs(fused)
         self.claim = [torch.full(d.shape, -1, dtype=torch.int64, device=dev) for d in self.depths]
-        self.clptr = _used_ptrs(self.claim)
+        self.clptr = _ptrs(self.claim)
         ws_bytes = max(int(L.lib().pscv_colmap_fuse_workspace(int(d.shape[0]), int(d.shape[1]))) for d in self.depths)
         self.ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         self.cap = sum(int(d.numel()) for d in self.depths) if capacity is None else int(capacity)
@@ -806,14 +848,10 @@ def view_covisibility(depths: Sequence[torch.Tensor], cams: torch.Tensor, *, str
     ``max_depth_error`` (relative); pixel, rounding and depth test are those of phase A of ``colmap_fuse``.  The diagonal is 0.  One
     pscv_view_covisibility call on the current stream, no host synchronisation; ``utils.colmap_model.overlap_from_covisibility``
     turns the counts into the overlap lists of ``colmap_fuse``."""
-    cams = cams.to(torch.float32).contiguous()
-    _dev(cams)
-    depths, dptr, hw = _maps([d.to(torch.float32).contiguous() for d in depths], "pscv.view_covisibility")
-    n = len(depths)
-    _check_cams(cams, n if n else None, "pscv.view_covisibility")
-    dev = cams.device
-    if any(d.device != dev for d in depths):
-        raise ValueError("pscv.view_covisibility: depth maps and cams must be on the same device")
+    what = "pscv.view_covisibility"
+    depths, cams = _view_maps(what, depths, cams, lo=0, cast=True)         # (the C entry point refuses V < 2)
+    dev = _one_device(what, "depth maps and cams", cams, *depths)
+    n, dptr, hw = len(depths), _ptrs(depths), _hw(depths)
     counts = torch.empty((n, n, 2), dtype=torch.int32, device=dev)
     ws = torch.empty(max(int(L.lib().pscv_view_covisibility_workspace(n)), 1), dtype=torch.uint8, device=dev)
     samples = sum(-(-d.shape[0] // max(int(stride), 1)) * -(-d.shape[1] // max(int(stride), 1)) for d in depths)
@@ -851,24 +889,15 @@ def depth_normals(depths: Sequence[torch.Tensor], cams: torch.Tensor, *, radius:
     window = (2 * r + 1) ** 2
     if not 3 <= int(min_support) <= window:
         raise ValueError(f"{what}: min_support must lie in [3, {window}] (the window of radius {r}), got {min_support}")
-    cams = cams.to(torch.float32).contiguous()
-    _dev(cams)
-    depths, _, _ = _maps([d.to(torch.float32).contiguous() for d in depths], what)
-    n = len(depths)
-    _check_cams(cams, n if n else None, what)
-    dev = cams.device
-    if any(d.device != dev for d in depths):
-        raise ValueError(f"{what}: depth maps and cams must be on the same device")
+    depths, cams = _view_maps(what, depths, cams, lo=0, cast=True)
+    dev = _one_device(what, "depth maps and cams", cams, *depths)
     normals = [torch.empty(tuple(d.shape) + (3,), dtype=torch.float32, device=dev) for d in depths]
     supports = [torch.empty(d.shape, dtype=torch.int32, device=dev) for d in depths] if want_support else None
-    for first in range(0, n, L.FUSE_MAX_VIEWS):
-        part = slice(first, min(first + L.FUSE_MAX_VIEWS, n))
-        _, dptr, hw = _maps(depths[part], what)
-        k = part.stop - first
+    for part, k, dptr, hw, cam_part in _view_chunks(depths, cams):
         pixels = sum(int(d.numel()) for d in depths[part])
         rc = _launch("depth_normals", lambda: L.lib().pscv_depth_normals(
-            dptr, hw, k, _p(cams[first:]), r, tau, int(min_support), _used_ptrs(normals[part]),
-            None if supports is None else _used_ptrs(supports[part]), _stream()),
+            dptr, hw, k, _p(cam_part), r, tau, int(min_support), _ptrs(normals[part]),
+            None if supports is None else _ptrs(supports[part]), _stream()),
             # per pixel: 4 B read, 12 (+ 4) B written; per tap ~12 fp64 operations
             cost=lambda: (float(pixels * (20 if want_support else 16)), 12.0 * window * pixels))
         L.check(rc, "pscv_depth_normals")
@@ -897,16 +926,13 @@ def point_world_normals(view: torch.Tensor, pixel: torch.Tensor, normals: Sequen
         raise ValueError(f"{what}: view and pixel must have one entry per point, got {tuple(view.shape)} and {tuple(pixel.shape)}")
     cams = cams.to(torch.float32).contiguous()
     view, pixel = view.contiguous(), pixel.contiguous()
-    _dev(cams, view, pixel, *normals)
     _check_cams(cams, n, what)
-    dev = cams.device
-    if any(t.device != dev for t in [view, pixel] + normals):
-        raise ValueError(f"{what}: indices, normal maps and cams must be on the same device")
+    dev = _one_device(what, "indices, normal maps and cams", cams, view, pixel, *normals)
     m = int(view.shape[0])
     out = torch.empty((m, 3), dtype=torch.float32, device=dev)
     hw = (C.c_int * (2 * n))(*[s for nm in normals for s in nm.shape[:2]])
     rc = _launch("point_world_normals", lambda: L.lib().pscv_point_world_normals(
-        _p(view), _p(pixel), m, _used_ptrs(normals), hw, n, _p(cams), _p(out), _stream()),
+        _p(view), _p(pixel), m, _ptrs(normals), hw, n, _p(cams), _p(out), _stream()),
         cost=lambda: (float(m * (8 + 12 + 12)), 15.0 * m))
     L.check(rc, "pscv_point_world_normals")
     return out
@@ -957,6 +983,19 @@ def _tsdf_grid(origin, voxel, what):
     return o, s
 
 
+def _trunc(trunc, what):
+    tr = float(trunc)
+    if not (tr > 0.0 and math.isfinite(tr)):
+        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
+    return tr
+
+
+def _tsdf_room(volume, n, what):
+    if volume.views + n > TSDF_MAX_VIEWS:
+        raise ValueError(f"{what}: {volume.views} + {n} views exceed the {TSDF_MAX_VIEWS} a volume can hold (its fp32 colour sums stay "
+                         f"exact only while 255 cweight < 2^24)")
+
+
 def _tsdf_state(state, what):
     if not isinstance(state, TsdfVolume):
         raise ValueError(f"{what}: state must be the TsdfVolume of ops.tsdf_volume, got {type(state).__name__}")
@@ -996,46 +1035,15 @@ def tsdf_integrate(state: TsdfVolume, depths: Sequence[torch.Tensor], colors: Se
     what = "pscv.tsdf_integrate"
     nx, ny, nz = _tsdf_state(state, what)
     o, s = _tsdf_grid(origin, voxel, what)
-    tr = float(trunc)
-    if not (tr > 0.0 and math.isfinite(tr)):
-        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
-    depths, colors = list(depths), list(colors)
-    n = len(depths)
-    if n < 1 or len(colors) != n:
-        raise ValueError(f"{what}: at least one depth map and as many colour images expected, got {n} and {len(colors)}")
-    if state.views + n > TSDF_MAX_VIEWS:
-        raise ValueError(f"{what}: {state.views} + {n} views exceed the {TSDF_MAX_VIEWS} a volume can hold (its fp32 colour sums stay "
-                         f"exact only while 255 cweight < 2^24)")
-    if not torch.is_tensor(cams):
-        raise ValueError(f"{what}: cams must be a tensor [V,{L.GEO_CAM_FLOATS}]")
-    _check_cams(cams, n, what)
-    packed = []
-    for v, (d, c) in enumerate(zip(depths, colors)):
-        if not torch.is_tensor(d) or d.dtype != torch.float32 or d.dim() != 2:
-            raise ValueError(f"{what}: depth map {v} must be fp32 [h,w], got {getattr(d, 'dtype', type(d))} {tuple(getattr(d, 'shape', ()))}")
-        if torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
-            packed.append(c)
-        elif torch.is_tensor(c) and c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
-            packed.append(None)
-        else:
-            raise ValueError(f"{what}: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
-    cams = cams.contiguous()
-    depths = [d.contiguous() for d in depths]
-    _dev(cams, *depths, *state.arrays())
-    dev = state.tsdf_sum.device
-    for c in colors:
-        _dev(c.contiguous())
-    if any(t.device != dev for t in [cams] + depths + colors + list(state.arrays())):
-        raise ValueError(f"{what}: state, depth maps, colours and cams must be on the same device")
-    packed = [pack_rgba8(c) if p is None else p.contiguous() for c, p in zip(colors, packed)]
-    for first in range(0, n, L.FUSE_MAX_VIEWS):
-        part = slice(first, min(first + L.FUSE_MAX_VIEWS, n))
-        _, dptr, hw = _maps(depths[part], what)
-        k = part.stop - first
+    tr = _trunc(trunc, what)
+    depths, cams = _view_maps(what, depths, cams, lo=1, cast=False)
+    packed = _view_colors(what, depths, colors)
+    _tsdf_room(state, len(depths), what)
+    _one_device(what, "state, depth maps, colours and cams", *state.arrays(), cams, *depths, *packed)
+    for part, k, dptr, hw, cam_part in _view_chunks(depths, cams):
         dmax = _max_valid_depth(depths[part])
-        cam_part = cams[part]
         rc = _launch("tsdf_integrate", lambda: L.lib().pscv_tsdf_integrate(
-            dptr, _used_ptrs(packed[part]), hw, k, _p(cam_part), _p(dmax), o[0], o[1], o[2], s, tr, nx, ny, nz,
+            dptr, _ptrs(packed[part]), hw, k, _p(cam_part), _p(dmax), o[0], o[1], o[2], s, tr, nx, ny, nz,
             _p(state.tsdf_sum), _p(state.weight), _p(state.rgb_sum), _p(state.cweight), _stream()),
             # the state read and written once (2 x 24 B per voxel); per voxel and view ~60 fp64 operations and three divisions
             cost=lambda: (48.0 * nx * ny * nz, 100.0 * nx * ny * nz * k))
@@ -1126,27 +1134,6 @@ def _brick_dims(dims, what):
     return (nx, ny, nz), nb
 
 
-def _trunc(trunc, what):
-    tr = float(trunc)
-    if not (tr > 0.0 and math.isfinite(tr)):
-        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
-    return tr
-
-
-def _depth_maps(depths, cams, what):
-    depths = list(depths)
-    n = len(depths)
-    if n < 1:
-        raise ValueError(f"{what}: at least one depth map expected")
-    if not torch.is_tensor(cams):
-        raise ValueError(f"{what}: cams must be a tensor [V,{L.GEO_CAM_FLOATS}]")
-    _check_cams(cams, n, what)
-    for v, d in enumerate(depths):
-        if not torch.is_tensor(d) or d.dtype != torch.float32 or d.dim() != 2:
-            raise ValueError(f"{what}: depth map {v} must be fp32 [h,w], got {getattr(d, 'dtype', type(d))} {tuple(getattr(d, 'shape', ()))}")
-    return [d.contiguous() for d in depths], cams.contiguous()
-
-
 def _min_valid_depth(depths):
     """fp32 [V] on the device: the smallest valid (0 < d finite) depth of each map, +inf for a map without one (plumbing)."""
     def amin(d):
@@ -1166,18 +1153,12 @@ def tsdf_brick_probe(depths: Sequence[torch.Tensor], cams: torch.Tensor, dims, *
     (nx, ny, nz), nb = _brick_dims(dims, what)
     o, s = _tsdf_grid(origin, voxel, what)
     tr = _trunc(trunc, what)
-    depths, cams = _depth_maps(depths, cams, what)
-    _dev(cams, *depths)
-    dev = cams.device
-    if any(d.device != dev for d in depths):
-        raise ValueError(f"{what}: depth maps and cams must be on the same device")
+    depths, cams = _view_maps(what, depths, cams, lo=1, cast=False)
+    dev = _one_device(what, "depth maps and cams", cams, *depths)
     masks = torch.zeros(nb[::-1], dtype=torch.int32, device=dev)
     nbricks = nb[0] * nb[1] * nb[2]
-    for first in range(0, len(depths), L.FUSE_MAX_VIEWS):
-        part = slice(first, min(first + L.FUSE_MAX_VIEWS, len(depths)))
-        _, dptr, hw = _maps(depths[part], what)
-        k = part.stop - first
-        dmax, dmin, cam_part = _max_valid_depth(depths[part]), _min_valid_depth(depths[part]), cams[part]
+    for part, k, dptr, hw, cam_part in _view_chunks(depths, cams):
+        dmax, dmin = _max_valid_depth(depths[part]), _min_valid_depth(depths[part])
         rc = _launch("tsdf_brick_probe", lambda: L.lib().pscv_tsdf_brick_probe(
             dptr, hw, k, _p(cam_part), _p(dmax), _p(dmin), o[0], o[1], o[2], s, tr, nx, ny, nz, _p(masks), _stream()),
             cost=lambda: (8.0 * nbricks, 100.0 * nbricks * k))
@@ -1244,36 +1225,14 @@ def tsdf_brick_integrate(bricks: TsdfBricks, depths: Sequence[torch.Tensor], col
     (nx, ny, nz), nbr = _tsdf_brick_state(bricks, what)
     o, s = _tsdf_grid(origin, voxel, what)
     tr = _trunc(trunc, what)
-    depths, colors = list(depths), list(colors)
-    n = len(depths)
-    if n < 1 or len(colors) != n:
-        raise ValueError(f"{what}: at least one depth map and as many colour images expected, got {n} and {len(colors)}")
-    if bricks.views + n > TSDF_MAX_VIEWS:
-        raise ValueError(f"{what}: {bricks.views} + {n} views exceed the {TSDF_MAX_VIEWS} a volume can hold (its fp32 colour sums stay "
-                         f"exact only while 255 cweight < 2^24)")
-    depths, cams = _depth_maps(depths, cams, what)
-    packed = []
-    for v, (d, c) in enumerate(zip(depths, colors)):
-        if torch.is_tensor(c) and c.dtype == torch.int32 and tuple(c.shape) == tuple(d.shape):
-            packed.append(c)
-        elif torch.is_tensor(c) and c.dtype == torch.uint8 and tuple(c.shape) == tuple(d.shape) + (3,):
-            packed.append(None)
-        else:
-            raise ValueError(f"{what}: colours of view {v} must be uint8 [h,w,3] (or packed int32 [h,w]) at the depth map's size")
-    _dev(cams, *depths, *bricks.arrays(), bricks.brick_ids, bricks.directory)
-    dev = bricks.tsdf_sum.device
-    for c in colors:
-        _dev(c.contiguous())
-    if any(t.device != dev for t in [cams, bricks.brick_ids, bricks.directory] + depths + colors + list(bricks.arrays())):
-        raise ValueError(f"{what}: bricks, depth maps, colours and cams must be on the same device")
-    packed = [pack_rgba8(c) if p is None else p.contiguous() for c, p in zip(colors, packed)]
-    for first in range(0, n, L.FUSE_MAX_VIEWS):
-        part = slice(first, min(first + L.FUSE_MAX_VIEWS, n))
-        _, dptr, hw = _maps(depths[part], what)
-        k = part.stop - first
-        dmax, cam_part = _max_valid_depth(depths[part]), cams[part]
+    depths, cams = _view_maps(what, depths, cams, lo=1, cast=False)
+    packed = _view_colors(what, depths, colors)
+    _tsdf_room(bricks, len(depths), what)
+    _one_device(what, "bricks, depth maps, colours and cams", *bricks.arrays(), bricks.brick_ids, bricks.directory, cams, *depths, *packed)
+    for part, k, dptr, hw, cam_part in _view_chunks(depths, cams):
+        dmax = _max_valid_depth(depths[part])
         rc = _launch("tsdf_brick_integrate", lambda: L.lib().pscv_tsdf_brick_integrate(
-            dptr, _used_ptrs(packed[part]), hw, k, _p(cam_part), _p(dmax), o[0], o[1], o[2], s, tr, nx, ny, nz, _p(bricks.brick_ids), nbr,
+            dptr, _ptrs(packed[part]), hw, k, _p(cam_part), _p(dmax), o[0], o[1], o[2], s, tr, nx, ny, nz, _p(bricks.brick_ids), nbr,
             _p(bricks.tsdf_sum), _p(bricks.weight), _p(bricks.rgb_sum), _p(bricks.cweight), _stream()),
             cost=lambda: (48.0 * 512 * nbr, 100.0 * 512 * nbr * k))
         L.check(rc, "pscv_tsdf_brick_integrate")
