@@ -40,7 +40,7 @@ struct Conv2dArgs {
     int out_cs, out_co, skip_cs, skip_co;
     int oys, oxs, oyo, oxo, Hof, Wof;
     int nt_total;            // 16-channel output tiles of the layer (blockIdx.y picks this block's first NT tiles)
-    float neg_slope;         // activation y -> max(y, neg_slope * y): 0 = ReLU, 0.1 = LeakyReLU(0.1), 1 = none
+    float neg_slope;         // activation y -> max(y, neg_slope * y) (c2_act): 0 = ReLU, 0.1 = LeakyReLU(0.1), 1 = none
     int nth, ntw;
     unsigned mg_th, mg_tw;
 };
@@ -50,6 +50,14 @@ __host__ __device__ constexpr int c2_vs(int cin) { return cin == 32 ? 96 : cin *
 constexpr int C2_TW = 32;    // output columns per workgroup (two 16-pixel MFMA column tiles)
 
 __host__ __device__ constexpr int c2_pad(int ks) { return ks == 2 ? 0 : ks / 2; }   // the 2x2 parity sub-convs read (i, i+1)
+
+// Activation y = max(v, neg_slope * v) with torch's results for non-finite v.  fmaxf returns the non-NaN operand, so a NaN v stays NaN
+// only because v * neg_slope is NaN too -- and for v = -inf under ReLU (neg_slope = 0) the product -inf * 0 is NaN while v is not:
+// fmaxf gave -inf where torch.relu (and conv3d's relu_floor) give 0.  `lo` = c2_act_floor(neg_slope) lifts exactly that value: under
+// ReLU fmaxf(v, v * 0) is below 0 for v = -inf only (finite negatives give -0), NaN < lo is false, and lo = -inf never triggers for a
+// LeakyReLU or the identity, whose bits are unchanged (leaky(-inf) = -inf as in torch).
+__device__ __forceinline__ float c2_act_floor(float neg_slope) { return neg_slope == 0.0f ? 0.0f : -__builtin_inff(); }
+__device__ __forceinline__ float c2_act(float v, float neg_slope, float lo) { return relu_floor(fmaxf(v, v * neg_slope), lo); }
 
 template <typename H, int CIN, int NT, int KS, int STRIDE>
 __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
@@ -74,6 +82,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, g = lane >> 4;
     const int nt0 = blockIdx.y * NT;
+    const float act_lo = c2_act_floor(a.neg_slope);
 
     // A fragments: the first PF k-steps (all of them for the small layers) are requested before the brick so that both
     // share one memory latency; wide layers (64 channels: 72 fragments) continue through a ring, step s + PF being
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
                     v[0] += Half16<H>::lo(sv.x); v[1] += Half16<H>::hi(sv.x); v[2] += Half16<H>::lo(sv.y); v[3] += Half16<H>::hi(sv.y);
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) y[k] = fmaxf(v[k], v[k] * a.neg_slope);
+                for (int k = 0; k < 4; ++k) y[k] = c2_act(v[k], a.neg_slope, act_lo);
                 *reinterpret_cast<uint2*>(slot) = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
             }
             __builtin_amdgcn_wave_barrier();                 // (LDS executes a wave's operations in order)
@@ -255,7 +264,7 @@ __global__ __launch_bounds__(256) void conv2d_kernel(const Conv2dArgs a) {
                 v[0] += Half16<H>::lo(sv.x); v[1] += Half16<H>::hi(sv.x); v[2] += Half16<H>::lo(sv.y); v[3] += Half16<H>::hi(sv.y);
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = fmaxf(v[k], v[k] * a.neg_slope);
+            for (int k = 0; k < 4; ++k) y[k] = c2_act(v[k], a.neg_slope, act_lo);
             if (a.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + pix * a.out_cs + a.out_co + c0) = make_float4(y[0], y[1], y[2], y[3]);
             else *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + pix * a.out_cs + a.out_co + c0) =
                      make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
@@ -309,6 +318,7 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_wlds_kernel(const Conv2
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned char* const so = smem + W_BYTES + C2W_BRICK + wave * (32 * OPITCH);   // this wave's output row: 32 pixels
     const int n = lane & 15, g = lane >> 4;
+    const float act_lo = c2_act_floor(a.neg_slope);
 
     // weights -> LDS (once)
     for (int q = tid; q < C2W_STEPS * NT * 64; q += C2W_THREADS) {
@@ -446,7 +456,7 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_wlds_kernel(const Conv2
                             v[0] += Half16<H>::lo(sv.x); v[1] += Half16<H>::hi(sv.x); v[2] += Half16<H>::lo(sv.y); v[3] += Half16<H>::hi(sv.y);
                         }
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) y[k] = fmaxf(v[k], v[k] * a.neg_slope);
+                        for (int k = 0; k < 4; ++k) y[k] = c2_act(v[k], a.neg_slope, act_lo);
                         *reinterpret_cast<uint2*>(slot) = make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
                     }
                 __builtin_amdgcn_wave_barrier();          // (LDS executes a wave's operations in order: the reads below see the row)
@@ -481,7 +491,7 @@ __global__ __launch_bounds__(C2W_THREADS, 2) void conv2d_wlds_kernel(const Conv2
                         v[0] += Half16<H>::lo(sv.x); v[1] += Half16<H>::hi(sv.x); v[2] += Half16<H>::lo(sv.y); v[3] += Half16<H>::hi(sv.y);
                     }
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) y[k] = fmaxf(v[k], v[k] * a.neg_slope);
+                    for (int k = 0; k < 4; ++k) y[k] = c2_act(v[k], a.neg_slope, act_lo);
                     if (a.out_f32) *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + pix * a.out_cs + a.out_co + c0) = make_float4(y[0], y[1], y[2], y[3]);
                     else *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + pix * a.out_cs + a.out_co + c0) =
                              make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
