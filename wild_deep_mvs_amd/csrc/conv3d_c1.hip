@@ -158,7 +158,9 @@ __global__ __launch_bounds__(256) void conv3d_c1_kernel(const C1Args a) {
         const int d0 = dbeg + blk * C1_P;
         if (d0 >= a.D) break;
         const unsigned char* sp = smem + blk * (C1_P * C1_PS * VB) + lane_off;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        // C_in 8: the two plane sets (q = 0, 1) run as chains of their own and are added at the end -- the summation order of the
+        // depth-sweep variant below, so that the two variants of a layer store the same fp32 bits
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f}, acc0b = {0.f, 0.f, 0.f, 0.f}, acc1b = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s = 0; s < NSTEPS; ++s) {
             // step s = (q, tap): lane group g reads plane 4 (g >> 1) + 2 q + (g & 1) (C_in 8) or 4 (g >> 1) + q
@@ -167,8 +169,17 @@ __global__ __launch_bounds__(256) void conv3d_c1_kernel(const C1Args a) {
             const int off = (((CIN == 8) ? 2 * q : q) * C1_PS + (t / 3) * C1_BW + (t % 3)) * VB;
             const uint4 x0 = *reinterpret_cast<const uint4*>(sp + off);
             const uint4 x1 = *reinterpret_cast<const uint4*>(sp + off + 16 * VB);
-            acc0 = Mfma<H>::run(wf[s], x0, acc0);
-            acc1 = Mfma<H>::run(wf[s], x1, acc1);
+            if (CIN == 8 && q == 1) {
+                acc0b = Mfma<H>::run(wf[s], x0, acc0b);
+                acc1b = Mfma<H>::run(wf[s], x1, acc1b);
+            } else {
+                acc0 = Mfma<H>::run(wf[s], x0, acc0);
+                acc1 = Mfma<H>::run(wf[s], x1, acc1);
+            }
+        }
+        if (CIN == 8) {
+            acc0 += acc0b;
+            acc1 += acc1b;
         }
         PSCV_STAMP(3)
         // ---- epilogue: lane (n, g) holds rows 4g..4g+3 = output planes d0 + 4g + r of pixel n ----

@@ -178,7 +178,8 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
 
         // epilogue: the base of output plane o is scalar arithmetic; a lane adds its precomputed row / column / channel offset
         {
-            fp16_ovfl_mode(true);     // saturating 16-bit stores; off again before the next plane's MFMAs (pscv_common.h)
+            // (16-bit stores through Half16::pack: it saturates a true +-inf at +-65504 like every other conv kernel; the FP16_OVFL mode
+            //  this epilogue used to raise around its conversions clamps overflowing finite values only and stored inf as inf)
             const long obase = ((long)b * a.Do + o) * oplane + a.out_co, sbase = ((long)b * a.Do + o) * splane + a.skip_co;
 #pragma unroll
             for (int r = 0; r < S2S_R; ++r)
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) y[k] = relu_floor(y[k], lo_post);
                             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + obase + lane_out[r] + m * 16) =
-                                make_uint2(Half16<H>::pack_ovfl(y[0], y[1]), Half16<H>::pack_ovfl(y[2], y[3]));
+                                make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
                             continue;
                         }
                         uint2 sv = make_uint2(0u, 0u);
@@ -202,10 +203,9 @@ __global__ __launch_bounds__(256) void conv3d_sweep_s2_kernel(const S2sArgs a) {
                             *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.out) + obase + lane_out[r] + m * 16) = pack4_f32(y);
                         else
                             *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(a.out) + obase + lane_out[r] + m * 16) =
-                                make_uint2(Half16<H>::pack_ovfl(y[0], y[1]), Half16<H>::pack_ovfl(y[2], y[3]));
+                                make_uint2(Half16<H>::pack(y[0], y[1]), Half16<H>::pack(y[2], y[3]));
                     }
                 }
-            fp16_ovfl_mode(false);
         }
         PSCV_STAMP(3)
         ring += 2;
