@@ -6,6 +6,8 @@ import pytest
 from _util import retry_infra
 import torch
 
+import _photo_cmp as PC                      # compare() and the per-kernel bounds (units of 2^-24 U) of the float64 tests
+import _photo_ref as R
 from oracle import photometric as P
 from wild_deep_mvs_amd import synthetic
 from wild_deep_mvs_amd.models.trainer import Trainer
@@ -40,10 +42,33 @@ def test_photometricloss_matches_reference_golden(tag):
     rel = np.abs(depth.grad.cpu().numpy() - g["grad_depth"]).sum() / np.abs(g["grad_depth"]).sum()
     print(f"[parity] {tag}: ssim max abs {err.max():.2e}, mask pixels differing {moved:.2e}, loss {float(loss):.6f} vs "
           f"{float(g['loss']):.6f}, grad_depth rel-L1 {rel:.2e}", flush=True)
-    assert moved <= 1e-3                        # |g| < 1 is a threshold on an fp32 coordinate
-    assert np.quantile(err, 0.999) <= 1e-4 and abs(float(loss) - float(g["loss"])) <= 1e-5
-    assert rel <= 1e-4
+    # The golden is fp32: against float64 it is itself off by 3.2e-5 (ssim, cancellation in E[x^2] - mu^2), 5.6e-6 (grad rel-L1) and
+    # no mask pixel (tests/test_photo_ref_cpu.py prints the figures); the kernels add ~1e-6.  No quantile: every element.
+    assert moved <= 2e-4                        # |g| < 1 is a threshold on an fp32 coordinate
+    assert err.max() <= 5e-5 and abs(float(loss) - float(g["loss"])) <= 1e-5
+    assert rel <= 2e-5
     assert sorted(tr.ims) == [f"warped{i}" for i in range(1, sc["imgs"].shape[1])]
+    # and per element against the float64 composition of tests/_photo_ref.py, with the bounds of tests/test_gpu_photo_ref.py
+    from wild_deep_mvs_amd import ops
+    kb = PC.BOUND
+    inv_ref = ops.inv_proj4x4(proj[:, 0].float().cuda().contiguous()).cpu()
+    f = R.fragile(sc["depths"][0], inv_ref, proj[:, 1:].float())
+    assert max(float(v.double().mean()) for v in f.values()) <= R.FRAGILE_CAP
+    # q_z ~ 0 would put a whole SSIM window in doubt: the golden scenes have no such sample (asserted with a wide margin on the CPU,
+    # tests/test_photo_ref_cpu.py); a scene that grows one must fail here, not pass unchecked
+    assert not bool(f["fwd"].any())
+    ref_mask = R.photo_warp(None, sc["depths"][0], inv_ref, proj[:, 1:].float())["mask"]
+    got_mask = mask.double().cpu()
+    assert torch.equal(got_mask[~f["mask"]], ref_mask[~f["mask"]]) and bool(((got_mask == 0) | (got_mask == 1)).all())
+    # a doubtful |g| = 1 pixel may legitimately fall either way: the composition takes the kernel's decision THERE (it enters the loss
+    # through the mask's own pixel and the 1 / sum(mask) scale only) and the comparison below is made on every element, always
+    comp = R.photometricloss(sc["imgs"], sc["depths"][0], inv_ref, proj[:, 1:].float(), mask=torch.where(f["mask"], got_mask, ref_mask),
+                             up=(kb[("photo_warp", "warped")] / kb[("ssim", "out")], kb[("ssim_bwd", "grad")] / kb[("photo_warp_bwd", "grad_depth")]))
+    print(f"[parity] {tag}: {int(f['mask'].sum())} doubtful mask pixels, {int((got_mask != ref_mask).sum())} decided the other way", flush=True)
+    S, C = comp["ssim"].shape[1], sc["imgs"].shape[2]
+    PC.compare(("photometricloss", "ssim"), f"{tag} ssim vs float64", ssim, comp["ssim"], comp["Ussim"])
+    PC.compare(("photometricloss", "grad_depth"), f"{tag} grad_depth vs float64", depth.grad, comp["grad_depth"], comp["Ugrad"],
+               cap=9 + C + S + 6, exempt=f["bwd"].any(dim=1), coarse=comp["coarse"] + kb[("ssim_bwd", "grad")] * R.EPS * comp["Ugrad"])
 
 
 def test_ssim_module_matches_oracle_and_autograd():
@@ -60,6 +85,9 @@ def test_ssim_module_matches_oracle_and_autograd():
     rel = ((bg.grad.cpu() - bc.grad).abs().sum() / bc.grad.abs().sum()).item()
     print(f"[parity] SSIM: value max abs {(got.detach().cpu() - want.detach()).abs().max().item():.2e}, grad rel-L1 {rel:.2e}", flush=True)
     assert rel <= 1e-4
+    r, gb = R.ssim(a, b, 3), R.ssim_bwd(a, b, go, 3)              # per element against float64 (the fp32 oracle above is the looser yardstick)
+    PC.compare(("ssim", "out"), "SSIM module vs float64", got, r["out"], r["U"])
+    PC.compare(("ssim_bwd", "grad"), "SSIM module gradient vs float64", bg.grad, gb["grad"], gb["U"])
 
 
 def test_get_flow_from_depthmap_matches_oracle():
@@ -70,6 +98,15 @@ def test_get_flow_from_depthmap_matches_oracle():
     assert (got_z.cpu() - want_z).abs().max().item() <= 1e-4
     assert ((got_f.cpu() - want_f).abs() > 1e-4).float().mean().item() <= 1e-4       # z ~ 0 pixels may flip to -10
     assert (want_f == -10).float().mean().item() > 0.2
+    from wild_deep_mvs_amd import ops
+    inv_ref = ops.inv_proj4x4(proj[:, 0].float().cuda().contiguous()).cpu()
+    fl = R.flows(sc["depths"][0], inv_ref, proj[:, 1:].float())    # per element against float64; only q_z ~ 0 pixels may flip to -10
+    fr = R.fragile(sc["depths"][0], inv_ref, proj[:, 1:].float())["fwd"]
+    assert float(fr.double().mean()) <= R.FRAGILE_CAP
+    ref_f = torch.stack((fl["gx"], fl["gy"]), dim=-1)
+    PC.compare(("photo_warp", "z"), "get_flow_from_depthmap z vs float64", got_z, fl["z"], fl["Uz"])
+    PC.compare(("photo_warp", "flows"), "get_flow_from_depthmap flows vs float64", got_f, ref_f, torch.stack((fl["Ugx"], fl["Ugy"]), dim=-1),
+               exempt=fr.unsqueeze(-1).expand_as(ref_f), coarse=(ref_f + 10.0).abs() + 1e-3)
 
 
 def _masked_worker(rank, world, port, q):

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _photo_cmp as PC
 from _util import check_close, load_golden, t
 
 pytestmark = pytest.mark.gpu
@@ -749,7 +750,13 @@ def test_function_level_warps_are_differentiable():
     s2 = src.detach().clone().cuda().requires_grad_(True)
     got = hw_vis(s2, H.cuda(), (16, 24))
     got.backward(gv.cuda())
-    check_close("vis homography_warping", got.detach().cpu(), ref.detach(), max_abs=3e-4)
+    # the same sampling rule through the fused sweep (one matrix per item): the output per element against the float64 reference of
+    # tests/_photo_ref.py, and the fp32 oracle at the bound these near-identity matrices give (about 1e-4), not the 3e-4 of before.
+    # The input gradient here comes from the sweep family's backward (pscv_warp_cost_bwd), whose own float64 reference and unit live
+    # in tests/test_gpu_warp_bwd.py: it keeps its rel_l2 bar below and is not held to homography_warp_bwd_kernel's bound.
+    tight = PC.homography_call("vis homography_warping", got.detach().cpu(), ref.detach(), src, H, (16, 24))
+    assert tight <= 3e-4, tight
+    check_close("vis homography_warping", got.detach().cpu(), ref.detach(), max_abs=tight)
     check_close("vis homography_warping d src", s2.grad.cpu(), src.grad, rel_l2=2e-4)
 
 

@@ -31,8 +31,9 @@ __device__ __forceinline__ FlowGeom flow_geom(const float* __restrict__ inv_ref,
     float gx = 2.0f * fx / (float)(w - 1) - 1.0f, gy = 2.0f * fy / (float)(h - 1) - 1.0f;
     const bool behind = q[2] <= 0.0f;
     if (behind) gx = gy = -10.0f;
-    g.gx = fminf(fmaxf(gx, -10.0f), 10.0f);
-    g.gy = fminf(fmaxf(gy, -10.0f), 10.0f);
+    if (q[2] != q[2]) gx = gy = q[2];        // torch.clamp(min=1e-6) hands a NaN depth on (fmaxf drops it): both coordinates are NaN
+    g.gx = gx != gx ? gx : fminf(fmaxf(gx, -10.0f), 10.0f);       // torch.clamp propagates NaN, fminf / fmaxf return the bound
+    g.gy = gy != gy ? gy : fminf(fmaxf(gy, -10.0f), 10.0f);
     g.dgx = g.dgy = 0.0f;
     if (want_grad && !behind) {
         const float dp[3] = {x, y, 1.0f};
@@ -49,6 +50,9 @@ __device__ __forceinline__ FlowGeom flow_geom(const float* __restrict__ inv_ref,
     }
     return g;
 }
+// A NaN coordinate has no texel: the sample and the depth gradient are NaN, as grid_sample and its backward give (trainer.py:227's
+// mask is 0 there, every comparison with NaN being false).  Callers test this before grid_taps, which must not see a NaN.
+__device__ __forceinline__ bool nan_pos(const FlowGeom& g) { return g.gx != g.gx || g.gy != g.gy; }
 
 struct Taps {
     int x0, y0;
@@ -86,6 +90,12 @@ __global__ __launch_bounds__(256) void photo_warp_kernel(const float* __restrict
     if (mask) mask[i] = (g.gx < 1.0f && g.gy < 1.0f && g.gx > -1.0f && g.gy > -1.0f) ? 1.0f : 0.0f;     // trainer.py:227
     if (z_src) z_src[i] = g.z;
     if (flows) { flows[2 * i] = g.gx; flows[2 * i + 1] = g.gy; }
+    if (nan_pos(g)) {
+        if (warped)
+            for (int c = 0; c < C; ++c) warped[(bs * C + c) * hw + pix] = g.gx + g.gy;
+        if (warped_depth) warped_depth[i] = g.gx + g.gy;
+        return;
+    }
     const Taps t = grid_taps(g.gx, g.gy, h, w);
     const float w00 = (1.f - t.ax) * (1.f - t.ay), w01 = t.ax * (1.f - t.ay), w10 = (1.f - t.ax) * t.ay, w11 = t.ax * t.ay;
     const long o00 = (long)t.y0 * w + t.x0;
@@ -126,6 +136,7 @@ __global__ __launch_bounds__(256) void photo_warp_bwd_kernel(const float* __rest
     for (int s = 0; s < S; ++s) {
         const long bs = (long)b * S + s;
         const FlowGeom g = flow_geom(inv_ref + b * 16, proj + bs * 16, (float)x, (float)y, d, h, w, true);
+        if (nan_pos(g)) { acc += g.gx + g.gy; continue; }
         if (g.dgx == 0.0f && g.dgy == 0.0f) continue;
         const Taps t = grid_taps(g.gx, g.gy, h, w);
         const long o00 = (long)t.y0 * w + t.x0;
@@ -180,8 +191,9 @@ __device__ __forceinline__ SsimTerms ssim_terms(const float* m) {
     const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2, B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
     SsimTerms t;
-    const float inv = 1.0f / (B1 * B2);
-    t.S = A1 * A2 * inv;                                                                 // ssimLoss.py:42
+    const float den = B1 * B2, inv = 1.0f / den;
+    t.S = A1 * A2 / den;      // ssimLoss.py:42.  A division, not `* inv`: S is exactly 1 (the loss exactly 0) where numerator and
+                              // denominator are the same number -- all-zero images: (C1 C2) / (C1 C2) -- as in the reference
     t.dmu2 = 2.f * mu1 * (A2 - A1) * inv - 2.f * mu2 * t.S / B1 + 2.f * mu2 * t.S / B2;
     t.de22 = -t.S / B2;
     t.de12 = 2.f * A1 * inv;
