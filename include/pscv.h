@@ -668,6 +668,58 @@ int pscv_mesh_vertex_normals(const float* xyz, const int* faces, const int* corn
                              long n_vertices, float* normals, void* stream);
 
 /*
+ * Mesh metrics (an addition to ABI 14: new exports only, no existing signature changes): surface samples proportional to area and
+ * the exact bounded distance from points to the surface of an indexed triangle mesh, the step that lets evaluation/metrics.py
+ * score a mesh against a ground-truth cloud (csrc/mesh_metrics.hip).  xyz device fp32 [n_vertices][3],
+ * faces device int32 [n_faces][3]; n_vertices < 2^31, 3 n_faces < 2^31; either may be 0.  A face with an index outside
+ * [0, n_vertices) is never followed: it gives no sample and no distance.  Every value is fp64 from the fp32 coordinates, every
+ * product and sum rounded once in the order section 2r writes down.  All calls are asynchronous on `stream`; every result is
+ * bit-reproducible (the only atomics are the integer ones of the grid build, and no result depends on their order).
+ *
+ * Hash: mix(k) is the splitmix64 finaliser, step(x) = mix(x + 0x9e3779b97f4a7c15) on 64-bit words, unit(h) = (h >> 11) * 2^-53.
+ * h_f = step(step(seed) ^ f);  h_fk = step(h_f ^ (k + 1)).
+ *
+ * pscv_mesh_sample_count: n_f = floor(A_f / spacing^2 + unit(h_f)) with A_f = 0.5 * sqrt(n . n), n = (b - a) x (c - a); 0 for a
+ *   face that is not valid or whose area is 0 or not finite; saturated at 2^31 - 1.  offsets device int32 [n_faces] = the
+ *   exclusive scan of n_f (saturated at 2^31 - 1; exact whenever the total fits), *total device int64 = the sum.
+ *   workspace: pscv_mesh_scan_workspace(n_faces) bytes.  `seed` carries 64 bits.
+ * pscv_mesh_sample_emit: sample i (face-major, k ascending inside a face; its face found by binary search in `offsets`) is
+ *   a + u (b - a) + v (c - a) rounded to fp32, u = unit(h_fk), v = unit(step(h_fk)), both replaced by 1 - u, 1 - v when
+ *   u + v > 1.  out device fp32 [n_samples][3]; face_out device int32 [n_samples] or NULL.  n_samples = *total <= 2^31 - 2.
+ *
+ * Grid of a mesh: every valid face is binned into every cell (edge `cell`, from the origin, 21 bits per axis; the caller keeps
+ * the vertices within 2^21 cells of the origin) that its bounding box touches.
+ * pscv_mesh_grid_count: pair_off device int32 [n_faces] = the exclusive scan of the cells per face, *total device int64 = the
+ *   number of (cell, face) pairs.  workspace: pscv_mesh_scan_workspace(n_faces) bytes.
+ * pscv_mesh_grid_build: groups the n_pairs = *total <= 2^31 - 1 pairs by cell as pscv_point_grid_build groups points (hash table
+ *   of >= 2 n_pairs slots, counts, scan, scatter) into `grid`, a device buffer of pscv_mesh_grid_workspace(n_pairs) bytes whose
+ *   first 4 bytes hold the number of occupied cells (uint32).  Same origin and cell as the count.
+ *
+ * pscv_mesh_point_dist: out[i] = sqrt(d2) and face_out[i] (may be NULL) = f for the lexicographically smallest (d2, f) over the
+ *   valid faces with d2 < maxdist^2 (strict), d2 the squared distance from query i to face f; +inf and -1 when there is none.
+ *   Per face: with n = (b - a) x (c - a) and n . n > 0, when the three edge functions ((b - a) x (q - a)) . n,
+ *   ((c - b) x (q - b)) . n, ((a - c) x (q - c)) . n are all >= 0, d2 = ((q - a) . n)^2 / (n . n); otherwise the minimum over
+ *   the edges ab, bc, ca of |w - t d|^2, d = p1 - p0, w = q - p0, t = clamp((w . d) / (d . d), 0, 1), t = 0 when d . d = 0.
+ *   The search visits rings 0..fine_rings of the fine grid, then rings 0..coarse_rings of the coarse grid of the same mesh (same
+ *   origin; coarse_rings * coarse_cell >= maxdist + coarse_cell); a cell is skipped and the rings stop only when the bound lies
+ *   strictly beyond the best d2, so no result depends on the cell sizes.  query device fp32 [m][3], finite.
+ */
+long pscv_mesh_scan_workspace(long n_faces);
+int pscv_mesh_sample_count(const float* xyz, const int* faces, long n_faces, long n_vertices, double spacing, long seed,
+                           int* offsets, long long* total, void* workspace, long workspace_bytes, void* stream);
+int pscv_mesh_sample_emit(const float* xyz, const int* faces, const int* offsets, long n_faces, long n_vertices, long seed,
+                          long n_samples, float* out, int* face_out, void* stream);
+int pscv_mesh_grid_count(const float* xyz, const int* faces, long n_faces, long n_vertices, double ox, double oy, double oz,
+                         double cell, int* pair_off, long long* total, void* workspace, long workspace_bytes, void* stream);
+long pscv_mesh_grid_workspace(long n_pairs);
+int pscv_mesh_grid_build(const float* xyz, const int* faces, const int* pair_off, long n_faces, long n_vertices, double ox,
+                         double oy, double oz, double cell, long n_pairs, void* grid, long grid_bytes, void* stream);
+int pscv_mesh_point_dist(const float* query, long m, const float* xyz, const int* faces, long n_faces, long n_vertices,
+                         const void* fine, long fine_pairs, const void* coarse, long coarse_pairs, double ox, double oy, double oz,
+                         double fine_cell, double coarse_cell, int fine_rings, int coarse_rings, double maxdist, double* out,
+                         int* face_out, void* stream);
+
+/*
  * Scene set-up from a COLMAP sparse model (an addition to ABI 14: new exports only, no existing signature changes): what
  * utils/colmap_utils.py:compute_src_imgs and compute_min_max_depth_yao compute for every YFCC scene (INTEGRATION.md section 2i,
  * csrc/scene_setup.hip).  All arrays are device memory; all calls are asynchronous on `stream`, need no workspace and are

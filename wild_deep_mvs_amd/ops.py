@@ -2239,6 +2239,184 @@ def nn_dist(query: torch.Tensor, target: torch.Tensor, maxdist: float, bb=None, 
 
 
 # --------------------------------------------------------------------------------------------
+# mesh metrics: surface samples proportional to area, bounded distance to the surface
+# --------------------------------------------------------------------------------------------
+MESH_MAX_SAMPLES = 2 ** 31 - 2
+MESH_MAX_PAIRS = 2 ** 31 - 1
+
+
+def _mesh_spacing(spacing, what):
+    try:
+        s = float(spacing)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if isinstance(spacing, bool) or not (s > 0.0 and np.isfinite(s) and 0.0 < s * s < float("inf")):
+        raise ValueError(f"{what}: spacing must be a positive number with a finite, non-zero square, got {spacing!r}")
+    return s
+
+
+def _mesh_seed(seed, what):
+    """Any integer, taken modulo 2^64 -> the signed 64-bit word the C ABI carries it in."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"{what}: seed must be an integer, got {seed!r}")
+    s = int(seed) & (2 ** 64 - 1)
+    return s - 2 ** 64 if s >= 2 ** 63 else s
+
+
+def _mesh_sample_total(total, spacing, what):
+    if total > MESH_MAX_SAMPLES:
+        raise ValueError(f"{what}: spacing {spacing} gives {total} samples, more than 2^31 - 2: use a larger spacing")
+    return int(total)
+
+
+def _mesh_pair_total(total, cell, what):
+    if total > MESH_MAX_PAIRS:
+        raise ValueError(f"{what}: cells of {cell} give {total} (cell, face) pairs, more than 2^31 - 1: use a larger cell")
+    return int(total)
+
+
+def _mesh_cloud_shapes(what, **clouds):
+    for name, pts in clouds.items():
+        if not torch.is_tensor(pts) or pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"pscv.{what}: {name} must be an fp32 tensor [n,3], got {getattr(pts, 'dtype', type(pts))} "
+                             f"{tuple(getattr(pts, 'shape', ()))}")
+
+
+def _mesh_points(what, **clouds):
+    """Finite float32 [n,3] clouds: a host tensor's finiteness is checked here, so that the complaint is a named ValueError that
+    needs no device; then the ``_points`` check of each cloud (device, contiguity, finiteness on the device)."""
+    for name, pts in clouds.items():
+        if not pts.is_cuda and pts.numel() and not bool(torch.isfinite(pts).all()):
+            raise ValueError(f"pscv.{what}: {name} must be finite")
+    return [_points(pts, what) for pts in clouds.values()]
+
+
+def mesh_sample(xyz: torch.Tensor, faces: torch.Tensor, spacing: float, *, seed: int = 0, return_faces: bool = False):
+    """Deterministic samples of the surface of an indexed triangle mesh, on average one per ``spacing``^2 of area (INTEGRATION.md
+    section 2r): xyz fp32 [V,3], faces int32 [F,3] on the GPU -> fp32 [N,3], and with ``return_faces`` the face int32 [N] each
+    sample lies on.  Face f gets floor(A_f / spacing^2 + r_f) samples (fp64 area, r_f in [0,1) from a splitmix64 hash of
+    (seed, f): stochastic rounding, so faces far smaller than spacing^2 still get their share); a face with zero or non-finite area
+    or an index out of range gets none.  The output is face-major; sample k of face f is a + u (b - a) + v (c - a) with (u, v) from
+    the hash of (seed, f, k), folded into the triangle.  Integer scan, no float atomics: the same bits on every call.  One host
+    read (N); more than 2^31 - 2 samples is a ValueError that names the spacing."""
+    what = "pscv.mesh_sample"
+    V = _mesh_vertices(xyz, None, None, what)
+    F, V = _mesh_faces(faces, V, what)
+    spacing = _mesh_spacing(spacing, what)
+    seed = _mesh_seed(seed, what)
+    _mesh_on_gpu(what, xyz=xyz, faces=faces)
+    dev = xyz.device
+    lib, st = L.lib(), _stream()
+    n = 0
+    if F:
+        ws_bytes = int(lib.pscv_mesh_scan_workspace(F))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(F, dtype=torch.int32, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        rc = _launch("mesh_sample_count", lambda: lib.pscv_mesh_sample_count(_p(xyz), _p(faces), F, V, spacing, seed, _p(offsets), _p(total),
+                                                                             _p(ws), ws_bytes, st),
+                     cost=lambda: (F * (12.0 + 36.0 + 12.0), F * 30.0))
+        L.check(rc, "pscv_mesh_sample_count")
+        n = _mesh_sample_total(int(total.item()), spacing, what)        # the one host read
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face_out = torch.empty(n, dtype=torch.int32, device=dev) if return_faces else None
+    if n:
+        rc = _launch("mesh_sample_emit", lambda: lib.pscv_mesh_sample_emit(_p(xyz), _p(faces), _p(offsets), F, V, seed, n, _p(out), _p(face_out),
+                                                                           st),
+                     cost=lambda: (n * (12.0 + 36.0 + 12.0 + (4.0 if return_faces else 0.0)), n * 12.0))
+        L.check(rc, "pscv_mesh_sample_emit")
+    return (out, face_out) if return_faces else out
+
+
+@dataclass
+class MeshGrid:
+    """A sparse uniform grid over the faces of a mesh built by pscv_mesh_grid_build: every face in every cell its bounding box
+    touches; ``pairs`` (cell, face) pairs in ``buf``."""
+    buf: torch.Tensor
+    pairs: int
+    origin: tuple
+    cell: float
+
+
+def _mesh_grid(xyz, faces, F, V, origin, cell, what) -> MeshGrid:
+    dev = xyz.device
+    lib, st = L.lib(), _stream()
+    ws_bytes = int(lib.pscv_mesh_scan_workspace(F))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    pair_off = torch.empty(F, dtype=torch.int32, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    rc = _launch("mesh_grid_count", lambda: lib.pscv_mesh_grid_count(_p(xyz), _p(faces), F, V, origin[0], origin[1], origin[2], cell,
+                                                                     _p(pair_off), _p(total), _p(ws), ws_bytes, st))
+    L.check(rc, "pscv_mesh_grid_count")
+    pairs = _mesh_pair_total(int(total.item()), cell, what)
+    nbytes = int(lib.pscv_mesh_grid_workspace(pairs))
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rc = _launch("mesh_grid_build", lambda: lib.pscv_mesh_grid_build(_p(xyz), _p(faces), _p(pair_off), F, V, origin[0], origin[1], origin[2],
+                                                                     cell, pairs, _p(buf), nbytes, st))
+    L.check(rc, "pscv_mesh_grid_build")
+    return MeshGrid(buf, pairs, origin, cell)
+
+
+def _mesh_cells(xyz, faces, V, maxdist, cell):
+    """(origin, fine cell, coarse cell) of the two grids of a mesh: fine cells of twice the mean bounding-box side of the faces (or
+    ``cell``), coarse cells of maxdist / 4 and no smaller than the fine ones; both at least the 21-bit span allows."""
+    lo, hi = _extent(xyz)
+    floor_cell = (float((hi - lo).max()) + 1e-6) / (GRID_SPAN - 8)
+    if cell is not None:
+        fine = max(float(cell), floor_cell)
+    else:
+        idx = faces.long()
+        tri = xyz[idx[((idx >= 0) & (idx < V)).all(dim=1)]]                  # [valid faces, 3 corners, 3]
+        side = float((tri.amax(dim=1) - tri.amin(dim=1)).amax(dim=1).double().mean()) if tri.shape[0] else 0.0
+        fine = max(2.0 * side, floor_cell)
+    coarse = max(maxdist / 4.0, fine)
+    return tuple(float(v) - fine for v in lo), fine, coarse            # (one fine cell of margin: every vertex stays inside the span)
+
+
+def mesh_dist(query: torch.Tensor, xyz: torch.Tensor, faces: torch.Tensor, maxdist: float, *, return_faces: bool = False,
+              cell: Optional[float] = None):
+    """Exact bounded distance from points to the surface of an indexed triangle mesh: query fp32 [m,3],
+    xyz fp32 [V,3], faces int32 [F,3] on the GPU -> float64 [m]: the distance to the nearest point of any triangle when it is
+    strictly below ``maxdist``, +inf otherwise (``nn_dist`` without ``bb``; maxdist = inf is allowed).  With ``return_faces`` also
+    int32 [m]: the face that attains the minimum, the lowest index among equals ((d^2, face) compared lexicographically), -1 where
+    the distance is inf.  Per face the squared plane distance when the projection falls inside the triangle, otherwise the nearest
+    of its three edges, in fp64 from the fp32 coordinates: degenerate faces (a segment, a point) need no special case; a face with
+    an index out of range is skipped.  The index is a fine and a coarse uniform grid over the faces (``cell`` overrides the fine
+    edge); no result depends on the cell sizes or on the order of the build's atomics.  Queries and vertices must be finite."""
+    what = "mesh_dist"
+    _mesh_cloud_shapes(what, query=query, xyz=xyz)
+    F, V = _mesh_faces(faces, int(xyz.shape[0]), f"pscv.{what}")
+    try:
+        maxdist = float(maxdist)
+    except (TypeError, ValueError):
+        maxdist = float("nan")
+    if not maxdist > 0.0:
+        raise ValueError(f"pscv.{what}: maxdist {maxdist} must be positive")
+    if cell is not None and not (isinstance(cell, (int, float, np.integer, np.floating)) and not isinstance(cell, bool)
+                                 and 0.0 < float(cell) < float("inf")):
+        raise ValueError(f"pscv.{what}: cell must be a positive, finite number, got {cell!r}")
+    query, xyz = _mesh_points(what, query=query, xyz=xyz)
+    _mesh_on_gpu(f"pscv.{what}", query=query, xyz=xyz, faces=faces)
+    m, dev = int(query.shape[0]), query.device
+    out = torch.full((m,), float("inf"), dtype=torch.float64, device=dev)
+    face_out = torch.full((m,), -1, dtype=torch.int32, device=dev) if return_faces else None
+    if m and F and V:
+        if np.isinf(maxdist):
+            # no distance between the queries and the mesh reaches their joint bounding-box diagonal: a finite bound, same results
+            lo, hi = _extent(query, xyz)
+            maxdist = float(np.linalg.norm(hi - lo)) * 2.0 + 1.0
+        origin, fine_cell, coarse_cell = _mesh_cells(xyz, faces, V, maxdist, cell)
+        fine = _mesh_grid(xyz, faces, F, V, origin, fine_cell, f"pscv.{what}")
+        coarse = _mesh_grid(xyz, faces, F, V, origin, coarse_cell, f"pscv.{what}")
+        coarse_rings = int(np.ceil(maxdist / coarse_cell)) + 1
+        rc = _launch("mesh_point_dist", lambda: L.lib().pscv_mesh_point_dist(
+            _p(query), m, _p(xyz), _p(faces), F, V, _p(fine.buf), fine.pairs, _p(coarse.buf), coarse.pairs, origin[0], origin[1], origin[2],
+            fine_cell, coarse_cell, 2, coarse_rings, maxdist, _p(out), _p(face_out), _stream()))
+        L.check(rc, "pscv_mesh_point_dist")
+    return (out, face_out) if return_faces else out
+
+
+# --------------------------------------------------------------------------------------------
 # fused warp + cost
 # --------------------------------------------------------------------------------------------
 def warp_cost(ref: Optional[torch.Tensor], srcs: Sequence[torch.Tensor], cams: torch.Tensor, depth: torch.Tensor, *,
