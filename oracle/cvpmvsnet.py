@@ -143,11 +143,13 @@ def cost_reg_net(x, sd: SD, p: str = "model.cost_reg_refine", taps: Optional[dic
     return logits
 
 
-def cal_depth_hypo(ref_depths, ref_in, src_in, ref_ex, src_ex, depth_min, depth_max):
+def cal_depth_hypo(ref_depths, ref_in, src_in, ref_ex, src_ex, depth_min, depth_max, want_interval: bool = False):
     """Eval-mode hypothesis maps, ``calDepthHypo`` modules.py:131-226: the depth interval that moves the projection in
     the FIRST source view by one pixel along the epipolar line (fp64, per batch item, MEDIAN over valid pixels), then
-    8 planes ``depth + k * interval`` for k = -4..3.  ref_depths [B,H,W]; src_in [B,N,3,3]; src_ex [B,N,4,4]."""
+    8 planes ``depth + k * interval`` for k = -4..3.  ref_depths [B,H,W]; src_in [B,N,3,3]; src_ex [B,N,4,4].
+    ``want_interval``: also the float64 intervals [B] themselves (the planes only hold them rounded into an fp32 sum)."""
     d = 4
+    intervals = []
     B, H, W = ref_depths.shape
     ri, si = ref_in.double(), src_in.double()
     re, se = ref_ex.double(), src_ex.double()
@@ -183,9 +185,10 @@ def cal_depth_hypo(ref_depths, ref_in, src_in, ref_ex, src_ex, depth_min, depth_
         else:
             delta = (depth_max - depth_min) / 128 * torch.ones_like(X1_d)
         interval = torch.abs(delta).median()
+        intervals.append(interval.double().reshape(()))
         for k in range(-d, d):
             hypos[b, k + d] += k * interval
-    return hypos.float()
+    return (hypos.float(), torch.stack(intervals)) if want_interval else hypos.float()
 
 
 def forward(imgs, K, R, t, depth_min, depth_max, sd: SD, nscale: int = 2, training_hypos: bool = False,

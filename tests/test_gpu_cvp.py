@@ -120,6 +120,15 @@ def test_cal_depth_hypo_kernel_vs_oracle(env, case):
     step_want = (want[:, 5] - want[:, 4]).reshape(B, -1)[:, 0]
     print(f"[cal_depth_hypo] {case}: steps {step_want.tolist()}")
     check_close(f"calDepthHypo {case}", got.cpu(), want, max_abs=2e-6)
+    # the median itself and every plane against the float64 reference (tests/_depth_hypo_ref.py), constants built on the host
+    import numpy as np
+    import _depth_hypo_ref as DR
+    d_np, cams, fb = DR.inputs({"depth": depth, "ref_in": K[:, 0], "src_in": K[:, 1:], "ref_ex": ref_ex, "src_ex": src_ex, "dmin": dmin, "dmax": dmax})
+    hyp, steps = ops.cvp_depth_hypos(depth.cuda(), torch.from_numpy(cams).cuda(), torch.from_numpy(fb).cuda(), want_steps=True)
+    r = DR.reference(d_np, cams, fb)
+    worst = DR.check_steps(f"calDepthHypo {case}", steps.cpu().numpy(), r)
+    print(f"[parity] calDepthHypo {case}: n_valid {r['n_valid'].tolist()}, step distance {worst:.3f} of the bar {DR.STEP_BAR:.2e}", flush=True)
+    DR.check_planes(f"calDepthHypo {case}", hyp.cpu().numpy(), r)
 
 
 def test_cvp_cams_one_launch_equals_tensor_level_camera_algebra(env):
