@@ -240,7 +240,8 @@ def perturbed_hypothesis(Kinv, rows, cols, w, d, n, depth_min, depth_max, delta,
     u_p = pm_uniform(seed, view, pix, iteration, colour, SLOT_PHI)
     u_a = pm_uniform(seed, view, pix, iteration, colour, SLOT_ALPHA)
     u_d = pm_uniform(seed, view, pix, iteration, colour, SLOT_DEPTH)
-    axis = np.where((np.abs(n[:, 0]) < 0.9)[:, None], np.array([1.0, 0.0, 0.0]), np.array([0.0, 1.0, 0.0]))
+    # 0.9 as the fp32 number the kernel compares with: the two differ only for |n_x| = 0.9f exactly
+    axis = np.where((np.abs(n[:, 0]) < float(np.float32(0.9)))[:, None], np.array([1.0, 0.0, 0.0]), np.array([0.0, 1.0, 0.0]))
     e1 = np.cross(n, axis)
     e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
     e2 = np.cross(n, e1)

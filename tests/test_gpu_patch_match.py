@@ -1,7 +1,9 @@
 """GPU: PatchMatch stereo (csrc/patch_match.hip) against the numpy rule of tests/_patch_match_ref.py.
-Costs to 1e-4 with exact invalid flags; half-steps with identical candidates and the same choice wherever the oracle's best two
-costs are 1e-3 apart; determinism; the accuracy bars on make_patch_match_scene after the geometric pass and the filter; the
-geometric pass's gain; the filter against the oracle; the evaluation/colmap_stereo.py mirror; every limit."""
+Costs to 1e-4 with exact invalid flags (grazing planes to their derived bound); half-steps with identical candidates, the same
+choice wherever the oracle's best two costs are 1e-3 apart and a regret inside the derived bounds at every pixel; determinism; the
+accuracy bars on make_patch_match_scene after the geometric pass and the filter; the geometric pass's gain; the filter against
+the oracle, every pixel's count inside its decided range; the evaluation/colmap_stereo.py mirror; every limit.  The per-entry
+checks with derived bounds at every shape, window and source count are in tests/test_gpu_patch_match_ref.py."""
 import math
 from argparse import Namespace
 
@@ -9,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import _patch_match_bounds as PB
 from tests import _patch_match_ref as PR
 
 pytestmark = pytest.mark.gpu
@@ -78,7 +81,7 @@ def test_cost_matches_oracle_with_every_invalid_class(env):
     inv_o, inv_k = oc == 2.0, kc == 2.0
     assert np.array_equal(inv_o[~near], inv_k[~near])
     # fp32 homographies lose precision on planes seen within ~6 deg of grazing (|cos| of normal and ray < 0.1): the taps' positions
-    # cancel there; the invalid flags above still cover them
+    # cancel there; the flat 1e-4 bar holds away from them, and they are held to their own derived bound below
     ray = np.stack([cols, rows, np.ones(h * w)], -1) @ np.linalg.inv(K0).T
     cosv = np.abs((state[..., 1:].reshape(-1, 3) * ray).sum(1)) / np.linalg.norm(ray, axis=1)
     ok = ~near & ~inv_o & (cosv >= 0.1)[None]
@@ -87,6 +90,12 @@ def test_cost_matches_oracle_with_every_invalid_class(env):
     print(f"\n[patch_match] cost: max |dc| {dc[~near & ~inv_o].max():.2e} at source {worst[0]} (|cos| {cosv[worst[1]]:.3f}, "
           f"var_r {vr[worst[1]]:.2e}, var_s {vs[worst]:.2e}); {dc[ok].max():.2e} away from grazing planes, {ok.sum()} entries")
     assert dc[ok].max() <= 1e-4
+    cm = PB.cost_model(ref, imgs, cams_np.numpy(), rows, cols, state[..., 0].reshape(-1), state[..., 1:].reshape(-1, 3))
+    graz = cm["vdec"] & cm["valid"] & (cosv < 0.1)[None]
+    print(f"[patch_match] grazing planes: {graz.sum()} entries, worst |dc| / bound {(dc[graz] / (cm['cb'][graz] * PB.SCALE['cost'])).max():.3f}")
+    assert graz.sum() > 100 and (dc[graz] <= cm["cb"][graz] * PB.SCALE["cost"]).all()
+    dec = cm["vdec"]
+    assert np.array_equal(inv_k[dec], ~cm["valid"][dec])              # no band: every decided flag, the variance tests included
     # every invalid class occurs
     assert inv_o[2].all() and inv_o[3].mean() > 0.99             # behind; angle < 1 deg
     assert 0.05 < inv_o[4].mean() < 0.95                          # partly outside
@@ -106,7 +115,9 @@ def test_half_step_matches_oracle(env, S, geometric):
     dmin, dmax = float(sc["depth_min"][0]), float(sc["depth_max"][0])
     st0 = ops.patch_match_init(h, w, cams_v.cuda(), dmin, dmax, seed=5, view=7)
     init_o = PR.init_state(h, w, cams_v.numpy(), dmin, dmax, 5, 7)
-    assert np.allclose(st0.cpu().numpy(), init_o, rtol=1e-5, atol=1e-5)
+    init_v, init_b, init_dec = PB.init_model(h, w, cams_v.numpy(), dmin, dmax, 5, 7)
+    assert np.abs(init_v - init_o).max() <= 1e-9
+    assert (np.abs(st0.cpu().numpy() - init_v) <= init_b * PB.SCALE["init"])[init_dec].all()      # per element, derived
     # start from a half-converged state: ground truth on the left half, the random initialisation on the right
     state = st0.cpu().numpy()
     gt = np.concatenate([sc["depth"][0].numpy()[..., None], sc["normal"][0].numpy()], -1)
@@ -133,8 +144,15 @@ def test_half_step_matches_oracle(env, S, geometric):
         ch_k = choice.cpu().numpy()
         assert (ch_k[~mine] == -1).all()
         sure = mine & (gap > 1e-3) & ~amb
-        assert sure.mean() > 0.3 * mine.mean()
         assert np.array_equal(ch_k[sure], ch_o[sure])
+        # every pixel of the colour, sure or not: the chosen candidate's float64 cost is within the two bounds of the minimum, and
+        # among bit-identical candidates the lowest index was chosen
+        case = Namespace(ref=greys[0], srcs=[greys[s] for s in src], cams=cams_v.numpy(), radius=5, step=1, top_k=min(S, 3), h=h, w=w,
+                         sdepths=None if sd is None else [d.cpu().numpy() for d in sd])
+        from tests import _patch_match_cases as CS
+        res, _ = PB.check_choice(cd_k[mine], ch_k[mine], CS.agg_of(case, geometric, colour))
+        print(PB.fmt(f"S={S} geometric={geometric} colour={colour}", res))
+        assert not PB.failures(res), res
         # the written state is the chosen candidate
         ks = st.cpu().numpy()
         pick = np.take_along_axis(cd_k, np.clip(ch_k, 0, 10)[..., None, None], axis=2)[:, :, 0]
@@ -208,7 +226,10 @@ def test_filter_matches_oracle(env):
                                          [photo[s][..., 0].cpu().numpy() for s in src])
         keep_o = cnt_o >= PR.FILTER_MIN_CONSISTENT
         keep_k = depth[v] > 0
-        assert margin.mean() < 0.05
+        fm = PB.filter_model(geom[v].cpu().numpy(), greys[v], [greys[s] for s in src], cams[ids].numpy(),
+                             [photo[s][..., 0].cpu().numpy() for s in src])
+        res = PB.check_filter(fm, geom[v].cpu().numpy(), depth[v], normal[v], counts[v].cpu().numpy())
+        assert not PB.failures(res), res                        # every pixel: the count inside its decided range
         assert np.array_equal(keep_o[~margin], keep_k[~margin])
         assert np.array_equal(counts[v].cpu().numpy()[~margin], cnt_o[~margin])
         st = geom[v].cpu().numpy()
