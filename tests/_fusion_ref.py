@@ -1,9 +1,10 @@
 """numpy restatement of the depth-map fusion rule, the yardstick of csrc/depth_fusion.hip, and of the
 reference's ``utils/utils_ply.py:read_ply`` for the binary files the fusion step writes.
 
-Geometry is evaluated in float64 from the float32 inputs the kernel reads (depth maps, camera blocks [N,30] = K, K^-1, R, t), so
-the kernel's fp32 rounding is the only difference; ``fuse_pass`` also reports which pixels sit within that rounding of a decision
-(``fragile``), where the two may legitimately disagree."""
+Geometry is evaluated in float64 from the float32 inputs the kernel reads (depth maps, camera blocks [N,30] = K, K^-1, R, t, and the
+three thresholds as fp32 numbers), so the kernel's fp32 rounding is the only difference.  This is the plain statement of the rule;
+the kernel is held to tests/_fusion_bounds.py, which restates it with a derived rounding bound per step and evaluates every decision
+over its interval."""
 from __future__ import annotations
 
 import numpy as np
@@ -43,7 +44,9 @@ def cam_parts(cams):
 
 
 def valid(d, lo, hi):
-    return np.isfinite(d) & (d > lo) & (d < hi)
+    """finite and float32(lo) < d < float32(hi): the kernel holds its thresholds as fp32 numbers, so a depth equal to float32(1e-3),
+    which exceeds the double 1e-3, is not valid"""
+    return np.isfinite(d) & (d > float(np.float32(lo))) & (d < float(np.float32(hi)))
 
 
 def unproject(Ki, R, t, x, y, d):
@@ -52,13 +55,10 @@ def unproject(Ki, R, t, x, y, d):
     return (p - t) @ R
 
 
-def fuse_pass(i, depths, colors, cams, used, *, disp_thresh, num_consistent, depth_min=1e-3, depth_max=1e5, rel=1e-4):
+def fuse_pass(i, depths, colors, cams, used, *, disp_thresh, num_consistent, depth_min=1e-3, depth_max=1e5):
     """Pass i of the rule.  depths N x float32 [h,w], colors N x uint8 [h,w,3], cams [N,30], used N x uint8 [h,w] (NOT modified)
     -> dict: ``emit`` bool [h_i,w_i], ``xyz`` [h_i,w_i,3], ``rgb`` int [h_i,w_i,3] (valid where emit), ``n`` consistent views,
-    ``used`` the N masks after the pass, ``hits`` (j, consistent [h_i,w_i], qx, qy) per other view, ``fragile`` bool [h_i,w_i]: some view's test lies within rounding of its decision --
-    |disparity difference - threshold| below ``rel`` of the threshold (plus 2e-6 of the disparity f B / z itself: the fp32
-    rounding of the two disparities the kernel subtracts), a/z or b/z within ``rel`` of a half-integer, or z within 1e-5 of
-    zero."""
+    ``used`` the N masks after the pass, ``hits`` (j, consistent [h_i,w_i], qx, qy) per other view."""
     K, Ki, R, t = cam_parts(cams)
     N = len(depths)
     d = np.asarray(depths[i], dtype=np.float32).astype(np.float64)
@@ -71,7 +71,6 @@ def fuse_pass(i, depths, colors, cams, used, *, disp_thresh, num_consistent, dep
     S = np.zeros((h, w, 3))
     csum = np.asarray(colors[i]).astype(np.int64).copy()
     n = np.zeros((h, w), dtype=np.int64)
-    fragile = np.zeros((h, w), dtype=bool)
     hits = []
     for j in range(N):
         if j == i:
@@ -90,13 +89,7 @@ def fuse_pass(i, depths, colors, cams, used, *, disp_thresh, num_consistent, dep
         fb = f_i * np.linalg.norm(centre[i] - centre[j])
         with np.errstate(divide="ignore", invalid="ignore"):
             disp = np.abs(fb / z - fb / dj)
-        cons = ok & (disp < disp_thresh)
-        half = lambda a: np.abs(a - np.floor(a) - 0.5) < rel
-        with np.errstate(divide="ignore", invalid="ignore"):
-            fragile |= active & (np.abs(z) < 1e-5)
-            near = front & (fx >= -1) & (fx <= wj) & (fy >= -1) & (fy <= hj)      # (q or its rounding neighbour inside view j)
-            fragile |= near & (half(u) | half(v))
-            fragile |= ok & (np.abs(disp - disp_thresh) < rel * disp_thresh + 2e-6 * fb / np.abs(z))
+        cons = ok & (disp < float(np.float32(disp_thresh)))           # (the threshold as the kernel holds it: an fp32 number)
         Xj = unproject(Ki[j], R[j], t[j], qx.astype(np.float64), qy.astype(np.float64), dj)
         S += np.where(cons[..., None], Xj, 0.0)
         csum += np.where(cons[..., None], np.asarray(colors[j])[qy, qx].astype(np.int64), 0)
@@ -109,7 +102,7 @@ def fuse_pass(i, depths, colors, cams, used, *, disp_thresh, num_consistent, dep
     for j, cons, qx, qy in hits:
         m = emit & cons
         after[j][qy[m], qx[m]] = 1
-    return {"emit": emit, "xyz": xyz, "rgb": rgb, "n": n, "used": after, "fragile": fragile, "hits": hits}
+    return {"emit": emit, "xyz": xyz, "rgb": rgb, "n": n, "used": after, "hits": hits}
 
 
 def fuse_all(depths, colors, cams, **kw):
